@@ -3,6 +3,16 @@
 
 BASELINE.json metric "ICP iterations/sec + RANSAC hypotheses/sec, 100k↔100k pts, 1/2/4/8 GPU".
 
+A plain run (`--gpus N --steps K --warmup W`) does what the headline figure needs and no more: it
+builds the headline's pair and loop, runs W warm-up steps, times K steps once (no kernel events),
+writes `--dump-outputs DIR` if asked and prints the line; every other section of the line is null.
+`--full` adds every other leg described below: the second timed pass with kernel events and the
+rooflines from it, the grid NN, strong scaling, the cold calls, cfg3, RANSAC, the drop-in per-call
+path, cfg4 and the CPU baseline.  `--dump-outputs DIR` writes what the headline loop's caller holds
+after the last timed step (transformation, update, fitness, inlier_rmse, num_correspondences,
+iterations; N = 1 also correspondences and points) as DIR/<name>.npy, float64; the inputs are seeded
+(m3d.synth, seed 0), so two builds run with the same arguments can be compared array for array.
+
 * step (the timed unit of the headline) = one full cfg1 ICP run: 100k source ↔ 100k target
   points per GPU, 50 point-to-plane iterations (convergence disabled → exactly 50 updates, 51 NN
   evaluations), brute-force radius-bounded NN (r = 0.4·0.3), exact fp64 correspondences
@@ -100,6 +110,17 @@ def parse():
                     help="N>1 collectives: libm3d's RCCL communicator, or torch.distributed")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds per CPU baseline leg")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("M3D_BENCH_FULL") == "1",
+                    help="every leg beside the headline: the kernel-event pass and rooflines, grid "
+                         "NN, strong scaling, cold calls, cfg3, RANSAC, the drop-in per-call path, "
+                         "cfg4 and the CPU baseline (a plain run sets up, warms up, times --steps "
+                         "steps of the headline and prints the line).  M3D_BENCH_FULL=1 in the "
+                         "environment does the same, for a script that wraps several bench.py calls "
+                         "(tools/gpu.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline's last timed step left with "
+                         "its caller (the ICP result; N = 1: the correspondences and the points "
+                         "too) as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--launch-check", action="store_true",
                     help="bring up the ranks and the process group only, print the line with the "
                          "rank count and exit (no GPU work: the launcher's CPU test)")
@@ -157,6 +178,25 @@ def _g(d, *path):
 
 def _r(x, nd=4):
     return None if x is None else (round(x, nd) if isinstance(x, float) else x)
+
+
+DUMP_ARRAY_BYTES = 16 << 20  # per array; the headline leaves two large ones, so < 64 MB in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  An array above DUMP_ARRAY_BYTES
+    is cut down to a fixed sample of its rows (seed 0, increasing row order), the same rows in
+    every run of the same shape."""
+    import numpy as np
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            keep = DUMP_ARRAY_BYTES // (a.nbytes // len(a))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(d / f"{name}.npy", a)
 
 
 # the fields of `summary` (VERDICT r5 #5): the sub-legs the driver's truncated stdout tail must
@@ -345,11 +385,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def timed(fn, steps, kernels):
-        """(elapsed s of `steps` × fn without events, elapsed with events, {kernel: (ms, n)})."""
+    full = args.full
+
+    def timed(fn, steps, kernels, after_plain=None):
+        """(elapsed s of `steps` × fn without events, elapsed with events, {kernel: (ms, n)}).
+        The pass with events is --full's: without it (None, {}) stand in its place.  after_plain()
+        runs right after the pass without events (the headline's --dump-outputs)."""
         out = []
         prof = {}
-        for events in (False, True):
+        for events in (False, True) if full else (False,):
             ctx.profile(events)
             for k in kernels:
                 ctx.profile_read(k)
@@ -363,8 +407,25 @@ def main():
             out.append(max_over_ranks(time.perf_counter() - t0))
             if events:
                 prof = {k: ctx.profile_read(k) for k in kernels}
+            elif after_plain is not None:
+                after_plain()
             ctx.profile(False)
-        return out[0], out[1], prof
+        return out[0], (out[1] if full else None), prof
+
+    outputs = {}
+
+    def keep_outputs(loop):
+        """--dump-outputs: what the headline loop's caller holds after the last timed step — the
+        ICP result and, on one GPU, the correspondences and the transformed source points."""
+        if args.dump_outputs is None:
+            return
+        o = loop.result()
+        outputs.update(transformation=o.transformation, update=o.update, fitness=[o.fitness],
+                       inlier_rmse=[o.inlier_rmse], num_correspondences=[o.num_correspondences],
+                       iterations=[o.iterations])
+        if not multi:
+            outputs.update(correspondences=loop.correspondences().cpu().numpy(),
+                           points=loop.points().cpu().numpy())
 
     # ------------------------------------------------------------------ ICP loop runner
     def icp_runner(loop, iters, mode, off=0, ns_total=0):
@@ -438,7 +499,7 @@ def main():
                 "exchange_note": ("library RCCL all-reduces timed by events on their streams"
                                   if comm_name == "libm3d-rccl" else "exchange not issued by the library")}
 
-    def bench_icp(nn):
+    def bench_icp(nn, headline=False):
         loop = IcpLoop(src_c, tgt_c, r, relative_fitness=-1.0, relative_rmse=-1.0, max_iteration=iters, nn=nn)
         if mode1 == "source":
             loop.set_source_total(ns * world)
@@ -446,29 +507,37 @@ def main():
         for _ in range(args.warmup):
             run()
         torch.cuda.synchronize()
-        el, el_ev, prof = timed(run, args.steps, (K_NN, K_TERMS))
+        el, el_ev, prof = timed(run, args.steps, (K_NN, K_TERMS),
+                                (lambda: keep_outputs(loop)) if headline else None)
+        if not full:
+            return el, None, None, 0, None, loop.result()
         (nn_ms, nn_n), (t_ms, t_n) = prof[K_NN], prof[K_TERMS]
         return el, el_ev, max_over_ranks(nn_ms / max(nn_n, 1)), nn_n, t_ms / max(t_n, 1), loop.result()
 
-    el, el_ev, nn_avg_ms, nn_n, terms_avg_ms, res = bench_icp("brute")
-    icp_value = world * iters * args.steps / el
-    err = float(np.abs(res.transformation - T_true).max())
-    cfg1 = {
-        "value": icp_value, "ms_per_step": el / args.steps * 1e3,
-        "ms_per_step_with_kernel_events": el_ev / args.steps * 1e3,
-        "workload": (f"cfg1: {ns}<->{nt} synthetic pair per GPU, {iters} point-to-plane ICP "
-                     f"iterations, brute-force NN (r={r:g}), "
-                     + ("1 GPU" if not multi else
-                        (f"sources sharded over {world} GPUs ({ns} per GPU), target replicated (SUM terms)"
-                         if mode1 == "source" else
-                         f"target sharded over {world} GPUs ({nt} per GPU), sources replicated "
-                         "(MIN keys + MIN claims + SUM terms)"))),
-        "roofline": nn_roofline(ns, nt, nn_avg_ms, nn_n, terms_avg_ms),
-        "check": {"icp_fitness": res.fitness, "icp_rmse": res.inlier_rmse, "max_abs_err_vs_T_true": err},
-    }
+    def cfg1_section(el, el_ev, nn_avg_ms, nn_n, terms_avg_ms, res):
+        return {
+            "value": world * iters * args.steps / el, "ms_per_step": el / args.steps * 1e3,
+            "ms_per_step_with_kernel_events": None if el_ev is None else el_ev / args.steps * 1e3,
+            "workload": (f"cfg1: {ns}<->{nt} synthetic pair per GPU, {iters} point-to-plane ICP "
+                         f"iterations, brute-force NN (r={r:g}), "
+                         + ("1 GPU" if not multi else
+                            (f"sources sharded over {world} GPUs ({ns} per GPU), target replicated (SUM terms)"
+                             if mode1 == "source" else
+                             f"target sharded over {world} GPUs ({nt} per GPU), sources replicated "
+                             "(MIN keys + MIN claims + SUM terms)"))),
+            "roofline": nn_roofline(ns, nt, nn_avg_ms, nn_n, terms_avg_ms) if full else None,
+            "check": {"icp_fitness": res.fitness, "icp_rmse": res.inlier_rmse,
+                      "max_abs_err_vs_T_true": float(np.abs(res.transformation - T_true).max())},
+        }
+
+    # a plain run measures its headline only: cfg1's brute-force loop unless --config cfg3
+    cfg1 = res = None
+    if full or args.config == "cfg1":
+        el, el_ev, nn_avg_ms, nn_n, terms_avg_ms, res = bench_icp("brute", headline=args.config == "cfg1")
+        cfg1 = cfg1_section(el, el_ev, nn_avg_ms, nn_n, terms_avg_ms, res)
 
     icp_grid = None
-    if not args.no_grid:
+    if full and not args.no_grid:
         tg0 = time.perf_counter()
         IcpLoop(src_c, tgt_c, r, max_iteration=0, nn="grid")  # builds both clouds' grids once
         torch.cuda.synchronize()
@@ -498,11 +567,11 @@ def main():
     # (SURVEY §8(e) "ICP alternative"), value = ICP iterations/s of that one problem.  N = 1: the
     # headline run itself (the same workload), so SCALE's N = 1 line equals BENCH.
     cfg1_strong = None
-    if not multi:
+    if full and not multi:
         cfg1_strong = {"value": cfg1["value"], "ms_per_step": cfg1["ms_per_step"],
                        "grid_value": None if icp_grid is None else icp_grid["value"],
                        "note": "N = 1: the headline cfg1 run (same workload)"}
-    else:
+    elif full:
         s1, t1, n1, T1 = synth.icp_pair(ns, nt, seed=0)  # the N = 1 pair
         o1, c1 = D.shard_bounds(ns, world, rank)
         s1c, t1c = Cloud(s1[o1:o1 + c1]), Cloud(t1, n1)
@@ -537,12 +606,12 @@ def main():
     # between stages); plus the drop-in refine_registration on fresh Ply-likes (grid NN, Open3D's
     # default convergence criteria).
     cfg1_cold = None
-    if rank == 0 and world == 1:
+    if full and rank == 0 and world == 1:
         cfg1_cold = bench_cold(args, src, tgt_all[:nt], nrm_all[:nt], r, iters, reps=7)
 
     # ------------------------------------------------------------------ cfg3: 1M <-> 1M, strong
     cfg3 = None
-    if not args.no_cfg3 or args.config == "cfg3":
+    if (full and not args.no_cfg3) or args.config == "cfg3":
         n3, it3 = args.cfg3_n, args.cfg3_iters
         s3, t3, nr3, T3 = synth.icp_pair(n3, n3, seed=0)
         o3, c3 = D.shard_bounds(n3, world, rank)
@@ -568,12 +637,21 @@ def main():
                             f"{rank}), sources replicated, MIN fp64 keys + MIN claims + SUM terms per iteration",
                 "target_shards": shards3,
                 "steps": args.cfg3_steps, "icp_iterations_per_step": it3}
-        for nn in ("brute", "grid"):
+        for nn in ("brute", "grid") if full else ("brute",):
             lp = IcpLoop(s3c, t3c, r, relative_fitness=-1.0, relative_rmse=-1.0, max_iteration=it3, nn=nn)
             run = icp_runner(lp, it3, mode3, o3)
             run()
             torch.cuda.synchronize()
-            e3, e3_ev, prof = timed(run, args.cfg3_steps, (K_NN, K_TERMS, K_COMM))
+            e3, e3_ev, prof = timed(run, args.cfg3_steps, (K_NN, K_TERMS, K_COMM),
+                                    (lambda: keep_outputs(lp)) if nn == "brute" and args.config == "cfg3" else None)
+            if not full:  # the headline of a plain --config cfg3 run: no events pass, no roofline
+                r3 = lp.result()
+                cfg3.update({"value": it3 * args.cfg3_steps / e3,
+                             "ms_per_iteration": e3 / (it3 * args.cfg3_steps) * 1e3, "fitness": r3.fitness,
+                             "max_abs_err_vs_T_true": float(np.abs(r3.transformation - T3).max()),
+                             "roofline": None})
+                del lp
+                continue
             (m, n), (tm, tn) = prof[K_NN], prof[K_TERMS]
             avg = max_over_ranks(m / max(n, 1))
             r3 = lp.result()
@@ -611,12 +689,12 @@ def main():
         del s3c, t3c
         # the same pair from nothing (H2D + centring, grids, Morton copy, records; the 1M cold
         # path of refine_registration, which Open3D pays per call with its KD-tree build)
-        if rank == 0 and world == 1:
+        if full and rank == 0 and world == 1:
             cfg3["cold"] = bench_cold(args, s3, t3, nr3, r, it3, reps=2, nns=("grid",), tag="cfg3")
 
     # ------------------------------------------------------------------ cfg2: RANSAC
     ransac = None
-    if not args.no_ransac:
+    if full and not args.no_ransac:
         nc, H = args.nc, args.hyps
         rs_src, rs_tgt, corr, _ = synth.ransac_pair(nc, seed=42)
         cs = CorrSet(rs_src, rs_tgt, corr)
@@ -750,17 +828,17 @@ def main():
 
     # ------------------------------------------------------------------ drop-in per-call path
     ransac_api = None
-    if rank == 0 and world == 1 and not args.no_ransac_api:
+    if full and rank == 0 and world == 1 and not args.no_ransac_api:
         ransac_api = bench_ransac_api(args)
 
     # ------------------------------------------------------------------ cfg4: STL -> PLY -> register
     cfg4 = None
-    if rank == 0 and world == 1 and not args.no_cfg4:
+    if full and rank == 0 and world == 1 and not args.no_cfg4:
         cfg4 = bench_cfg4(args)
 
     # ------------------------------------------------------------------ CPU baseline
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(src, tgt_all[:nt], nrm_all[:nt], r, args, ransac is not None)
 
     if args.config == "cfg3":
@@ -790,8 +868,10 @@ def main():
                    "max_corr": r, "parallelism": "single" if not multi else f"{mode1}-shard x{world}",
                    "comm": comm_name, "comm_ranks": comm_ranks},
         "roofline": head["roofline"],
-        "ms_per_step_with_kernel_events": cfg1["ms_per_step_with_kernel_events"],
-        "cfg1": {k: v for k, v in cfg1.items() if k != "roofline"} if args.config == "cfg3" else None,
+        "full": full,  # False: the headline only, every other leg below is null
+        "ms_per_step_with_kernel_events": _g(cfg1, "ms_per_step_with_kernel_events"),
+        "cfg1": ({k: v for k, v in cfg1.items() if k != "roofline"}
+                 if args.config == "cfg3" and cfg1 is not None else None),
         "icp_grid": icp_grid,
         "cfg1_strong": cfg1_strong,
         "cfg1_cold": cfg1_cold,
@@ -801,10 +881,13 @@ def main():
         "ransac_api": ransac_api,
         "cfg4_synthetic": cfg4,
         "cpu_baseline": cpu,
-        "check": cfg1["check"],
+        "check": (cfg1["check"] if cfg1 is not None else
+                  {"icp_fitness": cfg3["fitness"], "max_abs_err_vs_T_true": cfg3["max_abs_err_vs_T_true"]}),
     }
     line["summary"] = build_summary(line)  # last: the part of the line a truncated tail keeps
     if rank == 0:
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     del comm
     if multi:

@@ -56,6 +56,41 @@ def test_single_gpu_launch_check_unchanged():
     assert json_lines(p.stdout)[0]["n_gpus"] == 1
 
 
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.delenv("M3D_BENCH_FULL", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs) == (True, "d")
+
+
+def test_dump_outputs_writes_float64_and_samples_a_large_array_the_same_way(tmp_path):
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    rows = 2 * bench.DUMP_ARRAY_BYTES // 24 + 5  # twice the per-array cap, an odd count
+    big = np.arange(rows * 3, dtype=np.float64).reshape(rows, 3)
+    arrays = {"t": np.eye(4), "count": [17], "idx": np.arange(9, dtype=np.int32), "big": big}
+    bench.dump_outputs(tmp_path / "a" / "b", arrays)  # creates the directory
+    bench.dump_outputs(tmp_path / "c", arrays)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a" / "b").glob("*.npy")}
+    assert set(got) == set(arrays) and all(v.dtype == np.float64 for v in got.values())
+    np.testing.assert_array_equal(got["idx"], np.arange(9))
+    assert got["count"].shape == (1,) and got["count"][0] == 17
+    s = got["big"]
+    assert s.shape == (bench.DUMP_ARRAY_BYTES // 24, 3) and s.nbytes <= bench.DUMP_ARRAY_BYTES
+    assert np.all(np.diff(s[:, 0]) > 0)  # distinct rows of the array, in its order
+    np.testing.assert_array_equal(s, big[(s[:, 0] / 3).astype(np.int64)])
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "big.npy"), s)
+
+
 def test_summary_is_the_last_key_and_survives_a_truncated_tail():
     """the JSON line ends with a compact `summary` of every sub-leg (grid, cold,
     strong, RANSAC, cfg3, ranks), so a driver that keeps only the last ~1,000 characters of stdout

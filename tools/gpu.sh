@@ -19,6 +19,9 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
+# every bench.py call below is the whole benchmark, as bench.py --full (a plain run times the
+# headline alone: no grid, cfg3, RANSAC, cold, cfg4 or CPU legs, no kernel events)
+export M3D_BENCH_FULL=1
 mkdir -p gpurun_out
 stop() { echo "stopping after $1 rc=$2"; exit "$2"; }
 pmc_run() {  # dir name "args" rocprof-args...
