@@ -552,6 +552,18 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// OR of v over the wave's 64 lanes (all active), wave-uniform: DPP inside each row of 16 lanes,
+// then the four rows by v_readlane.
+__device__ __forceinline__ uint32_t wave_or32(uint32_t v) {
+  int x = (int)v;
+  x |= __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false);   // lane ^ 1
+  x |= __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, false);   // lane ^ 2
+  x |= xor4_dpp(x);
+  x |= __builtin_amdgcn_mov_dpp(x, 0x128, 0xF, 0xF, false);  // row_ror:8
+  return (uint32_t)(__builtin_amdgcn_readlane(x, 0) | __builtin_amdgcn_readlane(x, 16) |
+                    __builtin_amdgcn_readlane(x, 32) | __builtin_amdgcn_readlane(x, 48));
+}
+
 __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(const float4* __restrict__ src32,
                                                           int64_t ns,
                                                           const uint4* __restrict__ tgt16,
@@ -672,10 +684,15 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         lds_dma16(tgt16 + (e / kTT) * nt_pad + j0 + tstep + e % kTT, &t16[buf ^ 1][e / kTT][(e % kTT) & ~63]);
       }
     }
-    // Sweep: MFMA + sign-OR test for the tile's sub-tiles, branch-free; a sub-tile that hits
-    // anywhere in the wave sets a bit of the wave-uniform mask (SALU).  Software-pipelined: the
-    // MFMA of step t+1 is issued before step t's tree, so a wave never waits on its own MFMA.
-    uint64_t hm = 0;
+    // Sweep: MFMA + sign-OR test for the tile's sub-tiles, branch-free.  A step records its sign
+    // bit in the lane's own shift register of its group (v_alignbit: rec = rec << 1 | sign), so
+    // the step is vector instructions only; the wave looks at the records once per tile.
+    // Software-pipelined: the MFMA of step t+1 is issued before step t's tree, so a wave never
+    // waits on its own MFMA.
+    static_assert(kSub == 32, "one 32-bit hit record per group and tile");
+    uint32_t rec[kMG];
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) rec[g] = 0;
     constexpr int kSteps = 8 * kMG;  // (sub-tile, group) steps of one half tile
 #pragma unroll
     for (int half = 0; half < kTH; ++half) {
@@ -693,10 +710,21 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         // whole MFMA latency every step and the matrix pipe idles under the tree)
         __builtin_amdgcn_sched_barrier(0);
         // a candidate's value is strictly negative: OR of the 16 bit patterns, test bit 31
-        const int g = t % kMG, sub = half * 8 + t / kMG;
-        if (__any((int32_t)or16(kc) < 0)) hm |= 1ull << (g * kSub + sub);
+        rec[t % kMG] = __builtin_amdgcn_alignbit(rec[t % kMG], or16(kc), 31);
         __builtin_amdgcn_sched_barrier(0);
         if (t + 1 < kSteps) kc = kn;
+      }
+    }
+    // One wave-level test per tile (hits are rare): only a tile with a hit ORs the records over
+    // the wave into the (group, sub-tile) mask.  Sub-tile 0 was pushed first: bit 31, hence bfrev.
+    uint64_t hm = 0;
+    {
+      uint32_t any = rec[0];
+#pragma unroll
+      for (int g = 1; g < kMG; ++g) any |= rec[g];
+      if (__any(any != 0)) {
+#pragma unroll
+        for (int g = 0; g < kMG; ++g) hm |= (uint64_t)wave_or32(__builtin_bitreverse32(rec[g])) << (g * kSub);
       }
     }
     // Exact path for the flagged (group, sub-tile) pairs, every lane (exact for any lane): direct

@@ -13,6 +13,8 @@
 //             do the two pipes overlap across waves of one SIMD?
 //   valu_or   the sign-OR tree only, every wave
 //   sweep_or_prio  sweep_or with s_setprio 1 around each MFMA issue
+//   sweep_rec sweep_or with the hit recorded per lane (v_alignbit into a shift register per
+//             group) and one wave-level test per 64 steps instead of __any + SALU every step
 //   sweep_c   threshold folded into the accumulator (C = −thr): tree over 2 groups at once,
 //             one test per two MFMAs
 // 512-thread blocks, 2048 blocks (≈2 blocks/CU at ≤128 VGPRs).  Prints ms per launch, the
@@ -63,7 +65,8 @@ __device__ __forceinline__ float tree(const floatx16& k) {
 
 // kV: 0 sweep (minimum3), 1 sweep_min (min3), 2 mfma only, 3 valu only, 4 sweep_c,
 // 5 sweep without the scheduling fences (compiler's own order), 6 sign-OR tree (v_bitop3, the
-// threshold folded into the MFMA), 7 the same without fences
+// threshold folded into the MFMA), 7 the same without fences, 11 sign-OR tree with the per-lane
+// hit record
 template <int kV>
 __global__ __launch_bounds__(512) void sweep(const uint4* __restrict__ in, float thr0,
                                              uint32_t* __restrict__ out, uint64_t* __restrict__ clk) {
@@ -82,6 +85,7 @@ __global__ __launch_bounds__(512) void sweep(const uint4* __restrict__ in, float
   floatx16 vdat = {};
   for (int r = 0; r < 16; ++r) vdat[r] = (float)(lane * 16 + r);
   uint32_t hm_all = 0;
+  uint32_t rec[kG] = {};
   float fold = 0.0f;
   uint64_t t0 = 0, r0 = 0;
   if (threadIdx.x == 0) {
@@ -139,7 +143,9 @@ __global__ __launch_bounds__(512) void sweep(const uint4* __restrict__ in, float
           kn = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[(t + 1) / kG].h, bq[(t + 1) % kG].h, zacc, 0, 0, 0);
         if (kV == 9) __builtin_amdgcn_s_setprio(0);
         if (kV != 5 && kV != 7) __builtin_amdgcn_sched_barrier(0);
-        if (kV >= 6 && kV != 8) {
+        if (kV == 11) {
+          rec[t % kG] = __builtin_amdgcn_alignbit(rec[t % kG], or16(kc), 31);
+        } else if (kV >= 6 && kV != 8) {
           if (__any((int32_t)or16(kc) < 0)) hm |= 1u << t;
         } else {
           const float m = tree<kV == 1 ? 1 : 0>(kc);
@@ -147,6 +153,10 @@ __global__ __launch_bounds__(512) void sweep(const uint4* __restrict__ in, float
         }
         if (kV != 5 && kV != 7) __builtin_amdgcn_sched_barrier(0);
         if (t + 1 < kSteps) kc = kn;
+      }
+      if (kV == 11 && (it & 3) == 3) {  // 64 steps = one 1024-target tile of nn_mfma_kernel
+        if (__any((rec[0] | rec[1]) != 0)) hm = __builtin_popcountll(__ballot(rec[0] != 0)) + rec[1];
+        rec[0] = rec[1] = 0;
       }
     }
     hm_all ^= hm + it;
@@ -209,6 +219,7 @@ int main() {
   run<5>("sweep_nb", in, out, clk, blocks);
   run<6>("sweep_or", in, out, clk, blocks);
   run<7>("sweep_or_nb", in, out, clk, blocks);
+  run<11>("sweep_rec", in, out, clk, blocks);
   run<8>("mix", in, out, clk, blocks);
   run<10>("valu_or", in, out, clk, blocks);
   run<9>("sweep_or_prio", in, out, clk, blocks);
