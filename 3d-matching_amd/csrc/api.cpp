@@ -1390,8 +1390,9 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
   {
     // Grid NN: cell ≈ the search radius, a query visits 3 cells per axis.  Brute force: the
     // same grids only ORDER the points (targets and queries in cell order make the MFMA
-    // screen's 32-target sub-tiles and 64-query waves spatially compact); every pair is still
-    // screened.
+    // screen's 32-target sub-tiles and 64-query waves spatially compact, and let the box cull of
+    // nn_mfma_kernel skip the tiles a query block cannot reach); every pair is still screened or
+    // excluded by a proven box bound.
     const double cell = max_dist * 1.001;
     int grc = ensure_grid(ctx, tgt, cell, nullptr, &tg);
     // the loop runs on the source in Morton slot order (sg: the copy's query grid)
@@ -1427,7 +1428,7 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
       if (e != hipSuccess) grc = m3d_fail(ctx, M3D_ERR_HIP, std::string("grid fp64 points: ") + hipGetErrorString(e));
     }
     if (!grc && params->nn_method == M3D_NN_BRUTE && tg->mf16 == nullptr) {
-      hipError_t e = build_mfma_tiles(tgt, const_cast<Grid*>(tg), nullptr);
+      hipError_t e = build_mfma_tiles(tgt, const_cast<Grid*>(tg), &ctx->tmp, nullptr);
       if (e != hipSuccess) grc = m3d_fail(ctx, M3D_ERR_HIP, std::string("mfma tiles: ") + hipGetErrorString(e));
     }
     // the loop's arrays in ONE block (from the block cache: a reused block's release mark is

@@ -777,6 +777,7 @@ void grid_free(Grid* g) {
   g->minv = nullptr;
   block_release(g->mf16);
   block_release(g->mf32);
+  block_release(g->mfbox);
   block_release(g->pts64);
   g->pts64 = nullptr;
   g->dev.pts64 = nullptr;
@@ -785,6 +786,7 @@ void grid_free(Grid* g) {
   g->order = nullptr;
   g->mf16 = nullptr;
   g->mf32 = nullptr;
+  g->mfbox = nullptr;
   g->mf_npad = 0;
 }
 
@@ -918,6 +920,44 @@ hipError_t morton_source(const m3d_cloud* src, double cell, m3d_cloud* out, Grid
       (e = hipMemcpyAsync(out->xyz32 + n, src->xyz32 + n, sizeof(float4) * (size_t)(src->n_pad - n),
                           hipMemcpyDeviceToDevice, st)) != hipSuccess)
     return e;
+  return hipSuccess;
+}
+
+// Morton order of a built grid's cells for the brute-force MFMA operand rows (icp.hip
+// build_mfma_tiles): perm[k] = position in g->pts (cell order) of the k-th point in Morton order of
+// the cells, points of one cell in their g->pts order (stable sort).  perm lives in the setup
+// arena: valid for the work enqueued next on st.
+hipError_t grid_morton_perm(const Grid* g, TmpArena* ta, hipStream_t st, const int32_t** perm) {
+  const int64_t n = g->n_pts;
+  *perm = nullptr;
+  if (n == 0) return hipSuccess;
+  int sh[3];
+  for (int k = 0; k < 3; ++k) {
+    sh[k] = 0;
+    while ((g->dev.n[k] >> sh[k]) > 1024) ++sh[k];
+  }
+  uint32_t *kin = nullptr, *kout = nullptr;
+  int32_t *vin = nullptr, *vout = nullptr;
+  size_t tmp_bytes = 0;
+  hipError_t e;
+  if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 30, st)) !=
+      hipSuccess)
+    return e;
+  tmp_bytes = std::max<size_t>(tmp_bytes, 1);
+  const size_t a4 = tmp_align(sizeof(uint32_t) * (size_t)n);
+  if ((e = ta->reserve(4 * a4 + tmp_align(tmp_bytes))) != hipSuccess) return e;
+  kin = reinterpret_cast<uint32_t*>(ta->base);
+  kout = reinterpret_cast<uint32_t*>(ta->base + a4);
+  vin = reinterpret_cast<int32_t*>(ta->base + 2 * a4);
+  vout = reinterpret_cast<int32_t*>(ta->base + 3 * a4);
+  void* tmp = ta->base + 4 * a4;
+  const unsigned blocks = (unsigned)((n + kGridBlock - 1) / kGridBlock);
+  morton_key_src_kernel<<<blocks, kGridBlock, 0, st>>>(g->pts, n, g->dev, sh[0], sh[1], sh[2], kin, vin);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 30, st)) !=
+      hipSuccess)
+    return e;
+  *perm = vout;
   return hipSuccess;
 }
 

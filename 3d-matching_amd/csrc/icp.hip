@@ -7,7 +7,8 @@
 // Kernels per iteration (all device resident, no host round trip):
 //   keyinit  O(Ns)      seeds each query's bound with its previous neighbour (fp32 d²)
 //   nn       O(Ns·Nt)   brute-force scan, nn_mfma_kernel: screen key |t|² − 2q·t on the matrix
-//                       cores (fp16 hi/lo split operands, proven error bound, refresh_rt32),
+//                       cores (fp16 hi/lo split operands, proven error bound, refresh_rt32; the
+//                       tiles a proven box bound puts out of reach are skipped, box_out_of_reach),
 //                       v_minimum3 tree per 32×32 block, flagged sub-tiles take the exact path:
 //                       direct fp32 d² with lexicographic (d², index) argmin — the same result as
 //                       a full direct scan (nn_kernel: the fp32 VALU form of the same screen,
@@ -427,11 +428,18 @@ __device__ __forceinline__ void thr_operand(half8& b, float thr0, bool& force) {
   b[4] = -tl;
 }
 
-// MFMA screen operands of a cloud in its grid's cell order (A rows of nn_mfma_kernel):
+// target operand rows in Morton order of the grid's cells (build_mfma_tiles); 0 (A/B builds):
+// row-major cells
+#ifndef M3D_NN_TILE_MORTON
+#define M3D_NN_TILE_MORTON 1
+#endif
+// MFMA screen operands of a cloud (A rows of nn_mfma_kernel), rows in Morton order of its grid's
+// cells — or in the grid's row-major cell order, M3D_NN_TILE_MORTON=0 (build_mfma_tiles):
 // mf16 = fp16 split (+ the two constant-1 threshold slots), mf32 = (x, y, z, original index
 // bits).  Pads: key 65504 (never hit),
 // far-away coordinates (never accepted by the exact path).
 __global__ __launch_bounds__(256) void pack16_sorted_kernel(const float4* __restrict__ sorted,
+                                                            const int32_t* __restrict__ perm,
                                                             const float4* __restrict__ xyz32,
                                                             int64_t n, int64_t n_pad, float S,
                                                             uint4* __restrict__ mf16,
@@ -442,7 +450,8 @@ __global__ __launch_bounds__(256) void pack16_sorted_kernel(const float4* __rest
   a.u = make_uint4(0, 0, 0, 0);
   b.u = make_uint4(0, 0, 0, 0);
   if (k < n) {
-    const int32_t idx = __float_as_int(sorted[k].w);
+    // row k: the k-th point of `sorted` (cell order), or of its permutation perm
+    const int32_t idx = __float_as_int(sorted[perm != nullptr ? perm[k] : k].w);
     const float4 t = xyz32[idx];  // w = |t|² (center_pack)
     _Float16 xh, xl, yh, yl, zh, zl, wh, wl;
     split16(t.x * S, xh, xl);
@@ -462,15 +471,64 @@ __global__ __launch_bounds__(256) void pack16_sorted_kernel(const float4* __rest
   mf16[n_pad + k] = b.u;
 }
 
-hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, hipStream_t st) {
+// Box of each 256-row half tile of mf32 (one block per half): box[2·half] = (lo.xyz, ·),
+// box[2·half + 1] = (hi.xyz, ·) over the rows' exact fp32 coordinates — the values nn_exact_rows
+// feeds to d2f — pads (index bits < 0) left out; an all-pad half keeps lo = +inf, hi = −inf.
+__global__ __launch_bounds__(kMTile) void tile_box_kernel(const float4* __restrict__ mf32,
+                                                          float4* __restrict__ box) {
+  const float4 t = mf32[(int64_t)blockIdx.x * kMTile + threadIdx.x];
+  const bool real = __float_as_int(t.w) >= 0;
+  float v[6] = {real ? t.x : kInf,  real ? t.y : kInf,  real ? t.z : kInf,
+                real ? t.x : -kInf, real ? t.y : -kInf, real ? t.z : -kInf};
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const float w = __shfl_xor(v[k], o);
+      v[k] = k < 3 ? fminf(v[k], w) : fmaxf(v[k], w);
+    }
+  __shared__ float part[kMTile / 64][6];
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) part[threadIdx.x >> 6][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int w = 1; w < kMTile / 64; ++w)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = k < 3 ? fminf(v[k], part[w][k]) : fmaxf(v[k], part[w][k]);
+  box[2 * (int64_t)blockIdx.x] = make_float4(v[0], v[1], v[2], 0.0f);
+  box[2 * (int64_t)blockIdx.x + 1] = make_float4(v[3], v[4], v[5], 0.0f);
+}
+
+hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, TmpArena* ta, hipStream_t st) {
   const int64_t n = c->n;
   const int64_t n_pad = std::max<int64_t>((n + kMTilePad - 1) / kMTilePad * kMTilePad, kMTilePad);
-  hipError_t e = block_alloc(reinterpret_cast<void**>(&g->mf16), sizeof(uint4) * 2 * n_pad, st);
-  if (e == hipSuccess) e = block_alloc(reinterpret_cast<void**>(&g->mf32), sizeof(float4) * n_pad, st);
+  const int32_t* perm = nullptr;  // (setup arena: consumed by pack16_sorted_kernel below)
+  hipError_t e = M3D_NN_TILE_MORTON ? grid_morton_perm(g, ta, st, &perm) : hipSuccess;
   if (e != hipSuccess) return e;
+  e = block_alloc(reinterpret_cast<void**>(&g->mf16), sizeof(uint4) * 2 * n_pad, st);
+  if (e == hipSuccess) e = block_alloc(reinterpret_cast<void**>(&g->mf32), sizeof(float4) * n_pad, st);
+  if (e == hipSuccess)
+    e = block_alloc(reinterpret_cast<void**>(&g->mfbox), sizeof(float4) * 2 * (n_pad / kMTile), st);
+  if (e != hipSuccess) {  // all three or none (mf16 != nullptr marks the tiles as built)
+    block_release(g->mf16);
+    block_release(g->mf32);
+    block_release(g->mfbox);
+    g->mf16 = nullptr;
+    g->mf32 = nullptr;
+    g->mfbox = nullptr;
+    return e;
+  }
   g->mf_npad = n_pad;
+  // Row order (private to nn_mfma_kernel: the exact path takes the original index from mf32.w):
+  // the grid's row-major cell order, where a 1024-row tile is a thin z-slab, or Morton order of
+  // the same cells, where it is a compact patch that fewer query boxes reach (M3D_NN_TILE_MORTON)
   pack16_sorted_kernel<<<(unsigned)((n_pad + 255) / 256), 256, 0, st>>>(
-      g->pts, c->xyz32, n, n_pad, (float)c->s16, g->mf16, g->mf32);
+      g->pts, perm, c->xyz32, n, n_pad, (float)c->s16, g->mf16, g->mf32);
+  // the target of a loop never moves: the boxes are built once per (cloud, cell size) and serve
+  // every evaluation of every loop on this grid
+  tile_box_kernel<<<(unsigned)(n_pad / kMTile), kMTile, 0, st>>>(g->mf32, g->mfbox);
   return hipGetLastError();  // asynchronous (stream order); m3d_icp_create synchronises once
 }
 
@@ -494,8 +552,8 @@ __device__ __forceinline__ int64_t start_key(const SeedArgs& sa, const IcpState*
 
 // whether a block publishes its k1: it changed, or (self-seeding) the grid.y = 0 blocks publish
 // the seed every block started from
-__device__ __forceinline__ bool publish_k1(const SeedArgs& sa, uint64_t k1, uint64_t k10) {
-  return k1 != k10 || (sa.on && blockIdx.y == 0 && key_real(k1));
+__device__ __forceinline__ bool publish_k1(const SeedArgs& sa, uint64_t k1, bool changed) {
+  return changed || (sa.on && blockIdx.y == 0 && key_real(k1));
 }
 
 // Exact fallback of nn_mfma_kernel when the scaled operands do not fit fp16 (mfma_ok == 0, a
@@ -524,7 +582,7 @@ __device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, cons
       const float d2 = d2f(qx, qy, qz, t.x, t.y, t.z);
       if (d2 <= r2_hi) near_push(k1, k1d, n2, make_key(d2, (uint32_t)(off + __float_as_int(t.w))), d2);
     }
-    const bool pk = publish_k1(sa, k1, k10);
+    const bool pk = publish_k1(sa, k1, k1 != k10);
     if (pk || n2 < kInf) near_publish((unsigned long long*)&keys[i], &near2[i], k1, n2, pk);
   }
 }
@@ -564,10 +622,60 @@ __device__ __forceinline__ uint32_t wave_or32(uint32_t v) {
                     __builtin_amdgcn_readlane(x, 32) | __builtin_amdgcn_readlane(x, 48));
 }
 
+// min / max of v over the wave's 64 lanes (all active), wave-uniform: as wave_or32
+template <bool kMax>
+__device__ __forceinline__ float wave_minmax(float v) {
+  const auto mm = [](float a, float b) { return kMax ? fmaxf(a, b) : fminf(a, b); };
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false)));
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false)));
+  v = mm(v, __int_as_float(xor4_dpp(__float_as_int(v))));
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false)));
+  const int x = __float_as_int(v);
+  return mm(mm(__int_as_float(__builtin_amdgcn_readlane(x, 0)), __int_as_float(__builtin_amdgcn_readlane(x, 16))),
+            mm(__int_as_float(__builtin_amdgcn_readlane(x, 32)), __int_as_float(__builtin_amdgcn_readlane(x, 48))));
+}
+
+// Box cull of the brute-force sweep.  A set of queries is summarised by the box
+// [lo, hi] of their fp32 coordinates and Xmax = the largest search bound X among them; a set of
+// targets by the box of their fp32 coordinates (Grid::mfbox).  G = d2f(g, 0) with, per axis,
+// g = max(0, qlo − thi, tlo − qhi) in fp32.
+// Lemma: d2f(q, t) ≥ G for every q in the query box and t in the target box, with no epsilon.
+//   * fp32 round-to-nearest is monotone: q − t ≥ qlo − thi in the reals gives fl(q − t) ≥
+//     fl(qlo − thi), likewise fl(t − q) ≥ fl(tlo − qhi); so |fl(q − t)| ≥ g on each axis (g = 0
+//     where the boxes overlap), and g − 0 is exact;
+//   * d2f's chain fma(dz, dz, fma(dy, dy, dx·dx)) is monotone in |dx|, |dy|, |dz|: each step is a
+//     monotone real function of non-negative arguments followed by one monotone rounding.
+// So a target set with G > Xmax holds only targets with d2f > Xmax ≥ X of every query concerned.
+// Such a target cannot become k1 (band_of(d) ≥ d, so X ≥ min(d2f(k1), r2_hi), and the exact path
+// takes d2f ≤ r2_hi only), and it cannot put a value ≤ search_bound(final k1) into near2: X only
+// ever tightens during the sweep (k1 only decreases, band_of is monotone), and near2 is only ever
+// compared with search_bound of the final k1 (nnkey.h winner_fp64; the bound-only seeds of target
+// shards reach X through the same search_bound).  Skipping the set therefore leaves every key and
+// every ambiguous / unambiguous classification as the every-pair sweep has them; near2's value
+// may differ only above the band.  The test is `G > Xmax`, strict: G = d2f = X is kept.  A NaN
+// coordinate never enters a box: fminf / fmaxf in the lane, wave and tile_box_kernel reductions
+// return the other operand.  That is harmless: a NaN point has no finite d2f, fails d2f ≤ r2_hi
+// and can never be a neighbour, swept or not.  (Should G itself come out NaN, e.g. from
+// inf − inf of an empty box, `G > Xmax` is false and the set is kept.)  M3D_NN_CULL=0 (A/B
+// build) sweeps every pair as before.
+#ifndef M3D_NN_CULL
+#define M3D_NN_CULL 1
+#endif
+struct QBox {
+  float lo[3], hi[3], X;
+};
+__device__ __forceinline__ bool box_out_of_reach(const QBox& q, const float4& tlo, const float4& thi) {
+  const float gx = fmaxf(0.0f, fmaxf(q.lo[0] - thi.x, tlo.x - q.hi[0]));
+  const float gy = fmaxf(0.0f, fmaxf(q.lo[1] - thi.y, tlo.y - q.hi[1]));
+  const float gz = fmaxf(0.0f, fmaxf(q.lo[2] - thi.z, tlo.z - q.hi[2]));
+  return d2f(gx, gy, gz, 0.0f, 0.0f, 0.0f) > q.X;
+}
+
 __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(const float4* __restrict__ src32,
                                                           int64_t ns,
                                                           const uint4* __restrict__ tgt16,
                                                           const float4* __restrict__ tgt32,
+                                                          const float4* __restrict__ tbox,
                                                           int64_t nt_pad, int64_t off,
                                                           const IcpState* __restrict__ s,
                                                           int64_t* __restrict__ keys,
@@ -575,11 +683,10 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
                                                           SeedArgs sa, int64_t q0) {
   if (s->done) return;
   // grid.y block y takes every gridDim.y-th target tile (strided: a query block's few candidate
-  // tiles, adjacent in cell order, spread over gridDim.y blocks instead of landing in one)
-  const int64_t tstep = (int64_t)gridDim.y * kTH * kMTile;
-  const int64_t jb = (int64_t)blockIdx.y * kTH * kMTile;
-  if (!s->mfma_ok) {  // the same tiles by a plain scan
-    for (int64_t t0 = jb; t0 < nt_pad; t0 += tstep)
+  // tiles, adjacent in row order, spread over gridDim.y blocks instead of landing in one)
+  if (!s->mfma_ok) {  // the same tiles by a plain scan, unculled
+    const int64_t tstep = (int64_t)gridDim.y * kTH * kMTile;
+    for (int64_t t0 = (int64_t)blockIdx.y * kTH * kMTile; t0 < nt_pad; t0 += tstep)
       nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTH * kMTile), off, s, keys, near2, sa, q0);
     return;
   }
@@ -591,10 +698,13 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   float qx[kMG], qy[kMG], qz[kMG], qq[kMG];
   uint32_t force = 0;  // groups whose threshold exceeds the fp16 range: exact path everywhere
   uint32_t act = 0;    // groups whose query (column c) exists
-  uint64_t k1[kMG], k10[kMG];
+  uint64_t k1[kMG];
+  uint32_t chg = 0;  // groups whose k1 left its starting key (k1 only ever decreases)
   float k1d[kMG], n2[kMG];
   int64_t qi[kMG];
   half8 bq[kMG];
+  // the lane's share of its wave's query box (box_out_of_reach): active queries only
+  QBox lq{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}, -1.0f};
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
     // queries: positions [q0, ns) of the visit order (order, or the slots themselves)
@@ -610,11 +720,17 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
       k1[g] = key == kKeyNone ? make_key(r2_hi, 0xFFFFFFFFu) : (uint64_t)key;
       X = search_bound(key_d2(k1[g]), be, r2_hi);
       act |= 1u << g;
+      lq.lo[0] = fminf(lq.lo[0], qx[g]);
+      lq.lo[1] = fminf(lq.lo[1], qy[g]);
+      lq.lo[2] = fminf(lq.lo[2], qz[g]);
+      lq.hi[0] = fmaxf(lq.hi[0], qx[g]);
+      lq.hi[1] = fmaxf(lq.hi[1], qy[g]);
+      lq.hi[2] = fmaxf(lq.hi[2], qz[g]);
+      lq.X = fmaxf(lq.X, X);
     } else {
       qx[g] = qy[g] = qz[g] = 0.0f;
       k1[g] = (uint64_t)kKeyNone;
     }
-    k10[g] = k1[g];
     k1d[g] = key_real_d2(k1[g]);
     qq[g] = fmaf(qz[g], qz[g], fmaf(qy[g], qy[g], qx[g] * qx[g]));
     _Float16 ah, al, bh, bl, ch, cl;
@@ -661,11 +777,90 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     if ((dfr >> g) & 1u) dmask |= kGMask << (g * kSub);
   dmask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(dmask >> 32)) << 32) |
           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dmask);  // wave-uniform: SGPRs
-  const int64_t je = nt_pad;
+  // The cull (box_out_of_reach above): the box and Xmax of each wave's active queries by a DPP
+  // reduction, published in LDS as (lo.xyz, Xmax), (hi.xyz, ·); the block's box is their union.
+  // The block skips, block-uniformly, every tile of its strided set none of whose half tiles its
+  // box can reach (no DMA, no sweep, no barrier); inside a surviving tile a wave sweeps only the
+  // half tiles its own box can reach.  (The boxes stay in LDS and are read back by the rare
+  // survivor rounds below: held in registers across the sweep they cost spills.)
+  __shared__ float4 qbox[kMBlock / 64][2];
+  {
+    float wlo[3], whi[3];
 #pragma unroll
-  for (int u = 0; u < kTH; ++u) {
-    const int e = threadIdx.x + u * kMBlock;
-    t16[0][e / kTT][e % kTT] = tgt16[(e / kTT) * nt_pad + jb + e % kTT];
+    for (int k = 0; k < 3; ++k) {
+      wlo[k] = wave_minmax<false>(lq.lo[k]);
+      whi[k] = wave_minmax<true>(lq.hi[k]);
+    }
+    const float wX = wave_minmax<true>(lq.X);
+    if (lane == 0) {
+      qbox[wave][0] = make_float4(wlo[0], wlo[1], wlo[2], wX);
+      qbox[wave][1] = make_float4(whi[0], whi[1], whi[2], 0.0f);
+    }
+  }
+  __syncthreads();
+  QBox bx;  // the block's box, in SGPRs: lane l takes wave l & 7's, three DPP steps merge the eight
+  {
+    static_assert(kMBlock / 64 == 8, "eight wave boxes, lanes ^1 ^2 ^4");
+    float4 lo = qbox[lane & 7][0], hi = qbox[lane & 7][1];
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+      const auto x = [&](float v) { return __int_as_float(xor_lane(__float_as_int(v), o, kWave)); };
+      lo = make_float4(fminf(lo.x, x(lo.x)), fminf(lo.y, x(lo.y)), fminf(lo.z, x(lo.z)), fmaxf(lo.w, x(lo.w)));
+      hi = make_float4(fmaxf(hi.x, x(hi.x)), fmaxf(hi.y, x(hi.y)), fmaxf(hi.z, x(hi.z)), 0.0f);
+    }
+    const auto u = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    bx = QBox{{u(lo.x), u(lo.y), u(lo.z)}, {u(hi.x), u(hi.y), u(hi.z)}, u(lo.w)};
+  }
+  // Survivors, 16 tiles of the block's strided set per round: lane l tests half tile l & 3 of
+  // tile tc + (l >> 2)·gridDim.y against both boxes (one round of box loads per 16 tiles).  mb:
+  // half tiles the block reaches — a tile survives if any of its four bits is set; mw ⊆ mb: those
+  // this wave reaches.  Every wave computes mb from the same data by the same instructions.
+  const int ntile = (int)(nt_pad / kTT), ty = (int)gridDim.y;
+  int tc = (int)blockIdx.y;
+  uint64_t mb = 0, mw = 0;
+  const auto cull_round = [&]() {
+    const int tl = tc + (lane >> 2) * ty;
+    bool kb = tl < ntile, kw = kb;
+    if (M3D_NN_CULL && kb) {
+      const int64_t hb = (int64_t)tl * kTH + (lane & 3);  // < nt_pad / kMTile
+      const float4 tlo = tbox[2 * hb], thi = tbox[2 * hb + 1];
+      const float4 l0 = qbox[wave][0], u0 = qbox[wave][1];
+      const QBox wq{{l0.x, l0.y, l0.z}, {u0.x, u0.y, u0.z}, l0.w};
+      kb = !box_out_of_reach(bx, tlo, thi);
+      kw = !box_out_of_reach(wq, tlo, thi);
+    }
+    mb = __ballot(kb);
+    mw = __ballot(kw);
+  };
+  // next surviving tile (ntile: none left) and this wave's half-tile mask of it
+  const auto next_tile = [&](int& t, uint32_t& hmask) {
+    for (;;) {
+      if (mb != 0) {
+        const int k = __builtin_ctzll(mb) >> 2;
+        t = tc + k * ty;
+        hmask = (uint32_t)(mw >> (4 * k)) & 15u;
+        mb &= ~(15ull << (4 * k));
+        return;
+      }
+      tc += 16 * ty;
+      if (tc >= ntile) {
+        t = ntile;
+        hmask = 0;
+        return;
+      }
+      cull_round();
+    }
+  };
+  cull_round();
+  int t0, t1;
+  uint32_t h0, h1;
+  next_tile(t0, h0);
+  if (t0 < ntile) {
+#pragma unroll
+    for (int u = 0; u < kTH; ++u) {
+      const int e = threadIdx.x + u * kMBlock;
+      t16[0][e / kTT][e % kTT] = tgt16[(e / kTT) * nt_pad + (int64_t)t0 * kTT + e % kTT];
+    }
   }
   uint64_t force64 = 0;
 #pragma unroll
@@ -673,15 +868,16 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     if ((force >> (g * 8)) & 1u) force64 |= kGMask << (g * kSub);
   __syncthreads();
   int buf = 0;
-  for (int64_t j0 = jb; j0 < je; j0 += tstep) {
-    const bool has_next = j0 + tstep < je;
-    // the next tile global → LDS by DMA while this one is swept (lds_dma.h): no prefetch
-    // registers (a wave's 64 elements are one plane's 64 consecutive targets)
-    if (has_next) {
+  for (; t0 < ntile; t0 = t1, h0 = h1) {
+    const int64_t j0 = (int64_t)t0 * kTT;
+    next_tile(t1, h1);
+    // the next surviving tile global → LDS by DMA while this one is swept (lds_dma.h): no
+    // prefetch registers (a wave's 64 elements are one plane's 64 consecutive targets)
+    if (t1 < ntile) {
 #pragma unroll
       for (int u = 0; u < kTH; ++u) {
         const int e = threadIdx.x + u * kMBlock;
-        lds_dma16(tgt16 + (e / kTT) * nt_pad + j0 + tstep + e % kTT, &t16[buf ^ 1][e / kTT][(e % kTT) & ~63]);
+        lds_dma16(tgt16 + (e / kTT) * nt_pad + (int64_t)t1 * kTT + e % kTT, &t16[buf ^ 1][e / kTT][(e % kTT) & ~63]);
       }
     }
     // Sweep: MFMA + sign-OR test for the tile's sub-tiles, branch-free.  A step records its sign
@@ -696,6 +892,13 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     constexpr int kSteps = 8 * kMG;  // (sub-tile, group) steps of one half tile
 #pragma unroll
     for (int half = 0; half < kTH; ++half) {
+      // a half tile out of this wave's reach (wave-uniform: a scalar branch): its 8 steps' bits
+      // are zeros, so that bfrev / ctz below still address the sub-tiles
+      if (!((h0 >> half) & 1u)) {
+#pragma unroll
+        for (int g = 0; g < kMG; ++g) rec[g] <<= 8;
+        continue;
+      }
       H8 av[8];
 #pragma unroll
       for (int sub = 0; sub < 8; ++sub) av[sub].u = t16[buf][h][half * kMTile + sub * 32 + c];
@@ -733,7 +936,16 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     // per-wave list below (dlist/dtile, resolved after the sweep, off the tile barrier:
     // −2.2 % per launch at cfg1); unseeded groups and a full list resolve here,
     // where the threshold refresh still prunes the rest of the sweep.
-    hm |= force64;
+    {  // `force` groups: every sub-tile of the half tiles swept (the lemma is about d2f)
+      uint32_t sm = 0;
+#pragma unroll
+      for (int half = 0; half < kTH; ++half)
+        if ((h0 >> half) & 1u) sm |= 0xFFu << (8 * half);
+      uint64_t fm = 0;
+#pragma unroll
+      for (int g = 0; g < kMG; ++g) fm |= (uint64_t)sm << (g * kSub);
+      hm |= force64 & fm;
+    }
     {
       const uint64_t hd = hm & dmask;
       if (hd != 0 && dn < kDefer) {
@@ -749,6 +961,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (int g = 0; g < kMG; ++g) {
       uint64_t mg = (hm >> (g * kSub)) & kGMask;
       if (mg == 0) continue;
+      const uint64_t kb = k1[g];
       while (mg != 0) {
         const int sub = __builtin_ctzll(mg);
         mg &= mg - 1;
@@ -757,6 +970,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         const float on2 = __shfl_xor(n2[g], 32);
         near_merge(k1[g], k1d[g], n2[g], o1, on2);
       }
+      chg |= (uint32_t)(k1[g] != kb) << g;
       bool fg;
       half8 bt = bq[g];
       const float X = (act >> g) & 1u ? search_bound(key_d2(k1[g]), be, r2_hi) : -1.0f;
@@ -774,6 +988,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 #pragma unroll
     for (int g = 0; g < kMG; ++g) {
       uint64_t mg = (ent >> (g * kSub)) & kGMask;
+      const uint64_t kb = k1[g];
       while (mg != 0) {
         const int sub = __builtin_ctzll(mg);
         mg &= mg - 1;
@@ -782,12 +997,13 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         const float on2 = __shfl_xor(n2[g], 32);
         near_merge(k1[g], k1d[g], n2[g], o1, on2);
       }
+      chg |= (uint32_t)(k1[g] != kb) << g;
     }
   }
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
     if (h != 0 || qi[g] < 0) continue;
-    const bool pk = publish_k1(sa, k1[g], k10[g]);
+    const bool pk = publish_k1(sa, k1[g], (chg >> g) & 1u);
     if (pk || n2[g] < kInf)
       near_publish((unsigned long long*)&keys[qi[g]], &near2[qi[g]], k1[g], n2[g], pk);
   }
@@ -1815,10 +2031,16 @@ hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStrea
     const int64_t tt = (int64_t)kTH * kMTile;
     if (tg->mf_npad % tt != 0) return hipErrorInvalidValue;  // pack16 pads to kMTilePad
     dim3 gm = nn_grid((ns - q0 + kMQueries - 1) / kMQueries, tg->mf_npad, tt, &slice);
-    // Strided tiles decouple grid.y from slice boundaries: pick S in [S0, 2·S0] so that the
-    // block count fills the resident block slots in whole rounds (the last partial round of
-    // equal-length blocks idles the rest of the chip: 196 × 11 blocks on 512 slots = 4.2
-    // rounds ran as 5).
+    // Strided tiles decouple grid.y from slice boundaries.  Every-pair sweep (M3D_NN_CULL=0):
+    // pick S in [S0, 2·S0], S0 = 2048 / grid.x, so that the block count fills the resident block
+    // slots in whole rounds (the last partial round of equal-length blocks idles the rest of the
+    // chip: 196 × 11 blocks on 512 slots = 4.2 rounds ran as 5).  Culled sweep: a block keeps only
+    // a few of its tiles, its setup (query load, seed gather, boxes, survivor round) weighs as
+    // much as what is left of the sweep, and the blocks' lengths differ — the fewest slices that
+    // fill the slots once, S = ⌈slots / grid.x⌉ (EXPERIMENTS §3.5: cfg1 59 µs at S = 3 against
+    // 63–73 at 4–6 and 86 at 13; the 1M pair fastest at S = 1).  The rule rests on those two
+    // shapes only.  With few query blocks it degenerates to one tile per block (grid.x = 1 gives
+    // S = ntiles, the clamp below): every block then pays the setup for at most one tile.
     static const int64_t slots = [] {
       int dev = 0, per = 0;
       hipDeviceProp_t p;
@@ -1829,21 +2051,24 @@ hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStrea
     }();
     const int64_t bx = gm.x, ntiles = tg->mf_npad / tt;
     if (slots > 0 && ntiles > 1) {
-      int64_t s0 = std::min<int64_t>(std::max<int64_t>((2048 + bx - 1) / bx, 1), ntiles);
-      int64_t best = s0;
-      double best_eff = 0.0;
-      for (int64_t S = s0; S <= std::min<int64_t>(2 * s0, ntiles); ++S) {
-        const int64_t blocks = bx * S, rounds = (blocks + slots - 1) / slots;
-        const double eff = (double)blocks / (double)(rounds * slots);
-        if (eff > best_eff + 1e-9) {
-          best_eff = eff;
-          best = S;
+      int64_t best = std::min<int64_t>(std::max<int64_t>((slots + bx - 1) / bx, 1), ntiles);
+      if (!M3D_NN_CULL) {
+        const int64_t s0 = std::min<int64_t>(std::max<int64_t>((2048 + bx - 1) / bx, 1), ntiles);
+        double best_eff = 0.0;
+        best = s0;
+        for (int64_t S = s0; S <= std::min<int64_t>(2 * s0, ntiles); ++S) {
+          const int64_t blocks = bx * S, rounds = (blocks + slots - 1) / slots;
+          const double eff = (double)blocks / (double)(rounds * slots);
+          if (eff > best_eff + 1e-9) {
+            best_eff = eff;
+            best = S;
+          }
         }
       }
       gm.y = (unsigned)best;
     }
     const SeedArgs sa{s->corr, s->tgt->xyz32, s->tgt->n, self_seed ? 1 : 0};
-    nn_mfma_kernel<<<gm, kMBlock, 0, st>>>(s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mf_npad, off,
+    nn_mfma_kernel<<<gm, kMBlock, 0, st>>>(s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox, tg->mf_npad, off,
                                            s->state, s->keys, s->near2, sa, q0);
     return hipGetLastError();
   }

@@ -114,10 +114,14 @@ struct Grid {
   bool occ_known = false;
   double cell = 0.0;      // cell size used
   double cell_req = 0.0;  // cell size requested
-  // brute-force MFMA screen operands in this grid's cell order (icp.hip pack16_sorted), padded
-  // to mf_npad: fp16 hi/lo split (2 × uint4 per point) + fp32 (x, y, z, original index bits)
+  // brute-force MFMA screen operands, rows in Morton order of this grid's cells (icp.hip
+  // build_mfma_tiles; M3D_NN_TILE_MORTON=0: the grid's row-major cell order), padded
+  // to mf_npad: fp16 hi/lo split (2 × uint4 per point) + fp32 (x, y, z, original index bits);
+  // mfbox = per 256-row half tile the axis-aligned box (lo.xyz, hi.xyz) of its rows' mf32
+  // coordinates, pads left out (an all-pad half: lo = +inf, hi = −inf) — nn_mfma_kernel's cull
   uint4* mf16 = nullptr;
   float4* mf32 = nullptr;
+  float4* mfbox = nullptr;
   int64_t mf_npad = 0;
   double4* pts64 = nullptr;  // dev.pts64 (build_grid_pts64, icp.hip)
   // one allocation holding several of the arrays above (Carve; grid_free frees it, not them)
@@ -527,7 +531,8 @@ int64_t validate_blocks(int64_t ns);
 hipError_t launch_validate(const Grid* qgrid, int64_t ns, const double* src64, const Grid* g,
                            const double* tgt64, int64_t nt, const IcpState* states, int64_t nhyp,
                            double* part, double* out, hipStream_t st);
-hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, hipStream_t st);
+hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, TmpArena* ta, hipStream_t st);
+hipError_t grid_morton_perm(const Grid* g, TmpArena* ta, hipStream_t st, const int32_t** perm);
 
 // preprocessing (prep.hip) and feature matching (feat.hip)
 size_t voxel_scratch_bytes(int64_t n);  // device scratch voxel_down_sample needs for n points
