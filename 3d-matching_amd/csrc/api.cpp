@@ -1166,7 +1166,7 @@ int cloud_create(m3d_ctx* ctx, const double* xyz, const double* normals, int64_t
   }
   rc = cloud_pack(ctx, c, n, center == nullptr, st);
   if (!rc) {
-    // fp16 screen operand scale: a power of two with |S·x|∞ ≤ 32 (icp.hip pack16_sorted)
+    // fp16 screen operand scale: a power of two with |S·x|∞ ≤ 32 (nn_brute.hip pack16_sorted)
     int ex = 0;
     std::frexp(std::max(c->rmax, 1e-30) / 32.0, &ex);
     c->s16 = std::ldexp(1.0, -std::min(std::max(ex, -100), 100));
@@ -1722,7 +1722,7 @@ int m3d_icp_shard_nn_range(m3d_icp* s, int64_t off, int64_t q0, int64_t q1, int6
   CHECK_ARG(ctx, off >= 0, "negative shard offset");
   CHECK_ARG(ctx, dkeys != nullptr, "null dkeys");
   CHECK_ARG(ctx, 0 <= q0 && q0 <= q1 && q1 <= s->src->n, "slot range outside [0, ns]");
-  CHECK_ARG(ctx, icp_nn_range_ok(s), "this loop's NN cannot run on a slot range (fp32 VALU / per-query form)");
+  CHECK_ARG(ctx, icp_nn_range_ok(s), "this loop's NN cannot run on a slot range (grid search without a Morton query grid)");
   return icp_shard_nn_range(s, off, q0, q1, dkeys, S(stream));
 }
 

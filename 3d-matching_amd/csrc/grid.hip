@@ -1,7 +1,7 @@
 // grid.hip — radius-bounded uniform-grid 1-NN for gfx950.
 //
 // Reference semantics: Open3D KDTreeFlann::SearchHybrid(p, r, max_nn = 1) inside
-// GetRegistrationResultAndCorrespondences (a8).  The brute-force scan (icp.hip nn_kernel) and
+// GetRegistrationResultAndCorrespondences (a8).  The brute-force scan (nn_brute.hip) and
 // this path return the SAME key for every query: the lexicographic (fp32 d², index) minimum over
 // the targets with d² ≤ r2_hi, where d² is the identical fp32 expression (d2f) of the identical
 // fp32 query (xform32).  The grid only restricts which targets are visited, and it provably
@@ -923,7 +923,7 @@ hipError_t morton_source(const m3d_cloud* src, double cell, m3d_cloud* out, Grid
   return hipSuccess;
 }
 
-// Morton order of a built grid's cells for the brute-force MFMA operand rows (icp.hip
+// Morton order of a built grid's cells for the brute-force MFMA operand rows (nn_brute.hip
 // build_mfma_tiles): perm[k] = position in g->pts (cell order) of the k-th point in Morton order of
 // the cells, points of one cell in their g->pts order (stable sort).  perm lives in the setup
 // arena: valid for the work enqueued next on st.

@@ -114,7 +114,7 @@ struct Grid {
   bool occ_known = false;
   double cell = 0.0;      // cell size used
   double cell_req = 0.0;  // cell size requested
-  // brute-force MFMA screen operands, rows in Morton order of this grid's cells (icp.hip
+  // brute-force MFMA screen operands, rows in Morton order of this grid's cells (nn_brute.hip
   // build_mfma_tiles; M3D_NN_TILE_MORTON=0: the grid's row-major cell order), padded
   // to mf_npad: fp16 hi/lo split (2 × uint4 per point) + fp32 (x, y, z, original index bits);
   // mfbox = per 256-row half tile the axis-aligned box (lo.xyz, hi.xyz) of its rows' mf32
@@ -470,7 +470,7 @@ hipError_t launch_ransac_shard_key(const m3d_ransac_result* r, int64_t hyp0, int
 hipError_t launch_ransac_shard_pack(const m3d_ransac_result* r, int64_t hyp0, int64_t* buf,
                                     hipStream_t st);
 // target-shard loop pieces (api.cpp): the NN + this shard's winners of source slots [q0, q1), and
-// whether the loop's NN can run on a slot range (grid NN; brute force with MFMA tiles in slot order)
+// whether the loop's NN can run on a slot range (grid NN with a Morton query grid; brute force always)
 int icp_shard_nn_range(m3d_icp* s, int64_t off, int64_t q0, int64_t q1, int64_t* dkeys, hipStream_t st);
 bool icp_nn_range_ok(const m3d_icp* s);
 

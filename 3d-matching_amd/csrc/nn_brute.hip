@@ -1,0 +1,773 @@
+// nn_brute.hip — the brute-force nearest-neighbour scan of the ICP loop for gfx950 (icp.hip's "nn"
+// step, O(Ns·Nt)): the target's MFMA operand tiles and their boxes (build_mfma_tiles), the box
+// cull (box_out_of_reach), nn_mfma_kernel and its launcher.  Per query the scan state (k1, near2)
+// of nnkey.h; the target tiles are dealt to grid.y in strides and the blocks merge with a 64-bit
+// atomicMin on packed (bits(d²) << 32 | idx): order independent → deterministic, lowest index wins
+// exact ties.  Shares only IcpState and nnkey.h with the fp64 tail in icp.hip.
+#include <algorithm>
+
+#include "lds_dma.h"
+#include "m3d_internal.h"
+#include "nnkey.h"
+
+namespace m3d {
+
+// ------------------------------------------------------------------------------- NN, MFMA screen
+// The screen key |t|² − 2q·t is a rank-4 contraction over (x, y, z, 1): here it runs on the
+// matrix cores.  One v_mfma_f32_32x32x16_f16 computes S²·(key − thr) for 32 targets (A rows) ×
+// 32 queries (B columns) from fp16 hi/lo splits of the S-scaled operands, K = 16:
+//   A (target) = [xh, xh, xl, yh, yh, yl, zh, zh | zl, wh, wl, 1,   1,   0, 0, 0]
+//   B (query)  = [ah, al, ah, bh, bl, bh, ch, cl | ch, 1,  1,  −Th, −Tl, 0, 0, 0]
+// (a,b,c) = −2S·q; Th + Tl = the query's threshold S²·thr split in fp16 (thr_split).  Products
+// of fp16 are exact in fp32; the bound on the key error is screen_eps_m (refresh_rt32) plus the
+// threshold terms' share of the accumulation and split error (thr_operand).  So a target can
+// only be a candidate if its value is negative, and the screen is a sign test: per MFMA a lane
+// ORs the bit patterns of its 16 values with v_bitop3_b32 — a full-rate 3-input op on gfx950,
+// where v_min3/v_minimum3/v_or3 issue at half rate (tools/ubench_ops.hip) — and tests bit 31.
+// A lane holds column c = lane & 31 (its query) and 16 of the 32 rows; the lane pair (c, c + 32)
+// covers all 32.  A sub-tile that hits anywhere in the wave runs the fp32 exact path
+// (direct d², lexicographic (d², index)) over the lane's 16 rows, and the pair merges its two
+// states with one shuffle.  Result: the same key as a full direct scan and as the grid search.
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+constexpr int kMG = 2;        // 32-query groups per wave
+constexpr int kMTile = 256;   // targets per half tile (8 sub-tiles of 32)
+constexpr int kTH = 4;        // half tiles per LDS tile
+constexpr int kMTilePad = 1024; // MFMA operand arrays are padded to a multiple of every tile size
+constexpr int kMBlock = 512;  // 8 waves × kMG × 32 = 512 queries per block: every target tile
+                              // staged in LDS serves 512 queries (L2→LDS traffic per pair halved)
+constexpr int kMQueries = (kMBlock / 64) * kMG * 32;  // queries per block
+
+__device__ __forceinline__ void split16(float x, _Float16& hi, _Float16& lo) {
+  hi = (_Float16)x;
+  lo = (_Float16)(x - (float)hi);
+}
+
+union H8 {
+  uint4 u;
+  half8 h;
+};
+
+// Sign bits of 16 screen values ORed by a full-rate tree: 7 v_bitop3_b32 (a | b | c) + 1 v_or.
+__device__ __forceinline__ uint32_t or16(const floatx16& k) {
+  const auto b = [&](int i) { return __float_as_uint(k[i]); };
+  const uint32_t o0 = __builtin_amdgcn_bitop3_b32(b(0), b(1), b(2), 0xFE);
+  const uint32_t o1 = __builtin_amdgcn_bitop3_b32(b(3), b(4), b(5), 0xFE);
+  const uint32_t o2 = __builtin_amdgcn_bitop3_b32(b(6), b(7), b(8), 0xFE);
+  const uint32_t o3 = __builtin_amdgcn_bitop3_b32(b(9), b(10), b(11), 0xFE);
+  const uint32_t o4 = __builtin_amdgcn_bitop3_b32(b(12), b(13), b(14), 0xFE);
+  const uint32_t o5 = __builtin_amdgcn_bitop3_b32(o0, o1, o2, 0xFE);
+  const uint32_t o6 = __builtin_amdgcn_bitop3_b32(o3, o4, b(15), 0xFE);
+  return o5 | o6;
+}
+
+// The query's threshold as B operand elements 11-12 (lane half 1), in S² units.  thr0 =
+// ((best − |q|²) + eps)·S² carries the key's error bound; the threshold terms add their own
+// share of the MFMA's accumulation bound (32u·|thr|, as for the other products) and of the fp16
+// split (u16²|thr| + σ), with 5 % slack that also covers this sum's fp32 rounding, so that every
+// candidate's value is strictly negative.  |thr| is clamped to 32768 (fp16 range): clamping a
+// negative threshold up only adds false hits; a positive threshold that large (radius far
+// beyond the cloud's extent) sets `force`, and the group then runs the exact path everywhere.
+__device__ __forceinline__ void thr_operand(half8& b, float thr0, bool& force) {
+  const float extra = 1.05f * ((32.0f * 1.01f * 5.9604645e-08f + 2.3841858e-07f) * fabsf(thr0) +
+                               5.9604645e-08f);
+  float thr = thr0 + extra;
+  force = thr > 32768.0f;
+  thr = fminf(fmaxf(thr, -32768.0f), 32768.0f);
+  const _Float16 th = (_Float16)thr;
+  const _Float16 tl = (_Float16)(thr - (float)th);
+  b[3] = -th;
+  b[4] = -tl;
+}
+
+// target operand rows in Morton order of the grid's cells (build_mfma_tiles); 0 (A/B builds):
+// row-major cells
+#ifndef M3D_NN_TILE_MORTON
+#define M3D_NN_TILE_MORTON 1
+#endif
+// MFMA screen operands of a cloud (A rows of nn_mfma_kernel), rows in Morton order of its grid's
+// cells — or in the grid's row-major cell order, M3D_NN_TILE_MORTON=0 (build_mfma_tiles):
+// mf16 = fp16 split (+ the two constant-1 threshold slots), mf32 = (x, y, z, original index
+// bits).  Pads: key 65504 (never hit),
+// far-away coordinates (never accepted by the exact path).
+__global__ __launch_bounds__(256) void pack16_sorted_kernel(const float4* __restrict__ sorted,
+                                                            const int32_t* __restrict__ perm,
+                                                            const float4* __restrict__ xyz32,
+                                                            int64_t n, int64_t n_pad, float S,
+                                                            uint4* __restrict__ mf16,
+                                                            float4* __restrict__ mf32) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n_pad) return;
+  H8 a, b;
+  a.u = make_uint4(0, 0, 0, 0);
+  b.u = make_uint4(0, 0, 0, 0);
+  if (k < n) {
+    // row k: the k-th point of `sorted` (cell order), or of its permutation perm
+    const int32_t idx = __float_as_int(sorted[perm != nullptr ? perm[k] : k].w);
+    const float4 t = xyz32[idx];  // w = |t|² (center_pack)
+    _Float16 xh, xl, yh, yl, zh, zl, wh, wl;
+    split16(t.x * S, xh, xl);
+    split16(t.y * S, yh, yl);
+    split16(t.z * S, zh, zl);
+    split16(t.w * (S * S), wh, wl);
+    a.h = half8{xh, xh, xl, yh, yh, yl, zh, zh};
+    b.h = half8{zl, wh, wl, (_Float16)1, (_Float16)1, (_Float16)0, (_Float16)0, (_Float16)0};
+    mf32[k] = make_float4(t.x, t.y, t.z, __int_as_float(idx));
+  } else {
+    b.h[1] = (_Float16)65504.0f;  // value ≥ 65504 − 32768 > 0: never a hit
+    b.h[3] = (_Float16)1;
+    b.h[4] = (_Float16)1;
+    mf32[k] = make_float4(1.0e18f, 1.0e18f, 1.0e18f, __int_as_float(-1));
+  }
+  mf16[k] = a.u;  // two planes: elements 0-7 (lane half 0), elements 8-15 (lane half 1)
+  mf16[n_pad + k] = b.u;
+}
+
+// Box of each 256-row half tile of mf32 (one block per half): box[2·half] = (lo.xyz, ·),
+// box[2·half + 1] = (hi.xyz, ·) over the rows' exact fp32 coordinates — the values nn_exact_rows
+// feeds to d2f — pads (index bits < 0) left out; an all-pad half keeps lo = +inf, hi = −inf.
+__global__ __launch_bounds__(kMTile) void tile_box_kernel(const float4* __restrict__ mf32,
+                                                          float4* __restrict__ box) {
+  const float4 t = mf32[(int64_t)blockIdx.x * kMTile + threadIdx.x];
+  const bool real = __float_as_int(t.w) >= 0;
+  float v[6] = {real ? t.x : kInf,  real ? t.y : kInf,  real ? t.z : kInf,
+                real ? t.x : -kInf, real ? t.y : -kInf, real ? t.z : -kInf};
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const float w = __shfl_xor(v[k], o);
+      v[k] = k < 3 ? fminf(v[k], w) : fmaxf(v[k], w);
+    }
+  __shared__ float part[kMTile / 64][6];
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) part[threadIdx.x >> 6][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int w = 1; w < kMTile / 64; ++w)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = k < 3 ? fminf(v[k], part[w][k]) : fmaxf(v[k], part[w][k]);
+  box[2 * (int64_t)blockIdx.x] = make_float4(v[0], v[1], v[2], 0.0f);
+  box[2 * (int64_t)blockIdx.x + 1] = make_float4(v[3], v[4], v[5], 0.0f);
+}
+
+hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, TmpArena* ta, hipStream_t st) {
+  const int64_t n = c->n;
+  const int64_t n_pad = std::max<int64_t>((n + kMTilePad - 1) / kMTilePad * kMTilePad, kMTilePad);
+  const int32_t* perm = nullptr;  // (setup arena: consumed by pack16_sorted_kernel below)
+  hipError_t e = M3D_NN_TILE_MORTON ? grid_morton_perm(g, ta, st, &perm) : hipSuccess;
+  if (e != hipSuccess) return e;
+  e = block_alloc(reinterpret_cast<void**>(&g->mf16), sizeof(uint4) * 2 * n_pad, st);
+  if (e == hipSuccess) e = block_alloc(reinterpret_cast<void**>(&g->mf32), sizeof(float4) * n_pad, st);
+  if (e == hipSuccess)
+    e = block_alloc(reinterpret_cast<void**>(&g->mfbox), sizeof(float4) * 2 * (n_pad / kMTile), st);
+  if (e != hipSuccess) {  // all three or none (mf16 != nullptr marks the tiles as built)
+    block_release(g->mf16);
+    block_release(g->mf32);
+    block_release(g->mfbox);
+    g->mf16 = nullptr;
+    g->mf32 = nullptr;
+    g->mfbox = nullptr;
+    return e;
+  }
+  g->mf_npad = n_pad;
+  // Row order (private to nn_mfma_kernel: the exact path takes the original index from mf32.w):
+  // the grid's row-major cell order, where a 1024-row tile is a thin z-slab, or Morton order of
+  // the same cells, where it is a compact patch that fewer query boxes reach (M3D_NN_TILE_MORTON)
+  pack16_sorted_kernel<<<(unsigned)((n_pad + 255) / 256), 256, 0, st>>>(
+      g->pts, perm, c->xyz32, n, n_pad, (float)c->s16, g->mf16, g->mf32);
+  // the target of a loop never moves: the boxes are built once per (cloud, cell size) and serve
+  // every evaluation of every loop on this grid
+  tile_box_kernel<<<(unsigned)(n_pad / kMTile), kMTile, 0, st>>>(g->mf32, g->mfbox);
+  return hipGetLastError();  // asynchronous (stream order); m3d_icp_create synchronises once
+}
+
+// Self-seeding (single-device fused loop, m3d_icp_step): the fused tail of the previous
+// iteration left every key at kKeyNone, so instead of a keyinit launch every block computes
+// its queries' starting key itself (nnkey.h seed_key: the previous correspondence, exact — one
+// target load per query) and the blocks of grid.y == 0 also publish it; the MIN over the
+// blocks' atomics is the keyinit → scan result bit for bit.
+struct SeedArgs {
+  const int32_t* prev;  // corr of the previous evaluation
+  const float4* tgt;    // the target cloud's centred fp32 points, original order
+  int64_t nt;           // its size
+  int on;
+};
+
+__device__ __forceinline__ int64_t start_key(const SeedArgs& sa, const IcpState* __restrict__ s,
+                                             int64_t i, float4 p, float qx, float qy, float qz,
+                                             int64_t off, const int64_t* __restrict__ keys) {
+  return sa.on ? seed_key(s, i, p, qx, qy, qz, sa.tgt, sa.nt, off, sa.prev, nullptr) : keys[i];
+}
+
+// whether a block publishes its k1: it changed, or (self-seeding) the grid.y = 0 blocks publish
+// the seed every block started from
+__device__ __forceinline__ bool publish_k1(const SeedArgs& sa, uint64_t k1, bool changed) {
+  return changed || (sa.on && blockIdx.y == 0 && key_real(k1));
+}
+
+// Exact fallback of nn_mfma_kernel when the scaled operands do not fit fp16 (mfma_ok == 0, a
+// far-off transform): the same scan state over the block's slice by a plain scan, one thread
+// per query.
+__device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, const float4* __restrict__ tgt32,
+                              int64_t jb, int64_t je, int64_t off, const IcpState* __restrict__ s,
+                              int64_t* __restrict__ keys, uint32_t* __restrict__ near2,
+                              const SeedArgs& sa, int64_t q0) {
+  const float* Rt = s->Rt32;
+  const float r2_hi = s->r2_hi;
+  for (int qs = threadIdx.x; qs < kMQueries; qs += kMBlock) {
+    const int64_t slot = q0 + (int64_t)blockIdx.x * kMQueries + qs;
+    if (slot >= ns) return;
+    const int64_t i = slot;
+    float qx, qy, qz;
+    const float4 p = src32[i];
+    xform32(Rt, p, qx, qy, qz);
+    const int64_t key = start_key(sa, s, i, p, qx, qy, qz, off, keys);  // keyinit's starting key
+    uint64_t k1 = key == kKeyNone ? make_key(r2_hi, 0xFFFFFFFFu) : (uint64_t)key;
+    float k1d = key_real_d2(k1), n2 = kInf;
+    const uint64_t k10 = k1;
+    for (int64_t j = jb; j < je; ++j) {
+      const float4 t = tgt32[j];
+      if (__float_as_int(t.w) < 0) continue;  // pad
+      const float d2 = d2f(qx, qy, qz, t.x, t.y, t.z);
+      if (d2 <= r2_hi) near_push(k1, k1d, n2, make_key(d2, (uint32_t)(off + __float_as_int(t.w))), d2);
+    }
+    const bool pk = publish_k1(sa, k1, k1 != k10);
+    if (pk || n2 < kInf) near_publish((unsigned long long*)&keys[i], &near2[i], k1, n2, pk);
+  }
+}
+
+// Exact fp32 pass of nn_mfma_kernel over one flagged sub-tile (32 targets from `rows`), of which
+// this lane takes its 16 MFMA rows: direct d² pushed into the lane's scan state.  Pads: far
+// coordinates, d² ~ 1e36 > r2_hi.
+__device__ __forceinline__ void nn_exact_rows(const float4* __restrict__ rows, int64_t off, int h,
+                                              float qx, float qy, float qz, float r2_hi,
+                                              uint64_t& k1, float& k1d, float& n2) {
+  float4 t[16];  // all 16 loads in flight before the first use (one memory latency per sub-tile)
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) t[reg] = rows[(reg & 3) + 8 * (reg >> 2) + 4 * h];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const float d2 = d2f(qx, qy, qz, t[reg].x, t[reg].y, t[reg].z);
+    const uint64_t kc = make_key(d2, (uint32_t)(off + __float_as_int(t[reg].w)));
+    if (d2 <= r2_hi) near_push(k1, k1d, n2, kc, d2);
+  }
+}
+
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// OR of v over the wave's 64 lanes (all active), wave-uniform: DPP inside each row of 16 lanes,
+// then the four rows by v_readlane.
+__device__ __forceinline__ uint32_t wave_or32(uint32_t v) {
+  int x = (int)v;
+  x |= __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false);   // lane ^ 1
+  x |= __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, false);   // lane ^ 2
+  x |= xor4_dpp(x);
+  x |= __builtin_amdgcn_mov_dpp(x, 0x128, 0xF, 0xF, false);  // row_ror:8
+  return (uint32_t)(__builtin_amdgcn_readlane(x, 0) | __builtin_amdgcn_readlane(x, 16) |
+                    __builtin_amdgcn_readlane(x, 32) | __builtin_amdgcn_readlane(x, 48));
+}
+
+// min / max of v over the wave's 64 lanes (all active), wave-uniform: as wave_or32
+template <bool kMax>
+__device__ __forceinline__ float wave_minmax(float v) {
+  const auto mm = [](float a, float b) { return kMax ? fmaxf(a, b) : fminf(a, b); };
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false)));
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false)));
+  v = mm(v, __int_as_float(xor4_dpp(__float_as_int(v))));
+  v = mm(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false)));
+  const int x = __float_as_int(v);
+  return mm(mm(__int_as_float(__builtin_amdgcn_readlane(x, 0)), __int_as_float(__builtin_amdgcn_readlane(x, 16))),
+            mm(__int_as_float(__builtin_amdgcn_readlane(x, 32)), __int_as_float(__builtin_amdgcn_readlane(x, 48))));
+}
+
+// Box cull of the brute-force sweep.  A set of queries is summarised by the box
+// [lo, hi] of their fp32 coordinates and Xmax = the largest search bound X among them; a set of
+// targets by the box of their fp32 coordinates (Grid::mfbox).  G = d2f(g, 0) with, per axis,
+// g = max(0, qlo − thi, tlo − qhi) in fp32.
+// Lemma: d2f(q, t) ≥ G for every q in the query box and t in the target box, with no epsilon.
+//   * fp32 round-to-nearest is monotone: q − t ≥ qlo − thi in the reals gives fl(q − t) ≥
+//     fl(qlo − thi), likewise fl(t − q) ≥ fl(tlo − qhi); so |fl(q − t)| ≥ g on each axis (g = 0
+//     where the boxes overlap), and g − 0 is exact;
+//   * d2f's chain fma(dz, dz, fma(dy, dy, dx·dx)) is monotone in |dx|, |dy|, |dz|: each step is a
+//     monotone real function of non-negative arguments followed by one monotone rounding.
+// So a target set with G > Xmax holds only targets with d2f > Xmax ≥ X of every query concerned.
+// Such a target cannot become k1 (band_of(d) ≥ d, so X ≥ min(d2f(k1), r2_hi), and the exact path
+// takes d2f ≤ r2_hi only), and it cannot put a value ≤ search_bound(final k1) into near2: X only
+// ever tightens during the sweep (k1 only decreases, band_of is monotone), and near2 is only ever
+// compared with search_bound of the final k1 (nnkey.h winner_fp64; the bound-only seeds of target
+// shards reach X through the same search_bound).  Skipping the set therefore leaves every key and
+// every ambiguous / unambiguous classification as the every-pair sweep has them; near2's value
+// may differ only above the band.  The test is `G > Xmax`, strict: G = d2f = X is kept.  A NaN
+// coordinate never enters a box: fminf / fmaxf in the lane, wave and tile_box_kernel reductions
+// return the other operand.  That is harmless: a NaN point has no finite d2f, fails d2f ≤ r2_hi
+// and can never be a neighbour, swept or not.  (Should G itself come out NaN, e.g. from
+// inf − inf of an empty box, `G > Xmax` is false and the set is kept.)  M3D_NN_CULL=0 (A/B
+// build) sweeps every pair as before.
+#ifndef M3D_NN_CULL
+#define M3D_NN_CULL 1
+#endif
+struct QBox {
+  float lo[3], hi[3], X;
+};
+__device__ __forceinline__ bool box_out_of_reach(const QBox& q, const float4& tlo, const float4& thi) {
+  const float gx = fmaxf(0.0f, fmaxf(q.lo[0] - thi.x, tlo.x - q.hi[0]));
+  const float gy = fmaxf(0.0f, fmaxf(q.lo[1] - thi.y, tlo.y - q.hi[1]));
+  const float gz = fmaxf(0.0f, fmaxf(q.lo[2] - thi.z, tlo.z - q.hi[2]));
+  return d2f(gx, gy, gz, 0.0f, 0.0f, 0.0f) > q.X;
+}
+
+// ------------------------------------------------------------------------------- nn_mfma_kernel
+// Tiles of kTH × 256 targets in LDS, [buffer][lane half][target]: a half-wave's 32 ds_read_b128 hit
+// 32 consecutive 16-B slots.  The sweep runs the tile in halves of 8 sub-tiles (8 A-operand
+// registers live), one barrier per tile.  The fp32 coordinates are read from global memory by the
+// (rare) exact path only.
+constexpr int kTT = kTH * kMTile;  // targets per tile
+constexpr int kSub = kTT / 32;     // sub-tiles per tile
+constexpr uint64_t kGMask = (kSub == 64) ? ~0ull : ((1ull << kSub) - 1ull);
+constexpr int kDefer = 16;  // deferred entries per wave (more: resolved in the tile as before)
+static_assert(kMBlock == 2 * kMTile, "one 16-B operand half per thread per half tile");
+static_assert(kSub * kMG <= 64, "hit mask holds every (group, sub-tile)");
+static_assert(kSub == 32, "one 32-bit hit record per group and tile");
+static_assert(kMBlock / 64 == 8, "eight wave boxes, lanes ^1 ^2 ^4");
+
+// A lane's query of one 32-query group (column c of the group's MFMAs) and its scan state
+struct QState {
+  float qx, qy, qz, qq;  // exact-path coordinates, |q|²
+  int64_t qi;            // position in the visit order, −1: none
+  uint64_t k1;           // scan state (nnkey.h)
+  float k1d, n2;
+  half8 bq;              // B operand of the lane half: −2S·q split | threshold
+};
+
+// every sub-tile bit of the groups in `bits`, as a (group, sub-tile) mask
+__device__ __forceinline__ uint64_t group_mask(uint32_t bits) {
+  uint64_t m = 0;
+#pragma unroll
+  for (int g = 0; g < kMG; ++g)
+    if ((bits >> g) & 1u) m |= kGMask << (g * kSub);
+  return m;
+}
+
+// The query at position `slot` of the visit order ([q0, ns): order, or the slots themselves;
+// beyond ns: inactive): transform, starting key, B operand without its threshold; an active
+// query widens lq, the lane's share of its wave's query box (box_out_of_reach).  Returns the
+// search bound X, −1 for an inactive query.
+__device__ __forceinline__ float load_query(QState& q, QBox& lq, int64_t slot, int h,
+                                            const float4* __restrict__ src32, int64_t ns,
+                                            const IcpState* __restrict__ s, const SeedArgs& sa, int64_t off,
+                                            const int64_t* __restrict__ keys) {
+  const float* Rt = s->Rt32;
+  const float r2_hi = s->r2_hi, S = s->mfma_scale;
+  const int64_t i = slot < ns ? slot : -1;
+  q.qi = i;
+  q.n2 = kInf;
+  float X = -1.0f;
+  if (i >= 0) {
+    const float4 p = src32[i];
+    xform32(Rt, p, q.qx, q.qy, q.qz);
+    const int64_t key = start_key(sa, s, i, p, q.qx, q.qy, q.qz, off, keys);
+    q.k1 = key == kKeyNone ? make_key(r2_hi, 0xFFFFFFFFu) : (uint64_t)key;
+    X = search_bound(key_d2(q.k1), s->band_e, r2_hi);
+    lq.lo[0] = fminf(lq.lo[0], q.qx);
+    lq.lo[1] = fminf(lq.lo[1], q.qy);
+    lq.lo[2] = fminf(lq.lo[2], q.qz);
+    lq.hi[0] = fmaxf(lq.hi[0], q.qx);
+    lq.hi[1] = fmaxf(lq.hi[1], q.qy);
+    lq.hi[2] = fmaxf(lq.hi[2], q.qz);
+    lq.X = fmaxf(lq.X, X);
+  } else {
+    q.qx = q.qy = q.qz = 0.0f;
+    q.k1 = (uint64_t)kKeyNone;
+  }
+  q.k1d = key_real_d2(q.k1);
+  q.qq = fmaf(q.qz, q.qz, fmaf(q.qy, q.qy, q.qx * q.qx));
+  _Float16 ah, al, bh, bl, ch, cl;
+  split16(-2.0f * S * q.qx, ah, al);
+  split16(-2.0f * S * q.qy, bh, bl);
+  split16(-2.0f * S * q.qz, ch, cl);
+  const _Float16 one = (_Float16)1.0f, zero = (_Float16)0.0f;
+  q.bq = h == 0 ? half8{ah, al, ah, bh, bl, bh, ch, cl} : half8{ch, one, one, zero, zero, zero, zero, zero};
+  return X;
+}
+
+// The query's threshold for search bound X (< 0: never hits) into its B operand (thr_operand);
+// returns whether it exceeds the fp16 range.  Setup and after every exact pass: the threshold
+// only ever tightens, so a group that was not `force` at setup never becomes it.
+__device__ __forceinline__ bool refresh_threshold(QState& q, int h, float X, float eps, float S2) {
+  bool fg;
+  half8 bt = q.bq;
+  thr_operand(bt, X < 0.0f ? -1.0f : ((X - q.qq) + eps) * S2, fg);  // × power of two: exact
+  if (h == 1) q.bq = bt;
+  return fg;
+}
+
+// The cull's query boxes (box_out_of_reach above): the box and Xmax of each wave's active queries
+// by a DPP reduction, published in LDS as qbox[wave] = (lo.xyz, Xmax), (hi.xyz, ·); the block's
+// box, returned in SGPRs, is their union: lane l takes wave l & 7's, three DPP steps merge the
+// eight.  (The wave boxes stay in LDS and are read back by the rare survivor rounds: held in
+// registers across the sweep they cost spills.)
+__device__ __forceinline__ QBox reduce_boxes(const QBox& lq, float4 (&qbox)[kMBlock / 64][2], int lane, int wave) {
+  float wlo[3], whi[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    wlo[k] = wave_minmax<false>(lq.lo[k]);
+    whi[k] = wave_minmax<true>(lq.hi[k]);
+  }
+  const float wX = wave_minmax<true>(lq.X);
+  if (lane == 0) {
+    qbox[wave][0] = make_float4(wlo[0], wlo[1], wlo[2], wX);
+    qbox[wave][1] = make_float4(whi[0], whi[1], whi[2], 0.0f);
+  }
+  __syncthreads();
+  float4 lo = qbox[lane & 7][0], hi = qbox[lane & 7][1];
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    const auto x = [&](float v) { return __int_as_float(xor_lane(__float_as_int(v), o, kWave)); };
+    lo = make_float4(fminf(lo.x, x(lo.x)), fminf(lo.y, x(lo.y)), fminf(lo.z, x(lo.z)), fmaxf(lo.w, x(lo.w)));
+    hi = make_float4(fmaxf(hi.x, x(hi.x)), fmaxf(hi.y, x(hi.y)), fmaxf(hi.z, x(hi.z)), 0.0f);
+  }
+  const auto u = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+  return QBox{{u(lo.x), u(lo.y), u(lo.z)}, {u(hi.x), u(hi.y), u(hi.z)}, u(lo.w)};
+}
+
+// The block's surviving tiles, in order.  The block skips, block-uniformly, every tile of its
+// strided set (tc, tc + ty, …) none of whose half tiles its box can reach (no DMA, no sweep, no
+// barrier); inside a surviving tile a wave sweeps only the half tiles its own box can reach.
+// 16 tiles per round: lane l tests half tile l & 3 of tile tc + (l >> 2)·ty against both boxes
+// (one round of box loads per 16 tiles).  mb: half tiles the block reaches — a tile survives if
+// any of its four bits is set; mw ⊆ mb: those this wave reaches.  Every wave computes mb from the
+// same data by the same instructions.
+struct TileCursor {
+  const float4* tbox;   // Grid::mfbox
+  const float4* wbox;   // this wave's box, qbox[wave] (LDS)
+  QBox bx;              // the block's box
+  int lane, ntile, ty;  // tiles in all, the set's stride (gridDim.y)
+  int tc;               // first tile of the current round
+  uint64_t mb, mw;
+
+  __device__ __forceinline__ void cull_round() {
+    const int tl = tc + (lane >> 2) * ty;
+    bool kb = tl < ntile, kw = kb;
+    if (M3D_NN_CULL && kb) {
+      const int64_t hb = (int64_t)tl * kTH + (lane & 3);  // < nt_pad / kMTile
+      const float4 tlo = tbox[2 * hb], thi = tbox[2 * hb + 1];
+      const float4 l0 = wbox[0], u0 = wbox[1];
+      const QBox wq{{l0.x, l0.y, l0.z}, {u0.x, u0.y, u0.z}, l0.w};
+      kb = !box_out_of_reach(bx, tlo, thi);
+      kw = !box_out_of_reach(wq, tlo, thi);
+    }
+    mb = __ballot(kb);
+    mw = __ballot(kw);
+  }
+  // next surviving tile (ntile: none left) and this wave's half-tile mask of it
+  __device__ __forceinline__ void next(int& t, uint32_t& hmask) {
+    for (;;) {
+      if (mb != 0) {
+        const int k = __builtin_ctzll(mb) >> 2;
+        t = tc + k * ty;
+        hmask = (uint32_t)(mw >> (4 * k)) & 15u;
+        mb &= ~(15ull << (4 * k));
+        return;
+      }
+      tc += 16 * ty;
+      if (tc >= ntile) {
+        t = ntile;
+        hmask = 0;
+        return;
+      }
+      cull_round();
+    }
+  }
+};
+
+// Tile t's operands global → LDS: thread x stages kTH elements e = x + u·512, plane e / kTT,
+// target e % kTT (mf16 is stored as two planes, so the loads are coalesced).  dma: by LDS DMA
+// (lds_dma.h), no prefetch registers — a wave's 64 elements are one plane's 64 consecutive
+// targets; the caller retires it with lds_dma_wait().
+__device__ __forceinline__ void stage_tile(uint4 (&dst)[2][kTT], const uint4* __restrict__ tgt16,
+                                           int64_t nt_pad, int t, bool dma) {
+#pragma unroll
+  for (int u = 0; u < kTH; ++u) {
+    const int e = threadIdx.x + u * kMBlock;
+    const uint4* src = tgt16 + (e / kTT) * nt_pad + (int64_t)t * kTT + e % kTT;
+    if (dma)
+      lds_dma16(src, &dst[e / kTT][(e % kTT) & ~63]);
+    else
+      dst[e / kTT][e % kTT] = *src;
+  }
+}
+
+// Sweep of one tile: MFMA + sign-OR test for the tile's sub-tiles, branch-free.  A step records
+// its sign bit in the lane's own shift register of its group (v_alignbit: rec = rec << 1 | sign),
+// so the step is vector instructions only; the wave looks at the records once per tile
+// (hit_mask).  Software-pipelined: the MFMA of step t+1 is issued before step t's tree, so a wave
+// never waits on its own MFMA.  hmask: the half tiles this wave's box reaches.
+__device__ __forceinline__ void sweep_tile(uint32_t (&rec)[kMG], const uint4 (&t16)[2][2][kTT], int buf,
+                                           int h, int c, uint32_t hmask, const QState (&q)[kMG],
+                                           const floatx16& zacc) {
+#pragma unroll
+  for (int g = 0; g < kMG; ++g) rec[g] = 0;
+  constexpr int kSteps = 8 * kMG;  // (sub-tile, group) steps of one half tile
+#pragma unroll
+  for (int half = 0; half < kTH; ++half) {
+    // a half tile out of this wave's reach (wave-uniform: a scalar branch): its 8 steps' bits
+    // are zeros, so that bfrev / ctz still address the sub-tiles
+    if (!((hmask >> half) & 1u)) {
+#pragma unroll
+      for (int g = 0; g < kMG; ++g) rec[g] <<= 8;
+      continue;
+    }
+    H8 av[8];
+#pragma unroll
+    for (int sub = 0; sub < 8; ++sub) av[sub].u = t16[buf][h][half * kMTile + sub * 32 + c];
+    floatx16 kc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0].h, q[0].bq, zacc, 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < kSteps; ++t) {
+      floatx16 kn;
+      if (t + 1 < kSteps)
+        kn = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[(t + 1) / kMG].h, q[(t + 1) % kMG].bq, zacc, 0, 0, 0);
+      // keep the pipeline the source states: without this fence the scheduler sinks each
+      // MFMA next to its consumer (same accumulator registers, the VALU then waits out the
+      // whole MFMA latency every step and the matrix pipe idles under the tree)
+      __builtin_amdgcn_sched_barrier(0);
+      // a candidate's value is strictly negative: OR of the 16 bit patterns, test bit 31
+      rec[t % kMG] = __builtin_amdgcn_alignbit(rec[t % kMG], or16(kc), 31);
+      __builtin_amdgcn_sched_barrier(0);
+      if (t + 1 < kSteps) kc = kn;
+    }
+  }
+}
+
+// One wave-level test per tile (hits are rare): only a tile with a hit ORs the records over the
+// wave into the (group, sub-tile) mask.  Sub-tile 0 was pushed first: bit 31, hence bfrev.
+// `force` groups (force64) add every sub-tile of the half tiles swept (the lemma is about d2f).
+__device__ __forceinline__ uint64_t hit_mask(const uint32_t (&rec)[kMG], uint32_t hmask, uint64_t force64) {
+  uint64_t hm = 0;
+  uint32_t any = rec[0];
+#pragma unroll
+  for (int g = 1; g < kMG; ++g) any |= rec[g];
+  if (__any(any != 0)) {
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) hm |= (uint64_t)wave_or32(__builtin_bitreverse32(rec[g])) << (g * kSub);
+  }
+  uint32_t sm = 0;
+#pragma unroll
+  for (int half = 0; half < kTH; ++half)
+    if ((hmask >> half) & 1u) sm |= 0xFFu << (8 * half);
+  uint64_t fm = 0;
+#pragma unroll
+  for (int g = 0; g < kMG; ++g) fm |= (uint64_t)sm << (g * kSub);
+  return hm | (force64 & fm);
+}
+
+// Exact path for one group's flagged sub-tiles mg of the tile whose rows start at `tile`, every
+// lane (exact for any lane): direct fp32 d² over the lane's 16 rows, then the lane pair
+// (c, c + 32) merges its two states.  Returns whether k1 changed.
+__device__ __forceinline__ bool nn_exact_subtiles(uint64_t mg, const float4* __restrict__ tile, int64_t off,
+                                                  int h, float r2_hi, QState& q) {
+  const uint64_t kb = q.k1;
+  while (mg != 0) {
+    const int sub = __builtin_ctzll(mg);
+    mg &= mg - 1;
+    nn_exact_rows(tile + sub * 32, off, h, q.qx, q.qy, q.qz, r2_hi, q.k1, q.k1d, q.n2);
+    const uint64_t o1 = shfl_xor64(q.k1, 32);
+    const float on2 = __shfl_xor(q.n2, 32);
+    near_merge(q.k1, q.k1d, q.n2, o1, on2);
+  }
+  return q.k1 != kb;
+}
+
+__global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(const float4* __restrict__ src32,
+                                                          int64_t ns,
+                                                          const uint4* __restrict__ tgt16,
+                                                          const float4* __restrict__ tgt32,
+                                                          const float4* __restrict__ tbox,
+                                                          int64_t nt_pad, int64_t off,
+                                                          const IcpState* __restrict__ s,
+                                                          int64_t* __restrict__ keys,
+                                                          uint32_t* __restrict__ near2,
+                                                          SeedArgs sa, int64_t q0) {
+  if (s->done) return;
+  // grid.y block y takes every gridDim.y-th target tile (strided: a query block's few candidate
+  // tiles, adjacent in row order, spread over gridDim.y blocks instead of landing in one)
+  if (!s->mfma_ok) {  // the same tiles by a plain scan, unculled
+    const int64_t tstep = (int64_t)gridDim.y * kTT;
+    for (int64_t t0 = (int64_t)blockIdx.y * kTT; t0 < nt_pad; t0 += tstep)
+      nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTT), off, s, keys, near2, sa, q0);
+    return;
+  }
+  __shared__ uint4 t16[2][2][kTT];
+  __shared__ uint64_t dlist[kMBlock / 64][kDefer];  // deferred: flagged (group, sub-tile) bits
+  __shared__ uint32_t dtile[kMBlock / 64][kDefer];  // their tile's first target
+  __shared__ float4 qbox[kMBlock / 64][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const float r2_hi = s->r2_hi, eps = s->screen_eps_m, S = s->mfma_scale, be = s->band_e;
+  const float S2 = S * S;
+
+  // queries: per-group state, the lane's box share, group masks
+  QState q[kMG];
+  uint32_t act = 0;    // groups whose query (column c) exists
+  uint32_t force = 0;  // groups whose threshold exceeds the fp16 range: exact path everywhere
+  uint32_t chg = 0;    // groups whose k1 left its starting key (k1 only ever decreases)
+  QBox lq{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}, -1.0f};
+#pragma unroll
+  for (int g = 0; g < kMG; ++g) {
+    const int64_t slot = q0 + (int64_t)blockIdx.x * kMQueries + (wave * kMG + g) * 32 + c;
+    const float X = load_query(q[g], lq, slot, h, src32, ns, s, sa, off, keys);
+    if (q[g].qi >= 0) act |= 1u << g;
+    if (__any(refresh_threshold(q[g], h, X, eps, S2))) force |= 1u << g;
+  }
+  const floatx16 zacc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
+                         0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  // Deferred exact passes: a group whose every query starts from a real seed already screens
+  // with (nearly) its final threshold, so its flagged sub-tiles need not be resolved inside the
+  // tile — where one wave's exact pass holds the block's other 7 waves at the tile barrier —
+  // but can wait in a per-wave list (tile offset, flagged bits) until after the sweep (−2.2 %
+  // per launch at cfg1).  The candidates evaluated are the same sub-tiles' rows, so
+  // the key is the same.  Unseeded groups and a full list resolve in the tile, where the
+  // threshold refresh still prunes the rest of the sweep.
+  uint32_t dfr = 0;
+#pragma unroll
+  for (int g = 0; g < kMG; ++g)
+    if (!((force >> g) & 1u) && __all(q[g].qi < 0 || key_real(q[g].k1))) dfr |= 1u << g;
+  int dn = 0;
+  uint64_t dmask = group_mask(dfr);
+  dmask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(dmask >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dmask);  // wave-uniform: SGPRs
+
+  const QBox bx = reduce_boxes(lq, qbox, lane, wave);
+  const int ntile = (int)(nt_pad / kTT);
+  TileCursor cur{tbox, qbox[wave], bx, lane, ntile, (int)gridDim.y, (int)blockIdx.y, 0, 0};
+  cur.cull_round();
+  int t0, t1;
+  uint32_t h0, h1;  // the wave's half-tile masks of tiles t0, t1
+  cur.next(t0, h0);
+  if (t0 < ntile) stage_tile(t16[0], tgt16, nt_pad, t0, false);
+  const uint64_t force64 = group_mask(force);
+  __syncthreads();
+  int buf = 0;
+  for (; t0 < ntile; t0 = t1, h0 = h1) {
+    const int64_t j0 = (int64_t)t0 * kTT;
+    cur.next(t1, h1);
+    // the next surviving tile while this one is swept
+    if (t1 < ntile) stage_tile(t16[buf ^ 1], tgt16, nt_pad, t1, true);
+    uint32_t rec[kMG];
+    sweep_tile(rec, t16, buf, h, c, h0, q, zacc);
+    uint64_t hm = hit_mask(rec, h0, force64);
+    const uint64_t hd = hm & dmask;
+    if (hd != 0 && dn < kDefer) {
+      if (lane == 0) {
+        dlist[wave][dn] = hd;
+        dtile[wave][dn] = (uint32_t)j0;
+      }
+      ++dn;
+      hm &= ~hd;
+    }
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) {
+      const uint64_t mg = (hm >> (g * kSub)) & kGMask;
+      if (mg == 0) continue;
+      chg |= (uint32_t)nn_exact_subtiles(mg, tgt32 + j0, off, h, r2_hi, q[g]) << g;
+      refresh_threshold(q[g], h, (act >> g) & 1u ? search_bound(key_d2(q[g].k1), be, r2_hi) : -1.0f, eps, S2);
+    }
+    lds_dma_wait();
+    __syncthreads();
+    buf ^= 1;
+  }
+  // the deferred exact passes (rows from global memory: the tiles have left LDS)
+  for (int e = 0; e < dn; ++e) {
+    const uint64_t ent = dlist[wave][e];
+    const float4* tile = tgt32 + (int64_t)dtile[wave][e];
+#pragma unroll
+    for (int g = 0; g < kMG; ++g)
+      chg |= (uint32_t)nn_exact_subtiles((ent >> (g * kSub)) & kGMask, tile, off, h, r2_hi, q[g]) << g;
+  }
+#pragma unroll
+  for (int g = 0; g < kMG; ++g) {
+    if (h != 0 || q[g].qi < 0) continue;
+    const bool pk = publish_k1(sa, q[g].k1, (chg >> g) & 1u);
+    if (pk || q[g].n2 < kInf)
+      near_publish((unsigned long long*)&keys[q[g].qi], &near2[q[g].qi], q[g].k1, q[g].n2, pk);
+  }
+}
+
+// grid.y of nn_mfma_kernel for bx query blocks and ntiles target tiles (block y takes every
+// grid.y-th tile); slots = the blocks resident on the device at once, 0 = unknown.
+// Every-pair sweep (M3D_NN_CULL=0): pick S in [S0, 2·S0], S0 = 2048 / grid.x, so that the block
+// count fills the resident block slots in whole rounds (the last partial round of equal-length
+// blocks idles the rest of the chip: 196 × 11 blocks on 512 slots = 4.2 rounds ran as 5).  Culled
+// sweep: a block keeps only a few of its tiles, its setup (query load, seed gather, boxes,
+// survivor round) weighs as much as what is left of the sweep, and the blocks' lengths differ —
+// the fewest slices that fill the slots once, S = ⌈slots / grid.x⌉ (EXPERIMENTS §3.5: cfg1 59 µs
+// at S = 3 against 63–73 at 4–6 and 86 at 13; the 1M pair fastest at S = 1).  The rule rests on
+// those two shapes only.  With few query blocks it degenerates to one tile per block (grid.x = 1
+// gives S = ntiles, the clamp): every block then pays the setup for at most one tile.
+// Unknown slots: S0 blocks per query block, evened out to equal tile counts.
+static int64_t nn_grid_y(int64_t bx, int64_t ntiles, int64_t slots, bool cull) {
+  const auto clamped = [&](int64_t S) { return std::min(std::max<int64_t>(S, 1), ntiles); };
+  const int64_t s0 = clamped((2048 + bx - 1) / bx);
+  if (slots <= 0 || ntiles <= 1) {
+    const int64_t per = (ntiles + s0 - 1) / s0;  // tiles per block
+    return (ntiles + per - 1) / per;
+  }
+  if (cull) return clamped((slots + bx - 1) / bx);
+  int64_t best = s0;
+  double best_eff = 0.0;
+  for (int64_t S = s0; S <= std::min(2 * s0, ntiles); ++S) {
+    const int64_t blocks = bx * S, rounds = (blocks + slots - 1) / slots;
+    const double eff = (double)blocks / (double)(rounds * slots);
+    if (eff > best_eff + 1e-9) {
+      best_eff = eff;
+      best = S;
+    }
+  }
+  return best;
+}
+
+static bool icp_nn_uses_mfma(const m3d_icp* s) {
+  return s->tgrid != nullptr && s->tgrid->mf16 != nullptr;
+}
+
+// whether the loop's NN can run on a slot range [q0, q1) of the visit order: the grid form needs
+// the source's Morton query grid; the brute form always can (m3d_icp_create builds its tiles)
+bool icp_nn_range_ok(const m3d_icp* s) {
+  if (s->params.nn_method == M3D_NN_GRID) return s->sgrid != nullptr && s->sgrid->mpts != nullptr;
+  return icp_nn_uses_mfma(s);
+}
+
+// Brute-force NN into s->keys (after launch_icp_keyinit, or self_seed: keys all kKeyNone, see
+// SeedArgs): nn_mfma_kernel alone (its exact in-kernel scan covers transforms whose operands do
+// not fit fp16).  m3d_icp_create builds the target's MFMA tiles for every brute-force loop.
+hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStream_t st, int64_t q0,
+                         int64_t q1) {
+  const int64_t ns = q1 < 0 ? s->src->n : q1;  // queries: visit positions [q0, ns)
+  if (ns <= q0 || s->tgt->n == 0) return hipSuccess;
+  const Grid* tg = s->tgrid;
+  const int64_t tt = (int64_t)kTH * kMTile;
+  if (!icp_nn_uses_mfma(s) || tg->mf_npad % tt != 0) return hipErrorInvalidValue;  // pack16 pads to kMTilePad
+  static const int64_t slots = [] {
+    int dev = 0, per = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return (int64_t)0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_kernel, kMBlock, 0) != hipSuccess)
+      return (int64_t)0;
+    return (int64_t)p.multiProcessorCount * (per > 0 ? per : 1);
+  }();
+  const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
+  const dim3 gm((unsigned)bx, (unsigned)nn_grid_y(bx, tg->mf_npad / tt, slots, M3D_NN_CULL != 0));
+  const SeedArgs sa{s->corr, s->tgt->xyz32, s->tgt->n, self_seed ? 1 : 0};
+  nn_mfma_kernel<<<gm, kMBlock, 0, st>>>(s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox, tg->mf_npad, off,
+                                         s->state, s->keys, s->near2, sa, q0);
+  return hipGetLastError();
+}
+
+}  // namespace m3d

@@ -1,5 +1,5 @@
 // nnkey.h — the fp32 query/distance expressions, packed keys and the fp64 resolution shared by
-// every NN kernel (icp.hip nn_mfma_kernel / nn_kernel / keyinit / terms, grid.hip grid_nn_kernel).
+// every NN kernel (nn_brute.hip nn_mfma_kernel, icp.hip keyinit / terms, grid.hip grid_nn_kernel).
 //
 // Result contract (Open3D KDTreeFlann::SearchHybrid(p, r, 1) in fp64): for each
 // source point the lexicographic (d64, index) minimum over the targets with d64 < r², where

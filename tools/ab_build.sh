@@ -6,8 +6,8 @@ name=$1; shift
 cd "$(dirname "$0")/../3d-matching_amd/csrc"
 out=/tmp/ab_$name; rm -rf $out; mkdir -p $out ../../tools/ab
 F="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -I../../include -w $*"
-X=${ABX:-"-fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form"}  # ransac/icp flags (ABX overrides)
-for f in ransac icp; do /opt/rocm/bin/hipcc $F $X -c $f.hip -o $out/$f.o & done
+X=${ABX:-"-fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form"}  # ransac/icp/nn_brute flags (ABX overrides)
+for f in ransac icp nn_brute; do /opt/rocm/bin/hipcc $F $X -c $f.hip -o $out/$f.o & done
 for f in grid prep feat; do /opt/rocm/bin/hipcc $F -c $f.hip -o $out/$f.o & done
 for f in api comm hostio; do /opt/rocm/bin/hipcc $F -x hip -c $f.cpp -o $out/$f.o & done
 wait

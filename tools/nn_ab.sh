@@ -12,6 +12,7 @@ for r in $(seq 1 "${ROUNDS:-3}"); do
   for v in "$@"; do
     echo "round $r $v:" >> gpurun_out/nn_ab.log
     AB_LIB=tools/ab/$v.so timeout -k 10 300 python3 "$S" ${ARGS:-20} 2>&1 | grep -v amdgpu.ids >> gpurun_out/nn_ab.log
+    (exit "${PIPESTATUS[0]}")  # $? = the timing run's status, not grep's
     rc=$?; [ $rc -eq 0 ] || { echo "stopping after $v rc=$rc"; tail -20 gpurun_out/nn_ab.log; exit $rc; }
   done
 done
