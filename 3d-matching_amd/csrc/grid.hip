@@ -128,9 +128,6 @@ __global__ __launch_bounds__(kGridBlock) void grid_gather_kernel(const float4* _
                     // grid scan, s_memrealtime (100 MHz)
 __device__ unsigned long long g_scan_clock[2 * 65536];
 #endif
-#ifndef M3D_SCAN_PHASE1
-#define M3D_SCAN_PHASE1 1
-#endif
 // append query t to the deferral list; a slot at or past the list's capacity (a count the loop
 // did not produce: it starts at zero at creation and at every reset) is dropped and flagged in
 // hcnt[kDeferFault] (m3d_icp_result_get then fails) — never written out of bounds
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(kGridBlock) void grid_nn_batched_kernel(
     k1d = key_real_d2(k1);
     if (g.ncells > 0 && !far) {
       float R = sqrtf(search_bound(key_d2(k1), be, r2_hi)) * 1.001f;
-      if (M3D_SCAN_PHASE1 && 2.0f * R * g.inv_h > 3.0f) {
+      if (2.0f * R * g.inv_h > 3.0f) {
         // a box wider than ~4 cells per axis (no seed, or a seed the update moved far — the first
         // evaluations; a dense target, where the cells are r/2 … r/4): the half-cell box around
         // the query first, every lane over every point (so each lane's state holds the same
@@ -273,12 +270,6 @@ __global__ __launch_bounds__(kGridBlock) void grid_nn_heavy_kernel(
     }
     const float4 p = qpts[t];
     const int64_t i = (int64_t)__float_as_int(p.w);
-#ifdef M3D_DEBUG_GUARDS
-    if (i < 0 || i >= nq) {
-      if (threadIdx.x == 0) printf("[guard] heavy t %lld: i %lld outside [0, %lld)\n", (long long)t, (long long)i, (long long)nq);
-      continue;
-    }
-#endif
     float qx, qy, qz;
     xform32(s->Rt32, p, qx, qy, qz);
     const int64_t seed = seed_key(s, i, p, qx, qy, qz, tgt32, nt_shard, off, prev, dprev);
@@ -348,9 +339,6 @@ __global__ __launch_bounds__(kGridBlock) void grid_nn_heavy_kernel(
           const float4 v = g.pts[j];
           if (!(d2f(qx, qy, qz, v.x, v.y, v.z) <= X)) continue;
           const int64_t lj = (int64_t)__float_as_int(v.w);
-#ifdef M3D_DEBUG_GUARDS
-          if (lj < 0 || lj >= nt_shard) { printf("[guard] heavy resolve lj %lld nt %lld j %d\n", (long long)lj, (long long)nt_shard, j); continue; }
-#endif
           const double* tp = tgt64 + 3 * lj;
           const double dx = Q[0] - tp[0], dy = Q[1] - tp[1], dz = Q[2] - tp[2];
           const double d = (dx * dx + dy * dy) + dz * dz;

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <stdlib.h>
 
@@ -34,17 +35,7 @@ namespace m3d {
 // terms pass geometry: 512-thread blocks, one source per thread (196 block partials at cfg1, as
 // 256 × 2 gave): two waves per SIMD share the fp64 work and hide each other's round trips — the
 // last terms wave of a cfg1 evaluation ends ≈ 1 µs sooner (docs/EXPERIMENTS.md §R6)
-#ifndef M3D_TERMS_BLOCK
-#define M3D_TERMS_BLOCK 512
-#endif
-constexpr int kTermsBlock = M3D_TERMS_BLOCK;
-#ifndef M3D_TERMS_PTS
-#define M3D_TERMS_PTS 1
-#endif
-constexpr int kTermsPtsDefault = M3D_TERMS_PTS;  // sources per terms thread (with 256-thread blocks
-                                                 // 2 was fastest: 1 doubled the partials, 4 / 8
-                                                 // lengthened each wave's chain)
-static int terms_pts() { return kTermsPtsDefault; }
+constexpr int kTermsBlock = 512;
 constexpr double kU = 5.9604644775390625e-08;
 constexpr double kU64 = 1.1102230246251565e-16;
 
@@ -102,13 +93,9 @@ __device__ void refresh_rt32_from(IcpState* s, const double* T, double r2, doubl
   // the fp32 part, term by term (xform32: q = fma(r0, px, fma(r1, py, fma(r2, pz, t′)))):
   // p rounding u·Σ|r||p| + R rounding u·Σ|r||p| + three fma roundings ≤ 3u(Σ|r||p| + |t′|) +
   // t′ rounding u|t′| + the target's u|t_c|, Σ|r||p| ≤ ‖r‖₁·|p|∞; ×1.01 for the O(u²) products.
-  // (Round 5 used 8u·(‖r‖₁|p|∞ + |t′| + |t|): 2.6× this at cfg1, and the fp32 → fp64 ambiguity
-  // band, hence the terms pass's fp64 walks, scale with E.)
-#ifndef M3D_TIGHT_E
-#define M3D_TIGHT_E 1
-#endif
-  const double E32 = M3D_TIGHT_E ? 1.01 * kU * (5.0 * rowl1 * pinf + 4.0 * tinf + qinf)
-                                 : 8.0 * kU * (rowl1 * pinf + tinf + qinf);
+  // (Term by term because the fp32 → fp64 ambiguity band, hence the terms pass's fp64 walks, scale
+  // with E.)
+  const double E32 = 1.01 * kU * (5.0 * rowl1 * pinf + 4.0 * tinf + qinf);
   const double E = E32 + 8.0 * kU64 * 1.7320508075688772 * (double)(iters + 2) * mag + 1e-11 * (mag + 1.0);
   // nnkey.h: |√d2f − |Q − t|| ≤ e_q + 3u√d2f with e_q = √3·E; band_of's absolute term 2·e_q
   const double eq = 1.7320508075688772 * E * 1.01;
@@ -161,6 +148,20 @@ __device__ __forceinline__ void set_identity(double* M) {
   for (int k = 0; k < 16; ++k) M[k] = (k % 5 == 0) ? 1.0 : 0.0;
 }
 
+// The common end of the state-setup kernels below, after T and dT are written: nothing evaluated
+// yet, radius r2, the search transform of T.  bound_ok = 0: keys / corr belong to another
+// transform, so no bound seeds until the next update.
+__device__ __forceinline__ void reset_eval(IcpState* s, double r2, const FrameParams& f) {
+  s->fitness = s->rmse = s->prev_fitness = s->prev_rmse = 0.0;
+  s->count = 0;
+  s->evals = s->iters = s->done = s->converged = 0;
+  s->ticket = 0;
+  s->r2 = r2;
+  s->bound_ok = 0;
+  refresh_rt32(s, f);
+  s->eq_prev = s->eq;
+}
+
 // apply_init: the points start as init·p (the loop's pcd64 holds p, dT = init); 0: as p (dT = I),
 // Open3D's RegistrationICP for an init that isIdentity() — T still starts at init
 __global__ void icp_init_kernel(IcpState* s, double T0, double T1, double T2, double T3, double T4,
@@ -173,14 +174,7 @@ __global__ void icp_init_kernel(IcpState* s, double T0, double T1, double T2, do
   s->T[15] = 1.0;
   for (int k = 0; k < 16; ++k) s->dT[k] = apply_init ? s->T[k] : ((k % 5 == 0) ? 1.0 : 0.0);
   set_identity(s->last_upd);
-  s->fitness = s->rmse = s->prev_fitness = s->prev_rmse = 0.0;
-  s->count = 0;
-  s->evals = s->iters = s->done = s->converged = 0;
-  s->ticket = 0;
-  s->r2 = r2;
-  s->bound_ok = 0;
-  refresh_rt32(s, f);
-  s->eq_prev = s->eq;
+  reset_eval(s, r2, f);
 }
 
 // state for evaluating transform T (device, row-major 4×4): feature-RANSAC validation (a6)
@@ -188,14 +182,7 @@ __global__ void icp_set_T_kernel(IcpState* s, const double* __restrict__ T, doub
   if (threadIdx.x != 0) return;
   for (int k = 0; k < 16; ++k) s->T[k] = s->dT[k] = T[k];  // the loop's pcd64 holds p
   set_identity(s->last_upd);
-  s->fitness = s->rmse = s->prev_fitness = s->prev_rmse = 0.0;
-  s->count = 0;
-  s->evals = s->iters = s->done = s->converged = 0;
-  s->ticket = 0;
-  s->r2 = r2;
-  s->bound_ok = 0;  // keys/corr of another transform: no bound seeds until the next update
-  refresh_rt32(s, f);
-  s->eq_prev = s->eq;
+  reset_eval(s, r2, f);
 }
 
 // a6 batched validation (grid.hip validate_kernel): one evaluation state per hypothesis, with
@@ -209,14 +196,7 @@ __global__ __launch_bounds__(64) void val_states_kernel(IcpState* __restrict__ s
   IcpState* s = states + k;
   const double* Th = T + 16 * (int64_t)list[k];
   for (int j = 0; j < 16; ++j) s->T[j] = s->dT[j] = Th[j];  // validation reads the source itself
-  s->fitness = s->rmse = s->prev_fitness = s->prev_rmse = 0.0;
-  s->count = 0;
-  s->evals = s->iters = s->done = s->converged = 0;
-  s->ticket = 0;
-  s->r2 = r2;
-  s->bound_ok = 0;
-  refresh_rt32(s, f);
-  s->eq_prev = s->eq;
+  reset_eval(s, r2, f);
 }
 
 // ------------------------------------------------------------------------------- keyinit
@@ -244,7 +224,7 @@ __global__ __launch_bounds__(256) void keyinit_kernel(const float4* __restrict__
 // Transposing wave reduction of 32 per-lane slots: each butterfly step halves the slots a lane
 // keeps (the partner gets the other half), so 32 slots cost 31 pair exchanges instead of
 // 32 × 6 full butterflies.  Steps 32 and 16 use the gfx950 permlane swaps (no selects);
-// 8, 4, 2 exchange by shuffles; the last step adds the two lanes of a pair.  Afterwards lanes
+// 8, 4, 2 exchange by DPP moves; the last step adds the two lanes of a pair.  Afterwards lanes
 // 2k and 2k+1 both hold the wave's sum of slot k.  A fixed tree: deterministic.
 template <bool k32>
 __device__ __forceinline__ double swap_add(double a, double b) {
@@ -260,33 +240,13 @@ __device__ __forceinline__ double swap_add(double a, double b) {
   return na + nb;  // lanes of bit 0: a-slot over both halves; bit 1: b-slot
 }
 
-#ifndef M3D_SUM_DPP
-#define M3D_SUM_DPP 1
-#endif
-// v from lane ^ kOff (all lanes active): DPP for 1 and 2 (quad permutes), 4 (two moves, xor4_dpp)
-// and 8 (a rotation by 8 inside a 16-lane row is lane ^ 8), without the LDS unit's round trip; a
-// shuffle otherwise
-template <int kOff>
-__device__ __forceinline__ double xor_lane64(double v) {
-  constexpr int ctrl = kOff == 1 ? 0xB1 : kOff == 2 ? 0x4E : kOff == 8 ? 0x128 : -1;
-  if (M3D_SUM_DPP && M3D_DPP_X4 && kOff == 4) {
-    const long long b = __double_as_longlong(v);
-    const int lo = xor4_dpp((int)(uint32_t)b), hi = xor4_dpp((int)(uint32_t)(b >> 32));
-    return __longlong_as_double(((long long)(uint32_t)hi << 32) | (uint32_t)lo);
-  }
-  if (M3D_SUM_DPP && ctrl >= 0) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)b, ctrl < 0 ? 0 : ctrl, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(b >> 32), ctrl < 0 ? 0 : ctrl, 0xF, 0xF, false);
-    return __longlong_as_double(((long long)(uint32_t)hi << 32) | (uint32_t)lo);
-  }
-  return __shfl_xor(v, kOff, kWave);
-}
+// the partner's half arrives by DPP (nnkey.h xor_lane_f64: all lanes active), without the LDS
+// unit's round trip
 template <int kOff>
 __device__ __forceinline__ double xchg_add(double a, double b, int lane) {
   const bool hi = (lane & kOff) != 0;
   const double keep = hi ? b : a, send = hi ? a : b;
-  return keep + xor_lane64<kOff>(send);
+  return keep + xor_lane_f64(send, kOff);
 }
 
 __device__ __forceinline__ double wave_transpose_sum32(const double (&v)[32], int lane) {
@@ -300,7 +260,7 @@ __device__ __forceinline__ double wave_transpose_sum32(const double (&v)[32], in
 #pragma unroll
   for (int j = 0; j < 2; ++j) w2[j] = xchg_add<4>(w4[j], w4[j + 2], lane);
   const double w1 = xchg_add<2>(w2[0], w2[1], lane);
-  return w1 + xor_lane64<1>(w1);  // slot lane >> 1
+  return w1 + xor_lane_f64(w1, 1);  // slot lane >> 1
 }
 
 // One source's contribution to the 30 term slots (layout below), in a fixed operation order:
@@ -373,20 +333,14 @@ struct TermsArgs {
 //      M3D_EST_POINT_TO_POINT → slots 0..2 Σp_c, 3..5 Σq_c, 6..14 Σ p_c q_cᵀ (row-major)
 // both: 28 count, 29 Σd²  (c = source centre: identical on every shard)
 // kWT: write the block partial through to memory (sc1 store) for the fused last-block reduce.
-// kP sources per thread, in two load rounds so that a thread's chains overlap: (1) every
-// source's key / runner-up / fp64 point (or claim / dmin), (2) after the fp64 decision, every
-// winner's fp64 target (and normal); the rare ambiguous queries are resolved by the whole wave in
-// between (nnkey.h resolve_wave, one ballot when there are none).
+// One source per thread, in two load rounds: (1) its key / runner-up / fp64 point (or claim /
+// dmin), (2) after the fp64 decision, the winner's fp64 target (and normal); the rare ambiguous
+// queries are resolved by the whole wave in between (nnkey.h resolve_wave, one ballot when there
+// are none).
 #if M3D_TAIL_CLOCK  // diagnostic builds only (tools/tail_clock.py): per-wave start / end of the
                     // terms pass, the last block's ticket, reduce and solve steps (100 MHz), and
                     // per wave the number of ambiguous queries it resolved
 __device__ unsigned long long g_tail_clock[3 * 4096 + 24];  // + 16 finer stamps at 3·4096 + 8
-#endif
-#ifndef M3D_WALK64
-#define M3D_WALK64 1  // build_grid_pts64 (0: resolve_wave gathers fp64 points after an fp32 screen)
-#endif
-#ifndef M3D_AMB_SKIP
-#define M3D_AMB_SKIP 0  // timing only (wrong winners on ambiguous queries): their cost
 #endif
 // kEst: the estimator as a template parameter (one path compiled per kernel: a runtime branch
 // between the two accumulation forms kept two accumulators in scratch memory)
@@ -404,7 +358,7 @@ __device__ unsigned long long g_terms_clock[4096 * 8];
   do {             \
   } while (0)
 #endif
-template <bool kWT, int kP, int kEst>
+template <bool kWT, int kEst>
 __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* __restrict__ s,
                                             double* __restrict__ partials) {
   __shared__ double red[kTermSlots][kTermsBlock / kWave];
@@ -415,6 +369,11 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
   double acc[30];
 #pragma unroll
   for (int k = 0; k < 30; ++k) acc[k] = 0.0;
+  // One source per thread, still written as kP = 1 rounds of one-element arrays (the form of the
+  // rounds-5/6 "sources per thread" experiments): with scalars and no `u` loops the compiler emits a
+  // different instruction stream for the four terms kernels (docs/EXPERIMENTS.md §R9), so that
+  // rewrite waits for a change that re-times them anyway.
+  constexpr int kP = 1;
   int64_t ii[kP];
   bool valid[kP];
   double vs[kP][3];
@@ -462,13 +421,12 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
       // nnkey.h winner_fp64, split: ambiguous queries resolved here by the wave, the others'
       // candidate (k1's target) re-evaluated in fp64 after the batched target loads below
       X[u] = valid[u] && k1[u] != (uint64_t)kKeyNone ? search_bound(key_d2(k1[u]), s->band_e, s->r2_hi) : -1.0f;
-      amb[u] = !M3D_AMB_SKIP && X[u] >= 0.0f && n2[u] <= X[u];
+      amb[u] = X[u] >= 0.0f && n2[u] <= X[u];
 #if M3D_TAIL_CLOCK
       {
         const int64_t gw = (int64_t)blockIdx.x * (kTermsBlock / kWave) + threadIdx.x / kWave;
         const int na = __popcll(__ballot(amb[u]));
-        if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096)
-          g_tail_clock[2 * 4096 + 8 + gw] = (u == 0 ? 0ull : g_tail_clock[2 * 4096 + 8 + gw]) + na;
+        if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096) g_tail_clock[2 * 4096 + 8 + gw] = na;
       }
 #endif
       qx[u] = qy[u] = qz[u] = 0.0f;
@@ -476,8 +434,8 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
       bj[u] = -1;
       bd[u] = 0.0;
     }
-    // every source round's ambiguous queries in one walk, two at a time (nnkey.h)
-    resolve_wave_kp<kP>(amb, a.g, a.tgt64, a.off, qx, qy, qz, X, vs, s->r2, bj, bd);
+    // the wave's ambiguous queries in one walk, two at a time (nnkey.h)
+    resolve_wave(amb[0], a.g, a.tgt64, a.off, qx[0], qy[0], qz[0], X[0], vs[0], s->r2, bj[0], bd[0]);
 #pragma unroll
     for (int u = 0; u < kP; ++u) {
       if (amb[u]) {
@@ -569,11 +527,11 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
 #endif
 }
 
-template <int kP, int kEst>
+template <int kEst>
 __global__ __launch_bounds__(kTermsBlock) void terms_kernel(TermsArgs a, const IcpState* __restrict__ s,
                                                             double* __restrict__ partials) {
   if (s->done) return;
-  terms_block<false, kP, kEst>(a, s, partials);
+  terms_block<false, kEst>(a, s, partials);
 }
 
 // Target-sharded evaluation, step 1 (m3d_icp_shard_nn): this shard's fp64 winner of every query
@@ -668,9 +626,6 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
 
 // sin / cos of |a| ≤ 0.5 by their Taylor series in z = a² (Horner, sine to a¹⁷, cosine to a¹⁸: the
 // first dropped terms are < 2e-20 relative), ≈ 2 ulp; an ICP update's angles are far inside this
-#ifndef M3D_SMALL_SINCOS
-#define M3D_SMALL_SINCOS 1
-#endif
 __device__ __forceinline__ void sincos_small(double a, double* sn, double* cs) {
   const double z = a * a;
   double ps = 1.0 / 355687428096000.0;  // 1/17!
@@ -699,7 +654,7 @@ __device__ __forceinline__ void vec6_to_matrix_wave(const double x[6], double T[
   double sn, cs;
   const double ang = lane == 0 ? x[0] : (lane == 1 ? x[1] : x[2]);
   // x is the same in every lane: the branch is uniform
-  if (M3D_SMALL_SINCOS && fmax(fabs(x[0]), fmax(fabs(x[1]), fabs(x[2]))) <= 0.5)
+  if (fmax(fabs(x[0]), fmax(fabs(x[1]), fabs(x[2]))) <= 0.5)
     sincos_small(ang, &sn, &cs);
   else
     sincos(ang, &sn, &cs);
@@ -758,16 +713,14 @@ __device__ void solve_state(const double* sums, IcpState* s, const SolveParams& 
   for (int k = 0; k < 12; ++k) rt[k] = in.rt[k];
   const double count = sm[28];
   const double r = sqrt(in.r2);  // for refresh_rt32_from; independent of everything below
-#ifndef M3D_SOLVE_SPEC
-#define M3D_SOLVE_SPEC 1
-#endif
   // point-to-plane: the unpivoted LDLT of JᵀJ does not depend on the convergence test, so it is
   // written first, in the same basic block as fitness / rmse, for the scheduler to interleave the
-  // chains (measured neutral against M3D_SOLVE_SPEC=0, docs/EXPERIMENTS.md §R6; the same bits);
+  // chains (measured neutral against filling A / b after the test, docs/EXPERIMENTS.md §R6; the
+  // same bits);
   // its result is used only if the loop goes on
   double A[36], b[6], x[6];
   bool spd_ok = false;
-  if (M3D_SOLVE_SPEC && kEst == M3D_EST_POINT_TO_PLANE) {
+  if (kEst == M3D_EST_POINT_TO_PLANE) {
     int k = 0;
 #pragma unroll
     for (int a = 0; a < 6; ++a)
@@ -801,9 +754,6 @@ __device__ void solve_state(const double* sums, IcpState* s, const SolveParams& 
     s->done = 1;
     return;
   }
-#if M3D_SOLVE_SKIP  // timing only: the solve's cost
-  return;
-#endif
   double upd[16];
   for (int k = 0; k < 16; ++k) upd[k] = (k % 5 == 0) ? 1.0 : 0.0;
   // the search transform of the evaluation just reduced: seed_key's bound for the next one
@@ -814,23 +764,9 @@ __device__ void solve_state(const double* sums, IcpState* s, const SolveParams& 
   M3D_TCLK(11);
   if (count > 0.0) {
     if (kEst == M3D_EST_POINT_TO_PLANE) {
-      if (!M3D_SOLVE_SPEC) {
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-          for (int c = a; c < 6; ++c) {
-            A[a * 6 + c] = sm[k];
-            A[c * 6 + a] = sm[k];
-            ++k;
-          }
-        for (int a = 0; a < 6; ++a) b[a] = -sm[21 + a];
-      }
       M3D_TCLK(3);
-#ifndef M3D_SOLVE_SPD
-#define M3D_SOLVE_SPD 1
-#endif
       // a full-rank JᵀJ unpivoted (no scalar-unit row swaps: 1.6 µs of the tail); a
       // (near-)singular one through Eigen's pivot order, which decides its zero components
-      if (!M3D_SOLVE_SPEC) spd_ok = M3D_SOLVE_SPD && ldlt6_solve_spd(A, b, x);
       if (!spd_ok) ldlt6_solve(A, b, x);
       M3D_TCLK(4);
       vec6_to_matrix_wave(x, upd);
@@ -935,7 +871,7 @@ __global__ __launch_bounds__(kTermSlots) void reduce_groups_kernel(double* __res
 // write-through (sc1), drains it (vmcnt(0)) and one lane adds to the agent-scope ticket; the
 // block whose add returned nblocks − 1 reads every partial with sc1 loads.  No L2 write-back or
 // invalidate fences are needed.
-template <int kP, int kEst>
+template <int kEst>
 __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
     TermsArgs a, IcpState* s, double* partials, int64_t nblocks, double* __restrict__ sums,
     SolveParams sp, int do_solve) {
@@ -945,7 +881,7 @@ __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
 #if M3D_TAIL_CLOCK
   const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  terms_block<true, kP, kEst>(a, s, partials);
+  terms_block<true, kEst>(a, s, partials);
 #if M3D_TAIL_CLOCK
   {
     const unsigned long long clk1 = __builtin_amdgcn_s_memrealtime();
@@ -1155,6 +1091,28 @@ static FrameParams frame_of(const m3d_icp* s) {
   return f;
 }
 
+static SolveParams solve_params(const m3d_icp* s) {
+  SolveParams sp;
+  sp.rel_fit = s->params.relative_fitness;
+  sp.rel_rmse = s->params.relative_rmse;
+  sp.max_iter = s->params.max_iteration;
+  sp.est = s->params.estimation;
+  sp.ns = s->ns_total > 0 ? s->ns_total : s->src->n;
+  for (int k = 0; k < 3; ++k) sp.c[k] = s->src->center[k];
+  sp.f = frame_of(s);
+  return sp;
+}
+
+// f(std::integral_constant<int, E>) for the estimator E = est: a launcher writes the launch of a
+// kEst kernel once
+template <typename F>
+static void with_est(int est, F f) {
+  if (est == M3D_EST_POINT_TO_PLANE)
+    f(std::integral_constant<int, M3D_EST_POINT_TO_PLANE>{});
+  else
+    f(std::integral_constant<int, M3D_EST_POINT_TO_POINT>{});
+}
+
 // the loop's fp64 points start as the source itself (the init, if applied, is dT)
 static hipError_t reset_points(const m3d_icp* s, hipStream_t st) {
   if (s->src->n == 0) return hipSuccess;
@@ -1269,7 +1227,7 @@ __global__ __launch_bounds__(256) void pack_pts64_kernel(const float4* __restric
 }
 
 hipError_t build_grid_pts64(const m3d_cloud* c, Grid* g, hipStream_t st) {
-  if (g->pts64 != nullptr || g->n_pts == 0 || M3D_WALK64 == 0) return hipSuccess;
+  if (g->pts64 != nullptr || g->n_pts == 0) return hipSuccess;
   double4* p = nullptr;
   hipError_t e = block_alloc(reinterpret_cast<void**>(&p), sizeof(double4) * g->n_pts, st);
   if (e != hipSuccess) return e;
@@ -1314,23 +1272,29 @@ hipError_t launch_icp_terms_mode(const m3d_icp* s, int64_t off, const int32_t* c
   if (ns == 0) return hipMemsetAsync(s->partials, 0, sizeof(double) * kTermSlots, st);
   const TermsArgs ta = terms_args(s, off, claim, dmin, false);
   const unsigned nb = (unsigned)s->nblocks;
-  if (ta.est == M3D_EST_POINT_TO_PLANE)
-    terms_kernel<kTermsPtsDefault, M3D_EST_POINT_TO_PLANE><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials);
-  else
-    terms_kernel<kTermsPtsDefault, M3D_EST_POINT_TO_POINT><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials);
+  with_est(ta.est, [&](auto e) {
+    terms_kernel<decltype(e)::value><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials);
+  });
   return hipGetLastError();
+}
+
+// reduce_groups_kernel; do_solve = 0: the sums only (the estimator matters to the solve alone: one
+// instance serves both)
+static void launch_reduce_groups(const m3d_icp* s, double* sums, int do_solve, hipStream_t st) {
+  const SolveParams sp = do_solve ? solve_params(s) : SolveParams{};
+  with_est(do_solve ? s->params.estimation : M3D_EST_POINT_TO_PLANE, [&](auto e) {
+    reduce_groups_kernel<decltype(e)::value><<<kReduceGroups, kTermSlots, 0, st>>>(
+        s->partials, s->nblocks, sums, s->state, sp, do_solve);
+  });
 }
 
 hipError_t launch_icp_reduce(const m3d_icp* s, double* sums, hipStream_t st) {
   if (s->nblocks > 256)  // group g's first row is block g's: rows 0..31 exist
-    reduce_groups_kernel<M3D_EST_POINT_TO_PLANE><<<kReduceGroups, kTermSlots, 0, st>>>(
-        s->partials, s->nblocks, sums, s->state, SolveParams{}, 0);
+    launch_reduce_groups(s, sums, 0, st);
   else
     reduce_kernel<<<1, kReduceGroups * kTermSlots, 0, st>>>(s->partials, s->nblocks, sums, s->state);
   return hipGetLastError();
 }
-
-static SolveParams solve_params(const m3d_icp* s);
 
 // the single-device separate tail after the terms pass: reduce + solve (one launch past 256
 // partials, reduce_groups_kernel's last block solving; two below)
@@ -1339,25 +1303,8 @@ hipError_t launch_icp_reduce_solve(const m3d_icp* s, hipStream_t st) {
     hipError_t e = launch_icp_reduce(s, s->sums, st);
     return e == hipSuccess ? launch_icp_solve(s, s->sums, st) : e;
   }
-  if (s->params.estimation == M3D_EST_POINT_TO_PLANE)
-    reduce_groups_kernel<M3D_EST_POINT_TO_PLANE><<<kReduceGroups, kTermSlots, 0, st>>>(
-        s->partials, s->nblocks, s->sums, s->state, solve_params(s), 1);
-  else
-    reduce_groups_kernel<M3D_EST_POINT_TO_POINT><<<kReduceGroups, kTermSlots, 0, st>>>(
-        s->partials, s->nblocks, s->sums, s->state, solve_params(s), 1);
+  launch_reduce_groups(s, s->sums, 1, st);
   return hipGetLastError();
-}
-
-static SolveParams solve_params(const m3d_icp* s) {
-  SolveParams sp;
-  sp.rel_fit = s->params.relative_fitness;
-  sp.rel_rmse = s->params.relative_rmse;
-  sp.max_iter = s->params.max_iteration;
-  sp.est = s->params.estimation;
-  sp.ns = s->ns_total > 0 ? s->ns_total : s->src->n;
-  for (int k = 0; k < 3; ++k) sp.c[k] = s->src->center[k];
-  sp.f = frame_of(s);
-  return sp;
 }
 
 // sharded tail: terms (shard offset off; claim/dmin: the target-shard exchange results, or null
@@ -1366,12 +1313,10 @@ static void launch_terms_solve(const TermsArgs& ta, const m3d_icp* s, double* su
                                hipStream_t st) {
   const unsigned nb = (unsigned)s->nblocks;
   const SolveParams sp = solve_params(s);
-  if (ta.est == M3D_EST_POINT_TO_PLANE)
-    terms_solve_kernel<kTermsPtsDefault, M3D_EST_POINT_TO_PLANE><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks,
-                                                                             sums, sp, do_solve);
-  else
-    terms_solve_kernel<kTermsPtsDefault, M3D_EST_POINT_TO_POINT><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks,
-                                                                             sums, sp, do_solve);
+  with_est(ta.est, [&](auto e) {
+    terms_solve_kernel<decltype(e)::value><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks, sums, sp,
+                                                                       do_solve);
+  });
 }
 
 hipError_t launch_icp_terms_reduce(const m3d_icp* s, int64_t off, const int32_t* claim,
@@ -1387,10 +1332,8 @@ hipError_t launch_icp_terms_reduce(const m3d_icp* s, int64_t off, const int32_t*
 }
 
 hipError_t launch_icp_solve(const m3d_icp* s, const double* sums, hipStream_t st) {
-  if (s->params.estimation == M3D_EST_POINT_TO_PLANE)
-    solve_kernel<M3D_EST_POINT_TO_PLANE><<<1, 64, 0, st>>>(sums, s->state, solve_params(s));
-  else
-    solve_kernel<M3D_EST_POINT_TO_POINT><<<1, 64, 0, st>>>(sums, s->state, solve_params(s));
+  const SolveParams sp = solve_params(s);
+  with_est(sp.est, [&](auto e) { solve_kernel<decltype(e)::value><<<1, 64, 0, st>>>(sums, s->state, sp); });
   return hipGetLastError();
 }
 
@@ -1455,10 +1398,7 @@ hipError_t launch_keys_to_idx(const int64_t* keys, int64_t n, int32_t* idx, hipS
   return hipGetLastError();
 }
 
-int64_t terms_blocks(int64_t ns) {
-  const int64_t per = (int64_t)kTermsBlock * terms_pts();
-  return ns > 0 ? (ns + per - 1) / per : 1;
-}
+int64_t terms_blocks(int64_t ns) { return ns > 0 ? (ns + kTermsBlock - 1) / kTermsBlock : 1; }
 
 }  // namespace m3d
 

@@ -135,9 +135,6 @@ __device__ __forceinline__ bool grid_box_miss(const GridDev& g, float qx, float 
          grid_miss(qz, R, g.o[2], g.inv_h, g.n[2]);
 }
 
-#ifndef M3D_SCAN_FLATLOAD
-#define M3D_SCAN_FLATLOAD 1
-#endif
 // The start / end offsets of rows r0 .. r0 + kR − 1 of a query's box (rows past `rows`: a = b = 0).
 // Every load is unconditional (a row past the box reads row r0's starts, dropped by the select):
 // loads under a per-lane branch compile to load → s_waitcnt vmcnt(0) → copy, one round trip each;
@@ -149,20 +146,11 @@ __device__ __forceinline__ void scan_row_starts(const GridDev& g, int r0, int ro
 #pragma unroll
   for (int k = 0; k < kR; ++k) {
     const int r = r0 + k;
-    if (M3D_SCAN_FLATLOAD) {
-      const int rr = r < rows ? r : r0;  // r0 < rows
-      const int64_t row = ((int64_t)(z0 + rr / ny) * g.n[1] + (y0 + rr % ny)) * g.n[0];
-      const int32_t sa = g.start[row + x0], sb = g.start[row + x1 + 1];
-      a[k] = r < rows ? sa : 0;
-      b[k] = r < rows ? sb : 0;
-    } else {
-      a[k] = b[k] = 0;
-      if (r < rows) {
-        const int64_t row = ((int64_t)(z0 + r / ny) * g.n[1] + (y0 + r % ny)) * g.n[0];
-        a[k] = g.start[row + x0];
-        b[k] = g.start[row + x1 + 1];
-      }
-    }
+    const int rr = r < rows ? r : r0;  // r0 < rows
+    const int64_t row = ((int64_t)(z0 + rr / ny) * g.n[1] + (y0 + rr % ny)) * g.n[0];
+    const int32_t sa = g.start[row + x0], sb = g.start[row + x1 + 1];
+    a[k] = r < rows ? sa : 0;
+    b[k] = r < rows ? sb : 0;
   }
 }
 
@@ -209,10 +197,7 @@ __device__ __forceinline__ void grid_scan(const GridDev& g, float qx, float qy, 
 #pragma unroll
         for (int m = 0; m < kB; ++m) {
           const int32_t j = a[k] + base + m * kL;
-          if (M3D_SCAN_FLATLOAD)
-            v[k][m] = g.pts[j < b[k] ? j : 0];
-          else if (j < b[k])
-            v[k][m] = g.pts[j];
+          v[k][m] = g.pts[j < b[k] ? j : 0];
         }
 #pragma unroll
       for (int k = 0; k < kR; ++k)
@@ -229,12 +214,6 @@ __device__ __forceinline__ void grid_scan(const GridDev& g, float qx, float qy, 
   if (ncand != nullptr) *ncand = cand;
 }
 
-#ifndef M3D_MERGE_DPP
-#define M3D_MERGE_DPP 1
-#endif
-#ifndef M3D_DPP_X4
-#define M3D_DPP_X4 1
-#endif
 // v from lane ^ 4 by two DPP moves: lane ^ 3 (quad permute [3,2,1,0]), then lane ^ 7 (the mirror
 // inside each 8 lanes, row_half_mirror): (i ^ 7) ^ 3 = i ^ 4
 __device__ __forceinline__ int xor4_dpp(int v) {
@@ -243,10 +222,10 @@ __device__ __forceinline__ int xor4_dpp(int v) {
 // v from lane ^ o: DPP for o = 1, 2 (quad permutes), 4 (two moves) and 8 (row_ror:8), with no
 // LDS round trip; a shuffle otherwise
 __device__ __forceinline__ int xor_lane(int v, int o, int width) {
-  if (M3D_MERGE_DPP && o == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);  // [1,0,3,2]
-  if (M3D_MERGE_DPP && o == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);  // [2,3,0,1]
-  if (M3D_MERGE_DPP && M3D_DPP_X4 && o == 4) return xor4_dpp(v);
-  if (M3D_MERGE_DPP && o == 8) return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);  // row_ror:8
+  if (o == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);  // [1,0,3,2]
+  if (o == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);  // [2,3,0,1]
+  if (o == 4) return xor4_dpp(v);
+  if (o == 8) return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);  // row_ror:8
   return __shfl_xor(v, o, width);
 }
 __device__ __forceinline__ double xor_lane_f64(double v, int o) {
@@ -277,69 +256,38 @@ __device__ __forceinline__ void grid_merge_lanes(uint64_t& k1, float& k1d, float
 // lexicographic (d64, global index) minimum among d64 < r2 (bj = −1: none).  With the grid's fp64
 // points (g.pts64, the ICP loops' target grid) every target of the box is evaluated from one
 // 32-B load — a superset holding the same minimum — instead of an fp32 screen and a gather.
-#ifndef M3D_WALK_PAIRS
-#define M3D_WALK_PAIRS 1
-#endif
-template <int kP, typename T>
-__device__ __forceinline__ T item_of(const T (&v)[kP], int u) {  // v[u] for a wave-uniform u
-  T r = v[0];
-#pragma unroll
-  for (int k = 1; k < kP; ++k)
-    if (u == k) r = v[k];
-  return r;
-}
-template <int kP>
-__device__ __forceinline__ double item_q(const double (&Q)[kP][3], int u, int c) {
-  double r = Q[0][c];
-#pragma unroll
-  for (int k = 1; k < kP; ++k)
-    if (u == k) r = Q[k][c];
-  return r;
-}
-// resolve_wave over kP queries per lane (the terms pass's sources per thread): the ambiguous
-// (u, lane) items of all kP rounds are walked two at a time, one per half-wave (M3D_WALK_PAIRS),
-// so a wave holding two walks them side by side instead of one after the other — its block waits
-// for it.  Any box lane split gives the same minimum.
-template <int kP>
-__device__ __forceinline__ void resolve_wave_kp(const bool (&amb)[kP], const GridDev& g,
-                                                const double* __restrict__ tgt64, int64_t off,
-                                                const float (&qx)[kP], const float (&qy)[kP],
-                                                const float (&qz)[kP], const float (&X)[kP],
-                                                const double (&Q)[kP][3], double r2,
-                                                int64_t (&bj)[kP], double (&bd)[kP]) {
+// The ambiguous lanes are walked two at a time, one per half-wave, so a wave holding two walks
+// them side by side instead of one after the other — its block waits for it.  Any box lane split
+// gives the same minimum.
+__device__ __forceinline__ void resolve_wave(bool amb, const GridDev& g,
+                                             const double* __restrict__ tgt64, int64_t off,
+                                             float qx, float qy, float qz, float X,
+                                             const double Q[3], double r2, int64_t& bj,
+                                             double& bd) {
   const int lane = threadIdx.x & (kWave - 1);
-  uint64_t m[kP];
-#pragma unroll
-  for (int u = 0; u < kP; ++u) m[u] = __ballot(amb[u]);
-  auto next = [&](int& u, int& L) {  // the next (u, lane) item, u = −1: none
-    u = -1;
-    L = 0;
-#pragma unroll
-    for (int k = 0; k < kP; ++k)
-      if (u < 0 && m[k] != 0) {
-        u = k;
-        L = __builtin_ctzll(m[k]);
-        m[k] &= m[k] - 1;
-      }
+  uint64_t m = __ballot(amb);
+  auto next = [&](int& L) {  // the next ambiguous lane into L; false: none left
+    if (m == 0) return false;
+    L = __builtin_ctzll(m);
+    m &= m - 1;
+    return true;
   };
   for (;;) {
-    int uA, LA, uB = -1, LB = 0;
-    next(uA, LA);
-    if (uA < 0) break;
-    if (M3D_WALK_PAIRS) next(uB, LB);
-    const bool two = uB >= 0;
+    int LA = 0, LB = 0;
+    if (!next(LA)) break;
+    const bool two = next(LB);
     const int W = two ? kWave / 2 : kWave;  // lanes per query (wave-uniform)
     const int sl = lane & (W - 1);           // this lane's place among them
     const bool hb = two && lane >= kWave / 2;
-    float lx = __shfl(item_of(qx, uA), LA), ly = __shfl(item_of(qy, uA), LA);
-    float lz = __shfl(item_of(qz, uA), LA), lX = __shfl(item_of(X, uA), LA);
-    double Q0 = __shfl(item_q(Q, uA, 0), LA), Q1 = __shfl(item_q(Q, uA, 1), LA);
-    double Q2 = __shfl(item_q(Q, uA, 2), LA);
+    float lx = __shfl(qx, LA), ly = __shfl(qy, LA);
+    float lz = __shfl(qz, LA), lX = __shfl(X, LA);
+    double Q0 = __shfl(Q[0], LA), Q1 = __shfl(Q[1], LA);
+    double Q2 = __shfl(Q[2], LA);
     if (two) {
-      const float bx = __shfl(item_of(qx, uB), LB), by = __shfl(item_of(qy, uB), LB);
-      const float bz = __shfl(item_of(qz, uB), LB), bX = __shfl(item_of(X, uB), LB);
-      const double b0 = __shfl(item_q(Q, uB, 0), LB), b1 = __shfl(item_q(Q, uB, 1), LB);
-      const double b2 = __shfl(item_q(Q, uB, 2), LB);
+      const float bx = __shfl(qx, LB), by = __shfl(qy, LB);
+      const float bz = __shfl(qz, LB), bX = __shfl(X, LB);
+      const double b0 = __shfl(Q[0], LB), b1 = __shfl(Q[1], LB);
+      const double b2 = __shfl(Q[2], LB);
       if (hb) {
         lx = bx;
         ly = by;
@@ -413,33 +361,15 @@ __device__ __forceinline__ void resolve_wave_kp(const bool (&amb)[kP], const Gri
     const int64_t jA = __shfl(jl, 0);
     const double dB = __shfl(dl, kWave / 2);
     const int64_t jB = __shfl(jl, kWave / 2);
-#pragma unroll
-    for (int k = 0; k < kP; ++k) {
-      if (uA == k && lane == LA) {
-        bj[k] = jA == INT64_MAX ? -1 : jA;
-        bd[k] = dA;
-      }
-      if (two && uB == k && lane == LB) {
-        bj[k] = jB == INT64_MAX ? -1 : jB;
-        bd[k] = dB;
-      }
+    if (lane == LA) {
+      bj = jA == INT64_MAX ? -1 : jA;
+      bd = dA;
+    }
+    if (two && lane == LB) {
+      bj = jB == INT64_MAX ? -1 : jB;
+      bd = dB;
     }
   }
-}
-
-__device__ __forceinline__ void resolve_wave(bool amb, const GridDev& g,
-                                             const double* __restrict__ tgt64, int64_t off,
-                                             float qx, float qy, float qz, float X,
-                                             const double Q[3], double r2, int64_t& bj,
-                                             double& bd) {
-  const bool a1[1] = {amb};
-  const float x1[1] = {qx}, y1[1] = {qy}, z1[1] = {qz}, X1[1] = {X};
-  const double Q1[1][3] = {{Q[0], Q[1], Q[2]}};
-  int64_t b1[1] = {bj};
-  double d1[1] = {bd};
-  resolve_wave_kp<1>(a1, g, tgt64, off, x1, y1, z1, X1, Q1, r2, b1, d1);
-  bj = b1[0];
-  bd = d1[0];
 }
 
 // The fp64 winner of query i from its scan results (k1, near2) — see the header.  Q = its fp64

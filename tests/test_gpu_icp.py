@@ -56,7 +56,7 @@ def _grid_cases():
     # loop defers the queries near it to grid_nn_heavy_kernel)
     fan = np.vstack([sph, sph[7] + rng.normal(scale=0.002, size=(3000, 3))])
     # a dense volume (≈ 100 points per r-cell: the loop's cells are r/4, so an unseeded query's
-    # box is 9 cells wide and the scan takes its half-cell first pass, grid.hip M3D_SCAN_PHASE1)
+    # box is 9 cells wide and the scan takes its half-cell first pass, grid.hip grid_nn_batched_kernel)
     cube = rng.uniform(-0.5, 0.5, (60000, 3))
     return {
         "dense_volume": (cube[::3] + 1e-3, cube, 0.12),

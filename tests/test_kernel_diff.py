@@ -41,3 +41,21 @@ def test_missing_unless_removed():
     base = ASM.format(fn=3, lab=7, vgpr=4)
     assert kernel_diff.compare(base, [""]) == (["missing  _ZN3m3d3fooEPf"], 1)
     assert kernel_diff.compare(base, [""], removed=["foo"]) == (["removed  _ZN3m3d3fooEPf"], 0)
+
+
+_BAR = "_ZN3m3d3barILi1EEEvPf"
+
+
+def test_renamed_with_identical_stream_is_same():
+    base = ASM.format(fn=3, lab=7, vgpr=4)
+    new = ASM.format(fn=0, lab=2, vgpr=4).replace("_ZN3m3d3fooEPf", _BAR)
+    assert kernel_diff.compare(base, [new], renamed=[("_ZN3m3d3fooEPf", _BAR)]) == ([f"same  {_BAR}"], 0)
+    # without the option the kernel escapes the comparison: one missing, one new
+    out, rc = kernel_diff.compare(base, [new])
+    assert sorted(out) == ["missing  _ZN3m3d3fooEPf", f"new  {_BAR}"] and rc == 1
+
+
+def test_renamed_to_an_absent_symbol_fails():
+    base = ASM.format(fn=3, lab=7, vgpr=4)
+    out, rc = kernel_diff.compare(base, [base], renamed=[("_ZN3m3d3fooEPf", _BAR)])
+    assert rc != 0 and out[0].startswith(f"missing  {_BAR}")

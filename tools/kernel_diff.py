@@ -10,9 +10,12 @@ have moved to another translation unit) one line:
 Comments are stripped and local labels (.LBB<n>_<m>, .Ltmp<n>, ...) renumbered in order of first
 appearance inside the kernel, so moving a kernel inside or between files does not count.  Exit
 status 1 on DESCRIPTOR-DIFF or missing, unless the symbol was given with --removed NAME (the
-mangled symbol or the plain function name).  Pure text comparison: no GPU, no table of mnemonics.
+mangled symbol or the plain function name).  --renamed OLD=NEW (mangled symbols; a changed template
+parameter list changes the name) compares the baseline's OLD against the new files' NEW as one
+kernel, listed under NEW; both must exist, otherwise `missing` and exit status 1.  Pure text
+comparison: no GPU, no table of mnemonics.
 
-Usage: tools/kernel_diff.py BASE.s NEW.s [NEW2.s ...] [--removed NAME ...]"""
+Usage: tools/kernel_diff.py BASE.s NEW.s [NEW2.s ...] [--removed NAME ...] [--renamed OLD=NEW ...]"""
 import argparse
 import re
 import sys
@@ -80,12 +83,21 @@ def delta(a, b):
         ", ".join(f"{m} {v:+d}" for m, v in d.items()) or "same counts, other order or operands")
 
 
-def compare(base_text, new_texts, removed=()):
-    """(report lines, exit status)"""
+def compare(base_text, new_texts, removed=(), renamed=()):
+    """(report lines, exit status); renamed = (OLD, NEW) symbol pairs"""
     base, new = parse(base_text), {}
     for t in new_texts:
         new.update(parse(t))
     out, bad = [], 0
+    for old, sym in renamed:
+        if old in base and sym in new and sym not in base:
+            stream, desc = base.pop(old)
+            base[sym] = ([ln.replace(old, sym) for ln in stream], desc)
+        else:
+            out.append(f"missing  {sym}\n    --renamed {old}={sym}: " +
+                       ("no such baseline symbol" if old not in base else
+                        "no such new symbol" if sym not in new else "the baseline has both"))
+            bad = 1
     for sym in sorted(set(base) | set(new)):
         gone_ok = sym in removed or any(n in removed for n in source_names(sym))
         if sym not in new:
@@ -112,9 +124,12 @@ def main(argv=None):
     ap.add_argument("base")
     ap.add_argument("new", nargs="+")
     ap.add_argument("--removed", action="append", default=[], metavar="NAME")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args(argv)
+    if any(r.count("=") != 1 for r in a.renamed):
+        ap.error("--renamed takes OLD=NEW")
     read = lambda p: open(p, encoding="utf-8", errors="replace").read()
-    out, rc = compare(read(a.base), [read(p) for p in a.new], a.removed)
+    out, rc = compare(read(a.base), [read(p) for p in a.new], a.removed, [r.split("=") for r in a.renamed])
     print("\n".join(out))
     return rc
 
