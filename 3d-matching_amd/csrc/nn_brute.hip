@@ -240,6 +240,17 @@ __device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, cons
   }
 }
 
+// 16 target rows (x, y, z, index bits) pushed into a query's scan state: direct d²
+__device__ __forceinline__ void nn_push_rows(const float4 (&t)[16], int64_t off, float qx, float qy, float qz,
+                                             float r2_hi, uint64_t& k1, float& k1d, float& n2) {
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const float d2 = d2f(qx, qy, qz, t[reg].x, t[reg].y, t[reg].z);
+    const uint64_t kc = make_key(d2, (uint32_t)(off + __float_as_int(t[reg].w)));
+    if (d2 <= r2_hi) near_push(k1, k1d, n2, kc, d2);
+  }
+}
+
 // Exact fp32 pass of nn_mfma_kernel over one flagged sub-tile (32 targets from `rows`), of which
 // this lane takes its 16 MFMA rows: direct d² pushed into the lane's scan state.  Pads: far
 // coordinates, d² ~ 1e36 > r2_hi.
@@ -249,12 +260,7 @@ __device__ __forceinline__ void nn_exact_rows(const float4* __restrict__ rows, i
   float4 t[16];  // all 16 loads in flight before the first use (one memory latency per sub-tile)
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) t[reg] = rows[(reg & 3) + 8 * (reg >> 2) + 4 * h];
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const float d2 = d2f(qx, qy, qz, t[reg].x, t[reg].y, t[reg].z);
-    const uint64_t kc = make_key(d2, (uint32_t)(off + __float_as_int(t[reg].w)));
-    if (d2 <= r2_hi) near_push(k1, k1d, n2, kc, d2);
-  }
+  nn_push_rows(t, off, qx, qy, qz, r2_hi, k1, k1d, n2);
 }
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
@@ -311,8 +317,36 @@ __device__ __forceinline__ float wave_minmax(float v) {
 // and can never be a neighbour, swept or not.  (Should G itself come out NaN, e.g. from
 // inf − inf of an empty box, `G > Xmax` is false and the set is kept.)  M3D_NN_CULL=0 (A/B
 // build) sweeps every pair as before.
+// Second level, the per-query reach test (point_out_of_reach, M3D_NN_REACH=0 builds without it):
+// the same lemma with the query box shrunk to one query's point q (qlo = qhi = q) and Xmax
+// replaced by that query's own current bound X_q — every target t of the box has d2f(q, t) ≥
+// G_q = d2f(max(0, q − thi, tlo − q), 0), so G_q > X_q puts the whole box out of this query's
+// reach, now and for the rest of the sweep (X_q only tightens).  A wave keeps a half tile that
+// passed its box test only if one of its active queries reaches it, a block keeps a tile only if
+// one of its waves keeps one of its halves.  The queries run in Morton order: a wave or block that
+// straddles a Morton jump has a box far larger than the space its points occupy, and the box test
+// alone keeps everything in between.  Same strictness (G_q = X_q is kept), a NaN query or G_q
+// keeps the half, inactive queries never reach, and `force` groups are tested like any other
+// (the lemma is about d2f, not about the screen).
 #ifndef M3D_NN_CULL
 #define M3D_NN_CULL 1
+#endif
+#ifndef M3D_NN_REACH
+#define M3D_NN_REACH 1
+#endif
+// the deferred exact passes in batches through LDS (nn_mfma_kernel, after the sweep); 0 (A/B
+// builds): one sub-tile per global round trip, as before
+#ifndef M3D_NN_DEFER_BATCH
+#define M3D_NN_DEFER_BATCH 1
+#endif
+// diagnostic builds only (tools/nn_clock.py): per-block timeline and tile counts of the last
+// nn_mfma_kernel launch, s_memrealtime (100 MHz: one clock for every block, whichever XCD runs it)
+#ifndef M3D_NN_CLOCK
+#define M3D_NN_CLOCK 0
+#endif
+#if M3D_NN_CLOCK
+constexpr int kClkBlocks = 16384, kClkWords = 8;
+__device__ unsigned long long g_nn_clock[kClkWords * kClkBlocks];
 #endif
 struct QBox {
   float lo[3], hi[3], X;
@@ -322,6 +356,14 @@ __device__ __forceinline__ bool box_out_of_reach(const QBox& q, const float4& tl
   const float gy = fmaxf(0.0f, fmaxf(q.lo[1] - thi.y, tlo.y - q.hi[1]));
   const float gz = fmaxf(0.0f, fmaxf(q.lo[2] - thi.z, tlo.z - q.hi[2]));
   return d2f(gx, gy, gz, 0.0f, 0.0f, 0.0f) > q.X;
+}
+// the same test for one query point against a target box (lo, hi), X = the query's own bound
+__device__ __forceinline__ bool point_out_of_reach(float qx, float qy, float qz, float X, const float (&lo)[3],
+                                                   const float (&hi)[3]) {
+  const float gx = fmaxf(0.0f, fmaxf(qx - hi[0], lo[0] - qx));
+  const float gy = fmaxf(0.0f, fmaxf(qy - hi[1], lo[1] - qy));
+  const float gz = fmaxf(0.0f, fmaxf(qz - hi[2], lo[2] - qz));
+  return d2f(gx, gy, gz, 0.0f, 0.0f, 0.0f) > X;
 }
 
 // ------------------------------------------------------------------------------- nn_mfma_kernel
@@ -445,6 +487,23 @@ __device__ __forceinline__ QBox reduce_boxes(const QBox& lq, float4 (&qbox)[kMBl
 // (one round of box loads per 16 tiles).  mb: half tiles the block reaches — a tile survives if
 // any of its four bits is set; mw ⊆ mb: those this wave reaches.  Every wave computes mb from the
 // same data by the same instructions.
+// Per-query reach test (M3D_NN_REACH, point_out_of_reach): mw is refined to the half tiles some
+// active query of the wave reaches with its own current bound — the boxes are in the lanes that
+// loaded them, a scalar loop over the set bits of mw broadcasts each with v_readlane and every
+// lane tests its kMG queries — and mb becomes the OR of the eight waves' refined masks, through
+// one LDS word per wave, in the rounds where the block's box reaches a tile at all.  The barrier this
+// puts into such a round is legal: every wave reaches next() with the same (tc, mb) and takes the
+// box-level mb from the same box, so all of them run the same rounds and the same barriers.  Two slot sets by round parity: a
+// wave writes the set of round n + 2 only after the barrier of round n + 1, which every wave
+// passes after it has read the set of round n.  Every wave ORs the same eight words: mb stays
+// block-uniform.
+struct ReachArgs {
+  const QState (&q)[kMG];
+  const uint32_t& act;  // the lane's active groups
+  float be, r2_hi;
+  uint64_t (&slot)[2][kMBlock / 64];
+  int wave;
+};
 struct TileCursor {
   const float4* tbox;   // Grid::mfbox
   const float4* wbox;   // this wave's box, qbox[wave] (LDS)
@@ -452,13 +511,16 @@ struct TileCursor {
   int lane, ntile, ty;  // tiles in all, the set's stride (gridDim.y)
   int tc;               // first tile of the current round
   uint64_t mb, mw;
+  int par = 0;          // parity of the round (ReachArgs::slot)
 
-  __device__ __forceinline__ void cull_round() {
+  __device__ __forceinline__ void cull_round(const ReachArgs& ra) {
     const int tl = tc + (lane >> 2) * ty;
     bool kb = tl < ntile, kw = kb;
+    float4 tlo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), thi = tlo;
     if (M3D_NN_CULL && kb) {
       const int64_t hb = (int64_t)tl * kTH + (lane & 3);  // < nt_pad / kMTile
-      const float4 tlo = tbox[2 * hb], thi = tbox[2 * hb + 1];
+      tlo = tbox[2 * hb];
+      thi = tbox[2 * hb + 1];
       const float4 l0 = wbox[0], u0 = wbox[1];
       const QBox wq{{l0.x, l0.y, l0.z}, {u0.x, u0.y, u0.z}, l0.w};
       kb = !box_out_of_reach(bx, tlo, thi);
@@ -466,9 +528,43 @@ struct TileCursor {
     }
     mb = __ballot(kb);
     mw = __ballot(kw);
+#if M3D_NN_CULL && M3D_NN_REACH
+    // a round the block's box reaches nothing of (mb from the block's box: block-uniform) needs no
+    // second level, no exchange and no barrier — with grid.y = 1 on a large target most rounds
+    if (mb == 0) return;
+    float X[kMG];
+#pragma unroll
+    for (int g = 0; g < kMG; ++g)
+      X[g] = (ra.act >> g) & 1u ? search_bound(key_d2(ra.q[g].k1), ra.be, ra.r2_hi) : -1.0f;
+    uint64_t keep = 0;
+    for (uint64_t m = mw; m != 0; m &= m - 1) {
+      const int b = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+      const auto rl = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), b)); };
+      const float lo[3] = {rl(tlo.x), rl(tlo.y), rl(tlo.z)}, hi[3] = {rl(thi.x), rl(thi.y), rl(thi.z)};
+      bool reach = false;
+#pragma unroll
+      for (int g = 0; g < kMG; ++g)
+        reach |= ((ra.act >> g) & 1u) &&
+                 !point_out_of_reach(ra.q[g].qx, ra.q[g].qy, ra.q[g].qz, X[g], lo, hi);
+      if (__any(reach)) keep |= 1ull << b;
+    }
+    mw = keep;
+    par ^= 1;
+    if (lane == 0) ra.slot[par][ra.wave] = mw;
+    __syncthreads();
+    const uint64_t w = ra.slot[par][lane & 7];
+    int wl = (int)(uint32_t)w, wh = (int)(uint32_t)(w >> 32);
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+      wl |= xor_lane(wl, o, kWave);
+      wh |= xor_lane(wh, o, kWave);
+    }
+    mb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(wh) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane(wl);
+#endif
   }
   // next surviving tile (ntile: none left) and this wave's half-tile mask of it
-  __device__ __forceinline__ void next(int& t, uint32_t& hmask) {
+  __device__ __forceinline__ void next(int& t, uint32_t& hmask, const ReachArgs& ra) {
     for (;;) {
       if (mb != 0) {
         const int k = __builtin_ctzll(mb) >> 2;
@@ -483,7 +579,7 @@ struct TileCursor {
         hmask = 0;
         return;
       }
-      cull_round();
+      cull_round(ra);
     }
   }
 };
@@ -596,6 +692,9 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
                                                           uint32_t* __restrict__ near2,
                                                           SeedArgs sa, int64_t q0) {
   if (s->done) return;
+#if M3D_NN_CLOCK
+  const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
+#endif
   // grid.y block y takes every gridDim.y-th target tile (strided: a query block's few candidate
   // tiles, adjacent in row order, spread over gridDim.y blocks instead of landing in one)
   if (!s->mfma_ok) {  // the same tiles by a plain scan, unculled
@@ -608,6 +707,17 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   __shared__ uint64_t dlist[kMBlock / 64][kDefer];  // deferred: flagged (group, sub-tile) bits
   __shared__ uint32_t dtile[kMBlock / 64][kDefer];  // their tile's first target
   __shared__ float4 qbox[kMBlock / 64][2];
+  __shared__ uint64_t rslot[2][kMBlock / 64];  // the waves' refined half masks of a cull round
+#if M3D_NN_CLOCK
+  __shared__ uint32_t clk_slow, clk_ticket;  // half tiles swept by the block's slowest wave
+  __shared__ unsigned long long clk_exit;
+  if (threadIdx.x == 0) {  // (visible after the boxes' barrier)
+    clk_slow = 0;
+    clk_ticket = 0;
+    clk_exit = 0;
+  }
+  uint32_t clk_tiles = 0, clk_halves = 0;
+#endif
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const float r2_hi = s->r2_hi, eps = s->screen_eps_m, S = s->mfma_scale, be = s->band_e;
@@ -646,18 +756,26 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 
   const QBox bx = reduce_boxes(lq, qbox, lane, wave);
   const int ntile = (int)(nt_pad / kTT);
+  const ReachArgs ra{q, act, be, r2_hi, rslot, wave};
   TileCursor cur{tbox, qbox[wave], bx, lane, ntile, (int)gridDim.y, (int)blockIdx.y, 0, 0};
-  cur.cull_round();
+  cur.cull_round(ra);
   int t0, t1;
   uint32_t h0, h1;  // the wave's half-tile masks of tiles t0, t1
-  cur.next(t0, h0);
+  cur.next(t0, h0, ra);
   if (t0 < ntile) stage_tile(t16[0], tgt16, nt_pad, t0, false);
   const uint64_t force64 = group_mask(force);
   __syncthreads();
+#if M3D_NN_CLOCK
+  const unsigned long long clk1 = __builtin_amdgcn_s_memrealtime();
+#endif
   int buf = 0;
   for (; t0 < ntile; t0 = t1, h0 = h1) {
     const int64_t j0 = (int64_t)t0 * kTT;
-    cur.next(t1, h1);
+#if M3D_NN_CLOCK
+    ++clk_tiles;
+    clk_halves += (uint32_t)__builtin_popcount(h0);
+#endif
+    cur.next(t1, h1, ra);
     // the next surviving tile while this one is swept
     if (t1 < ntile) stage_tile(t16[buf ^ 1], tgt16, nt_pad, t1, true);
     uint32_t rec[kMG];
@@ -683,7 +801,101 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     __syncthreads();
     buf ^= 1;
   }
-  // the deferred exact passes (rows from global memory: the tiles have left LDS)
+#if M3D_NN_CLOCK
+  const unsigned long long clk2 = __builtin_amdgcn_s_memrealtime();
+  if (lane == 0) atomicMax(&clk_slow, clk_halves);
+#endif
+  // The deferred exact passes.  The tiles have left LDS and the fp32 rows come from global memory:
+  // one sub-tile at a time that is one dependent round trip per flagged sub-tile, and the slowest
+  // wave's list is what a block spends most of its life on (tools/nn_clock.py: 11 of 25 µs at
+  // cfg1).  So the wave fetches its flagged sub-tiles kStash at a time — a lane loads one row of
+  // eight of them, all in flight together — into its own eighth of the operand buffers (free:
+  // the loop's last barrier is behind every wave) and runs the exact pass from there.  Per group
+  // the rows are pushed in the same order as before, each by the lane that would have pushed it;
+  // the lane pair merges once at the end instead of after every sub-tile, which gives the same
+  // state: (k1, near2) is a function of the set of keys pushed — the minimum and the smallest d²
+  // of any other; a key held by both lanes (the seed, an earlier merge) counts once (near_push).
+#if M3D_NN_DEFER_BATCH
+  if (dn > 0) {
+    constexpr int kStash = 16;  // sub-tiles per batch: 16 × 32 rows × 16 B = 8 KiB per wave
+    static_assert(kStash * kMG <= 32, "a batch's group flags in one word");
+    static_assert(sizeof(t16) >= sizeof(float4) * (kMBlock / 64) * kStash * 32, "a stash per wave");
+    float4* const stash = reinterpret_cast<float4*>(&t16[0][0][0]) + wave * (kStash * 32);
+    const auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    // cursor over the list's flagged (entry, sub-tile) pairs, wave-uniform
+    int e = 0;
+    uint64_t ent = dlist[wave][0];
+    ent = ((uint64_t)uni((uint32_t)(ent >> 32)) << 32) | uni((uint32_t)ent);
+    uint32_t base = uni(dtile[wave][0]);
+    const auto subs = [](uint64_t m) {
+      uint32_t u = 0;
+#pragma unroll
+      for (int g = 0; g < kMG; ++g) u |= (uint32_t)(m >> (g * kSub)) & (uint32_t)kGMask;
+      return u;
+    };
+    uint32_t U = subs(ent);
+    // next pair: its first row and the groups that flagged it (0: the list is exhausted)
+    const auto pop = [&](uint32_t& row0, uint32_t& gs) {
+      row0 = 0;
+      gs = 0;
+      while (U == 0) {
+        if (e + 1 >= dn) return;
+        ++e;
+        ent = dlist[wave][e];
+        ent = ((uint64_t)uni((uint32_t)(ent >> 32)) << 32) | uni((uint32_t)ent);
+        base = uni(dtile[wave][e]);
+        U = subs(ent);
+      }
+      const int sub = __builtin_ctz(U);
+      U &= U - 1;
+      row0 = base + (uint32_t)sub * 32u;
+#pragma unroll
+      for (int g = 0; g < kMG; ++g) gs |= (uint32_t)((ent >> (g * kSub + sub)) & 1u) << g;
+    };
+    uint64_t kb[kMG];
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) kb[g] = q[g].k1;
+    for (;;) {
+      uint32_t gsel = 0;  // kMG bits per stash slot
+      float4 ld[kStash / 2];
+#pragma unroll
+      for (int k = 0; k < kStash / 2; ++k) {  // slots 2k (lanes 0–31) and 2k + 1 (lanes 32–63)
+        uint32_t ra, ga, rb, gb;
+        pop(ra, ga);
+        pop(rb, gb);
+        gsel |= (ga | (gb << kMG)) << (2 * kMG * k);
+        ld[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (h == 0 ? ga != 0 : gb != 0) ld[k] = tgt32[(int64_t)(h == 0 ? ra : rb) + c];  // < nt_pad
+      }
+#pragma unroll
+      for (int k = 0; k < kStash / 2; ++k) stash[(2 * k + h) * 32 + c] = ld[k];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 1
+      for (int sl = 0; sl < kStash; ++sl) {
+        const uint32_t gs = (gsel >> (kMG * sl)) & ((1u << kMG) - 1u);
+        if (gs == 0) break;  // the slots fill in order
+        float4 t[16];
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) t[reg] = stash[sl * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h];
+#pragma unroll
+        for (int g = 0; g < kMG; ++g)
+          if ((gs >> g) & 1u) nn_push_rows(t, off, q[g].qx, q[g].qy, q[g].qz, r2_hi, q[g].k1, q[g].k1d, q[g].n2);
+      }
+      if (U == 0 && e + 1 >= dn) break;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();  // the next batch overwrites the stash
+    }
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) {
+      const uint64_t o1 = shfl_xor64(q[g].k1, 32);
+      const float on2 = __shfl_xor(q[g].n2, 32);
+      near_merge(q[g].k1, q[g].k1d, q[g].n2, o1, on2);
+      chg |= (uint32_t)(q[g].k1 != kb[g]) << g;
+    }
+  }
+#else
   for (int e = 0; e < dn; ++e) {
     const uint64_t ent = dlist[wave][e];
     const float4* tile = tgt32 + (int64_t)dtile[wave][e];
@@ -691,13 +903,51 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (int g = 0; g < kMG; ++g)
       chg |= (uint32_t)nn_exact_subtiles((ent >> (g * kSub)) & kGMask, tile, off, h, r2_hi, q[g]) << g;
   }
+#endif
+#if M3D_NN_CLOCK
+  const unsigned long long clk2b = __builtin_amdgcn_s_memrealtime();
+#endif
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
     if (h != 0 || q[g].qi < 0) continue;
+#if (M3D_NN_CULL && M3D_NN_REACH) || M3D_NN_DEFER_BATCH
+    // the query's position again from the block's coordinates (through an empty asm, or the
+    // compiler keeps the value of the setup): held across the sweep it is two registers per group,
+    // which the reach test's rounds and the batched deferred passes no longer leave — the kernel
+    // would spill
+    int cq = c;
+    asm volatile("" : "+v"(cq));
+    const int64_t qi = q0 + (int64_t)blockIdx.x * kMQueries + (wave * kMG + g) * 32 + cq;
+#else
+    const int64_t qi = q[g].qi;
+#endif
     const bool pk = publish_k1(sa, q[g].k1, (chg >> g) & 1u);
-    if (pk || q[g].n2 < kInf)
-      near_publish((unsigned long long*)&keys[q[g].qi], &near2[q[g].qi], q[g].k1, q[g].n2, pk);
+    if (pk || q[g].n2 < kInf) near_publish((unsigned long long*)&keys[qi], &near2[qi], q[g].k1, q[g].n2, pk);
   }
+#if M3D_NN_CLOCK
+  // the block's record, written by its last wave out (LDS ticket; a wave's LDS operations execute
+  // in order, so every earlier wave's maximum is in): entry, setup done, tile loop done (the
+  // writer's own stamps: the latter two follow block barriers), the last wave's exit, the tiles
+  // the block kept, the half tiles its slowest wave swept
+  {
+    const unsigned long long clk3 = __builtin_amdgcn_s_memrealtime();
+    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (lane == 0) {
+      atomicMax(&clk_exit, clk3);
+      if (atomicAdd(&clk_ticket, 1u) == kMBlock / 64 - 1 && blk < kClkBlocks) {
+        unsigned long long* rec = g_nn_clock + kClkWords * blk;
+        rec[0] = clk0;
+        rec[1] = clk1;
+        rec[2] = clk2;
+        rec[3] = atomicMax(&clk_exit, 0ull);
+        rec[4] = clk_tiles;
+        rec[5] = atomicMax(&clk_slow, 0u);
+        rec[6] = (unsigned long long)blockIdx.x | ((unsigned long long)blockIdx.y << 32);
+        rec[7] = clk2b;  // the deferred passes done (the writer's own: the last wave out)
+      }
+    }
+  }
+#endif
 }
 
 // grid.y of nn_mfma_kernel for bx query blocks and ntiles target tiles (block y takes every
@@ -707,10 +957,14 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 // blocks idles the rest of the chip: 196 × 11 blocks on 512 slots = 4.2 rounds ran as 5).  Culled
 // sweep: a block keeps only a few of its tiles, its setup (query load, seed gather, boxes,
 // survivor round) weighs as much as what is left of the sweep, and the blocks' lengths differ —
-// the fewest slices that fill the slots once, S = ⌈slots / grid.x⌉ (EXPERIMENTS §3.5: cfg1 59 µs
-// at S = 3 against 63–73 at 4–6 and 86 at 13; the 1M pair fastest at S = 1).  The rule rests on
-// those two shapes only.  With few query blocks it degenerates to one tile per block (grid.x = 1
-// gives S = ntiles, the clamp): every block then pays the setup for at most one tile.
+// the most slices whose blocks are all resident at once, S = ⌊slots / grid.x⌋, at least 1.  A
+// second, partial round of blocks starts when the first blocks end and ends the launch a whole
+// block later (tools/nn_clock.py: 588 blocks on 512 slots, the last 76 started at 16–22 µs of 54);
+// with the per-query reach test the tile lists are short and even enough that fewer, longer blocks
+// in one round win (EXPERIMENTS §R10: cfg1 51 µs at S = 2 against 54 at 3, 60 at 4–5, 65 at 1; the
+// 1M pair fastest at S = 1, which both ⌊⌋ and the earlier ⌈⌉ give).  The rule rests on those two
+// shapes only.  With few query blocks it degenerates to one tile per block (grid.x = 1 gives
+// S = ntiles, the clamp): every block then pays the setup for at most one tile.
 // Unknown slots: S0 blocks per query block, evened out to equal tile counts.
 static int64_t nn_grid_y(int64_t bx, int64_t ntiles, int64_t slots, bool cull) {
   const auto clamped = [&](int64_t S) { return std::min(std::max<int64_t>(S, 1), ntiles); };
@@ -719,7 +973,7 @@ static int64_t nn_grid_y(int64_t bx, int64_t ntiles, int64_t slots, bool cull) {
     const int64_t per = (ntiles + s0 - 1) / s0;  // tiles per block
     return (ntiles + per - 1) / per;
   }
-  if (cull) return clamped((slots + bx - 1) / bx);
+  if (cull) return clamped(slots / bx);
   int64_t best = s0;
   double best_eff = 0.0;
   for (int64_t S = s0; S <= std::min(2 * s0, ntiles); ++S) {
@@ -733,6 +987,13 @@ static int64_t nn_grid_y(int64_t bx, int64_t ntiles, int64_t slots, bool cull) {
   return best;
 }
 
+#if M3D_NN_CLOCK
+}  // namespace m3d
+extern "C" int m3d_debug_nn_clock(unsigned long long* out, int n) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(m3d::g_nn_clock), sizeof(unsigned long long) * (size_t)n) == hipSuccess ? 0 : -1;
+}
+namespace m3d {
+#endif
 static bool icp_nn_uses_mfma(const m3d_icp* s) {
   return s->tgrid != nullptr && s->tgrid->mf16 != nullptr;
 }
