@@ -24,6 +24,12 @@ hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st);
 hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st);
 hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStream_t st);
 int64_t terms_blocks(int64_t ns);
+// eval.hip: the evaluation pass after a loop's NN scan; out[0 .. 16) receives the sums
+// (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz) and, in words 14 / 15, the deferral count / fault
+size_t eval_scratch_bytes(int64_t ns);
+hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
+                       double* out, hipStream_t st);
+hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st);
 }  // namespace m3d
 
 using namespace m3d;
@@ -1909,6 +1915,79 @@ int m3d_nn1(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const doub
   if (!rc && e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
   m3d_icp_destroy(s);
   return rc;
+}
+
+namespace {
+// GᵀG of the rows G₁ = (0, z, −y, 1, 0, 0), G₂ = (−z, 0, x, 0, 1, 0), G₃ = (y, −x, 0, 0, 0, 1) over
+// the matched target points, from eval.hip's sums m = (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz)
+void eval_information(const double* m, double* G) {
+  const double n = m[0], x = m[2], y = m[3], z = m[4], xx = m[5], yy = m[6], zz = m[7], xy = m[8],
+               xz = m[9], yz = m[10];
+  const double U[6][6] = {{yy + zz, 0.0 - xy, 0.0 - xz, 0.0, 0.0 - z, y},
+                          {0.0, xx + zz, 0.0 - yz, z, 0.0, 0.0 - x},
+                          {0.0, 0.0, xx + yy, 0.0 - y, x, 0.0},
+                          {0.0, 0.0, 0.0, n, 0.0, 0.0},
+                          {0.0, 0.0, 0.0, 0.0, n, 0.0},
+                          {0.0, 0.0, 0.0, 0.0, 0.0, n}};
+  for (int a = 0; a < 6; ++a)
+    for (int b = 0; b < 6; ++b) G[6 * a + b] = a <= b ? U[a][b] : U[b][a];
+}
+}  // namespace
+
+int m3d_evaluate_registration(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt,
+                              const double* T_host, double max_dist, int32_t nn_method, int32_t flags,
+                              m3d_eval_result* out, int32_t* corr_idx, double* d2, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  CHECK_ARG(ctx, src && tgt && out, "invalid arguments");
+  CHECK_ARG(ctx, max_dist > 0.0, "max_dist must be > 0");
+  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
+  memset(out, 0, sizeof(*out));
+  hipStream_t st = S(stream);
+  const int64_t ns = src->n, nt = tgt->n;
+  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched
+    hipSetDevice(ctx->device);
+    hipError_t e = launch_eval_fill(ns, corr_idx, d2, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    return M3D_OK;
+  }
+  m3d_icp_params p{1e-6, 1e-6, 0, M3D_EST_POINT_TO_POINT, nn_method, 0};
+  m3d_icp* s = nullptr;
+  int rc = icp_create(ctx, src, tgt, max_dist, &p, &s, true);
+  if (rc) return rc;
+  // (after icp_create: its setup used the same arena and has been synchronised)
+  if (ctx->tmp.reserve(eval_scratch_bytes(ns)) != hipSuccess)
+    rc = m3d_fail(ctx, M3D_ERR_OOM, "evaluation scratch");
+  if (!rc) rc = pin_ensure(ctx);
+  double sums[16] = {};
+  // EvaluateRegistration: pcd = source; if (!T.isIdentity()) pcd.Transform(T)
+  if (!rc) rc = icp_reset(s, T_host, true, stream);
+  if (!rc) {
+    // the sums and the scan's fault word land together in the context's mapped pinned memory:
+    // one stream sync brings both back, with no device-to-host copy
+    hipError_t e = enqueue_nn(s, 0, st);
+    if (e == hipSuccess)
+      e = launch_eval(s, (flags & M3D_EVAL_INFORMATION) != 0, corr_idx, d2,
+                      reinterpret_cast<double*>(ctx->tmp.base), pin_read<double>(ctx, true), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    const volatile double* h = pin_read<double>(ctx, false);
+    if (!rc)
+      for (int k = 0; k < 16; ++k) sums[k] = h[k];
+  }
+  m3d_icp_destroy(s);
+  if (rc) return rc;
+  if (sums[15] != 0.0)  // the grid scan's deferral fault word (m3d_icp_result_get)
+    return m3d_fail(ctx, M3D_ERR_HIP,
+                    "grid NN deferral list overflow (count " + std::to_string((uint32_t)sums[14]) +
+                        "): results since the last m3d_icp_reset are invalid");
+  const int64_t matched = (int64_t)sums[0];
+  out->num_correspondences = matched;
+  out->fitness = (double)matched / (double)ns;
+  out->inlier_rmse = matched > 0 ? std::sqrt(sums[1] / (double)matched) : 0.0;
+  if ((flags & M3D_EVAL_INFORMATION) != 0) eval_information(sums, out->information);
+  return M3D_OK;
 }
 
 // ------------------------------------------------------------------------------- preprocessing

@@ -26,6 +26,7 @@ EST_POINT_TO_POINT, EST_POINT_TO_PLANE = 0, 1
 KERNEL_NN, KERNEL_SCORE, KERNEL_KABSCH, KERNEL_TERMS, KERNEL_LOOP, KERNEL_COMM = 0, 1, 2, 3, 4, 5
 ICP_NO_SPLIT = 2
 NN_BRUTE, NN_GRID = 0, 1
+EVAL_INFORMATION = 1
 COMM_ID_BYTES = 128
 DT_I32, DT_I64, DT_F64 = 0, 1, 2
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -71,6 +72,11 @@ class IcpResult(C.Structure):
                 ("update", dbl * 16)]
 
 
+class EvalResult(C.Structure):
+    _fields_ = [("fitness", dbl), ("inlier_rmse", dbl), ("num_correspondences", i64),
+                ("information", dbl * 36)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "m3d_abi_version": (C.c_int, []),
@@ -100,6 +106,8 @@ SIGNATURES = {
     "m3d_cloud_destroy": (None, [vp]),
     "m3d_cloud_size": (i64, [vp]),
     "m3d_nn1": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, i32, vp, vp, vp]),
+    "m3d_evaluate_registration": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, i32, i32,
+                                            C.POINTER(EvalResult), vp, vp, vp]),
     "m3d_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams),
                               C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_create": (C.c_int, [vp, vp, vp, dbl, C.POINTER(IcpParams), C.POINTER(vp)]),

@@ -431,6 +431,42 @@ def nn1(src: Cloud, tgt: Cloud, T, max_dist: float, nn: str = "grid"):
 
 
 @dataclass
+class EvalOutcome:
+    fitness: float
+    inlier_rmse: float
+    num_correspondences: int
+    correspondence_set: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.int32))
+    information: np.ndarray | None = None  # (6, 6) f64 GᵀG of the matched target points
+    d2: object = None                      # (ns,) f64 torch cuda: d² per source, inf = unmatched
+    corr_idx: object = None                # (ns,) int32 torch cuda: matched target, -1 = unmatched
+
+
+def evaluate(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, nn: str = "grid", information=False,
+             with_correspondences=True, with_distances=False) -> EvalOutcome:
+    """Open3D ``evaluate_registration`` (and, with information=True,
+    ``get_information_matrix_from_point_clouds``) of the transform T on the device
+    (m3d_evaluate_registration): the source is transformed by T unless T isIdentity(), every
+    source point takes its nearest target strictly inside max_dist (nn1's winner), and fitness,
+    inlier_rmse and GᵀG are reduced over the matched pairs in fp64 in a fixed order — nn="brute"
+    and nn="grid", and repeated calls, return the same bits."""
+    method = _nn_method(nn)
+    if not max_dist > 0.0:
+        raise ValueError("max_dist must be > 0")
+    torch = _torch()
+    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    d2 = device_empty((max(src.n, 1),), torch.float64) if with_distances else None
+    res = _lib.EvalResult()
+    flags = _lib.EVAL_INFORMATION if information else 0
+    src.ctx.check(src.ctx.lib.m3d_evaluate_registration(
+        src.ctx.h, src.h, tgt.h, _T16(np.eye(4) if T is None else T), float(max_dist), method, flags,
+        C.byref(res), ptr(idx), ptr(d2), stream_handle()), "evaluate_registration")
+    cs = corr_pairs(src.ctx, idx, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
+    info = np.array(res.information[:]).reshape(6, 6) if information else None
+    return EvalOutcome(res.fitness, res.inlier_rmse, res.num_correspondences, cs, info,
+                       None if d2 is None else d2[: src.n], None if idx is None else idx[: src.n])
+
+
+@dataclass
 class IcpOutcome:
     transformation: np.ndarray
     fitness: float

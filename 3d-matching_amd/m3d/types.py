@@ -49,6 +49,13 @@ class PointCloud:
     def has_normals(self) -> bool:
         return len(self.normals) == len(self.points) and len(self.points) > 0
 
+    def compute_point_cloud_distance(self, target) -> np.ndarray:
+        """Open3D ``PointCloud.compute_point_cloud_distance``: for each point the distance to its
+        nearest point of ``target``, on the device (matcher.evaluate)."""
+        from matcher.evaluate import compute_point_cloud_distance
+
+        return compute_point_cloud_distance(self, target)
+
     def transform(self, T):
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]

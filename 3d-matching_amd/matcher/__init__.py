@@ -9,6 +9,11 @@ façade the reference's ``main()`` intends (`src/main.py:34-38`).
 
 from __future__ import annotations
 
+from .evaluate import (
+    compute_point_cloud_distance,
+    evaluate_registration,
+    get_information_matrix_from_point_clouds,
+)
 from .icp import refine_registration, registration_icp
 from .ransac import (
     compute_feature_correspondences,
@@ -22,9 +27,12 @@ from .register import register
 
 __all__ = [
     "compute_feature_correspondences",
+    "compute_point_cloud_distance",
     "compute_step_transformation",
     "evaluate_inlier_ratio",
     "evaluate_inlier_ratio_fast",
+    "evaluate_registration",
+    "get_information_matrix_from_point_clouds",
     "global_registration",
     "run_ransac",
     "refine_registration",

@@ -220,6 +220,31 @@ int m3d_trim_block_cache(m3d_ctx* ctx, int64_t* freed_bytes);
 int m3d_nn1(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* T_host,
             double max_dist, int32_t nn_method, int32_t* idx, double* d2, void* stream);
 
+/* Evaluation of a given transform (Open3D EvaluateRegistration and
+ * GetInformationMatrixFromPointClouds; added within ABI 13, the version number is unchanged).
+ * The source is transformed by T_host [host] 16 f64 (NULL = identity) only when T_host is not
+ * Eigen-isIdentity(), as in m3d_icp_reset(); each source point's correspondence is the winner
+ * m3d_nn1() defines (the lexicographic (d², index) minimum over the targets with d² < max_dist²).
+ *   fitness = matched / ns, inlier_rmse = sqrt(Σd² / matched), both 0 without a match;
+ *   information (flags & M3D_EVAL_INFORMATION) = GᵀG over the matched TARGET points q = (x, y, z)
+ *   in the target's original fp64 coordinates, rows G₁ = (0, z, −y, 1, 0, 0),
+ *   G₂ = (−z, 0, x, 0, 1, 0), G₃ = (y, −x, 0, 0, 0, 1).
+ * corr_idx [device] ns int32 or NULL: the matched target per source in the caller's order (-1 =
+ * none); d2 [device] ns f64 or NULL: its d² (INFINITY = none).  All sums are fp64 and added in a
+ * fixed order: both nn_methods, and repeated calls, return the same bits.  Synchronous (one host
+ * sync).  M3D_ERR_INVALID for max_dist <= 0 or an unknown nn_method; M3D_ERR_HIP when the grid
+ * NN's deferral list overflowed (as m3d_icp_result_get() reports it). */
+#define M3D_EVAL_INFORMATION 1 /* flags: also fill information[] */
+typedef struct {
+  double fitness;              /* matched / ns  (0 when ns == 0) */
+  double inlier_rmse;          /* sqrt(sum d2 / matched)  (0 when matched == 0) */
+  int64_t num_correspondences;
+  double information[36];      /* row-major GtG; zeros unless M3D_EVAL_INFORMATION */
+} m3d_eval_result;
+int m3d_evaluate_registration(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt,
+                              const double* T_host, double max_dist, int32_t nn_method, int32_t flags,
+                              m3d_eval_result* out, int32_t* corr_idx, double* d2, void* stream);
+
 typedef struct {
   double relative_fitness; /* ICPConvergenceCriteria defaults 1e-6 */
   double relative_rmse;    /* 1e-6 */
