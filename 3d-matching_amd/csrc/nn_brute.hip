@@ -339,6 +339,11 @@ __device__ __forceinline__ float wave_minmax(float v) {
 #ifndef M3D_NN_DEFER_BATCH
 #define M3D_NN_DEFER_BATCH 1
 #endif
+// the batched deferred pass pushes only the rows the screen flags for the lane's own query
+// (nn_defer_hits / nn_push_hits); 0 (A/B builds): every lane pushes all 16 of its rows
+#ifndef M3D_NN_DEFER_FILTER
+#define M3D_NN_DEFER_FILTER 1
+#endif
 // diagnostic builds only (tools/nn_clock.py): per-block timeline and tile counts of the last
 // nn_mfma_kernel launch, s_memrealtime (100 MHz: one clock for every block, whichever XCD runs it)
 #ifndef M3D_NN_CLOCK
@@ -681,6 +686,51 @@ __device__ __forceinline__ bool nn_exact_subtiles(uint64_t mg, const float4* __r
   return q.k1 != kb;
 }
 
+// Filtered deferred pass (M3D_NN_DEFER_FILTER): of a flagged sub-tile a lane pushes only the rows
+// the screen flags for its own query, instead of all 16 (cfg1 model, tools/nn_defer_model.py: the
+// lane with the most hits has 2.1 at the mean, 6 at most).  nn_defer_hits runs the sub-tile's
+// screen again — the sweep's MFMA on the same operands: `a` is the sub-tile's A operand from mf16,
+// bq the group's current B operand — and returns the signs of the lane's 16 values, bit reg =
+// value reg (the sweep's v_alignbit record, fed from 15 down so that no bfrev is needed);
+// nn_push_hits walks the set bits, each lane its own, and reads row (reg & 3) + 8·(reg >> 2) + 4·h
+// of the sub-tile from the LDS stash — the row register `reg` of nn_exact_rows holds — by a
+// computed address (a register array indexed per lane would go to scratch).  A lane without bits
+// left is masked; the loop ends when no lane of the wave has one.
+// The result does not change:
+//  1. a deferred group's bq carries the threshold of a bound X_q the query had at setup or at a
+//     later in-tile refresh (refresh_threshold); the bound only tightens (k1 only decreases,
+//     band_of is monotone), so X_q ≥ search_bound of the query's final k1;
+//  2. thr_operand makes the screen value strictly negative for every target with d2f ≤ X_q,
+//     whatever the MFMA's accumulation order (screen_eps_m plus the threshold terms' own share);
+//  3. so the rows pushed are a superset of the targets with d2f ≤ search_bound(final k1);
+//  4. k1 is the same: the minimum over the sub-tile lies inside the bound whenever it beats the
+//     seed, and ties go to the lower index through the same key order; the seed's own target is
+//     flagged and pushed, meets kc == k1 in near_push and counts once;
+//  5. near2 falls at or below the band exactly when it does with all rows pushed; its stored value
+//     may differ only above the band, where winner_fp64 does not look (it compares near2 with
+//     search_bound(final k1) only) — the freedom the cull lemma already takes (box_out_of_reach).
+// An inactive lane's query is the origin with threshold −1: its values are positive, its mask empty
+// (and its state is never published).
+__device__ __forceinline__ uint32_t nn_defer_hits(const half8& a, const half8& bq, const floatx16& zacc) {
+  const floatx16 v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq, zacc, 0, 0, 0);
+  uint32_t m = 0;
+#pragma unroll
+  for (int reg = 15; reg >= 0; --reg) m = __builtin_amdgcn_alignbit(m, __float_as_uint(v[reg]), 31);
+  return m;
+}
+__device__ __forceinline__ void nn_push_hits(uint32_t m, const float4* rows, int64_t off, int h, float qx,
+                                             float qy, float qz, float r2_hi, uint64_t& k1, float& k1d,
+                                             float& n2) {
+  while (m != 0) {
+    const int reg = __builtin_ctz(m);
+    m &= m - 1;
+    const float4 t = rows[(reg & 3) + 8 * (reg >> 2) + 4 * h];
+    // branch-free (push_within): a flagged row is nearly always within r2_hi, and under a branch the
+    // row's index would be a second, dependent LDS read
+    push_within(k1, k1d, n2, d2f(qx, qy, qz, t.x, t.y, t.z), r2_hi, (uint32_t)(off + __float_as_int(t.w)));
+  }
+}
+
 __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(const float4* __restrict__ src32,
                                                           int64_t ns,
                                                           const uint4* __restrict__ tgt16,
@@ -815,9 +865,19 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   // the lane pair merges once at the end instead of after every sub-tile, which gives the same
   // state: (k1, near2) is a function of the set of keys pushed — the minimum and the smallest d²
   // of any other; a key held by both lanes (the seed, an earlier merge) counts once (near_push).
+  // Filtered (M3D_NN_DEFER_FILTER, the default): of a slot's rows a lane pushes only those the
+  // screen, run again for the slot, flags for its own query (nn_defer_hits: why that is the same
+  // result) — the pushes of all 16 rows by every lane were most of the phase (tools/nn_clock.py:
+  // 11.8 → 5.7 µs mean at cfg1, EXPERIMENTS §R12).  Batches of 8, A operands in registers.
 #if M3D_NN_DEFER_BATCH
   if (dn > 0) {
+#if M3D_NN_DEFER_FILTER
+    // filtered (nn_defer_hits): 8 sub-tiles per batch — with the fp32 rows a lane loads the A
+    // operand of each of the batch's sub-tiles (4 registers a slot), all in one round trip
+    constexpr int kStash = 8;
+#else
     constexpr int kStash = 16;  // sub-tiles per batch: 16 × 32 rows × 16 B = 8 KiB per wave
+#endif
     static_assert(kStash * kMG <= 32, "a batch's group flags in one word");
     static_assert(sizeof(t16) >= sizeof(float4) * (kMBlock / 64) * kStash * 32, "a stash per wave");
     float4* const stash = reinterpret_cast<float4*>(&t16[0][0][0]) + wave * (kStash * 32);
@@ -858,6 +918,9 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (;;) {
       uint32_t gsel = 0;  // kMG bits per stash slot
       float4 ld[kStash / 2];
+#if M3D_NN_DEFER_FILTER
+      H8 av[kStash];  // the slots' A operands (an empty slot: row 0's, unused)
+#endif
 #pragma unroll
       for (int k = 0; k < kStash / 2; ++k) {  // slots 2k (lanes 0–31) and 2k + 1 (lanes 32–63)
         uint32_t ra, ga, rb, gb;
@@ -866,12 +929,31 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         gsel |= (ga | (gb << kMG)) << (2 * kMG * k);
         ld[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (h == 0 ? ga != 0 : gb != 0) ld[k] = tgt32[(int64_t)(h == 0 ? ra : rb) + c];  // < nt_pad
+#if M3D_NN_DEFER_FILTER
+        av[2 * k].u = tgt16[(int64_t)h * nt_pad + ra + c];  // row0 + c < nt_pad
+        av[2 * k + 1].u = tgt16[(int64_t)h * nt_pad + rb + c];
+#endif
       }
 #pragma unroll
       for (int k = 0; k < kStash / 2; ++k) stash[(2 * k + h) * 32 + c] = ld[k];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#if M3D_NN_DEFER_FILTER
+#pragma unroll
+      for (int sl = 0; sl < kStash; ++sl) {  // (unrolled: av[sl] stays in registers)
+        const uint32_t gs = (gsel >> (kMG * sl)) & ((1u << kMG) - 1u);
+        if (gs == 0) break;  // the slots fill in order
+        uint32_t hit[kMG];
+#pragma unroll
+        for (int g = 0; g < kMG; ++g) hit[g] = (gs >> g) & 1u ? nn_defer_hits(av[sl].h, q[g].bq, zacc) : 0u;
+#pragma unroll
+        for (int g = 0; g < kMG; ++g)
+          if ((gs >> g) & 1u)
+            nn_push_hits(hit[g], stash + sl * 32, off, h, q[g].qx, q[g].qy, q[g].qz, r2_hi, q[g].k1, q[g].k1d,
+                         q[g].n2);
+      }
+#else
 #pragma unroll 1
       for (int sl = 0; sl < kStash; ++sl) {
         const uint32_t gs = (gsel >> (kMG * sl)) & ((1u << kMG) - 1u);
@@ -883,6 +965,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         for (int g = 0; g < kMG; ++g)
           if ((gs >> g) & 1u) nn_push_rows(t, off, q[g].qx, q[g].qy, q[g].qz, r2_hi, q[g].k1, q[g].k1d, q[g].n2);
       }
+#endif
       if (U == 0 && e + 1 >= dn) break;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();  // the next batch overwrites the stash
