@@ -2142,6 +2142,83 @@ int m3d_compute_fpfh(m3d_ctx* ctx, const m3d_cloud* cloud, const double* normals
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- outlier removal
+// clean.hip; scratch from the context's preprocessing buffer (the calls synchronise before
+// returning), the ladder's grids from the block cache: no hipMalloc per call on the steady path
+extern "C++" {
+namespace {
+int clean_fail(m3d_ctx* ctx, const char* what, hipError_t e, const std::string& why) {
+  return m3d_fail(ctx, M3D_ERR_HIP, std::string(what) + ": " + (why.empty() ? hipGetErrorString(e) : why.c_str()));
+}
+}  // namespace
+}  // extern "C++"
+
+int m3d_knn_search(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, int32_t* idx, double* d2,
+                   int32_t* count, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && idx && d2 && count, "invalid arguments");
+  CHECK_ARG(ctx, k >= 1 && k <= 256, "1 <= k <= 256");
+  if (cloud->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  char* scratch = nullptr;
+  int rc = prep_buffer(ctx, clean_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  hipError_t e = knn_search(ctx, cloud, k, idx, d2, count, scratch, st, &why);
+  if (e != hipSuccess) return clean_fail(ctx, "knn_search", e, why);
+  return M3D_OK;
+}
+
+int m3d_remove_statistical_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_neighbors,
+                                   double std_ratio, int32_t* index_out, int64_t* n_out,
+                                   m3d_outlier_stats* stats, double* avg_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && n_out && (index_out || cloud->n == 0), "invalid arguments");
+  CHECK_ARG(ctx, nb_neighbors >= 1 && std_ratio > 0.0, "Illegal input parameters, the number of neighbors and "
+                                                       "standard deviation ratio must be positive.");
+  CHECK_ARG(ctx, nb_neighbors <= 256, "1 <= nb_neighbors <= 256");
+  *n_out = 0;
+  if (stats) *stats = m3d_outlier_stats{0, 0, 0.0, 0.0, 0.0};
+  if (cloud->n == 0) return M3D_OK;  // Open3D: an empty cloud gives an empty result
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  char* scratch = nullptr;
+  int rc = prep_buffer(ctx, clean_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  double h[4] = {0.0, 0.0, 0.0, 0.0};
+  hipError_t e = statistical_outliers(ctx, cloud, nb_neighbors, std_ratio, index_out, n_out, h, avg_out, scratch,
+                                      st, &why);
+  if (e != hipSuccess) return clean_fail(ctx, "remove_statistical_outlier", e, why);
+  if (stats) *stats = m3d_outlier_stats{*n_out, (int64_t)h[0], h[1], h[2], h[3]};
+  return M3D_OK;
+}
+
+int m3d_remove_radius_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_points, double radius,
+                              int32_t* index_out, int64_t* n_out, int32_t* count_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && n_out && (index_out || cloud->n == 0), "invalid arguments");
+  CHECK_ARG(ctx, nb_points >= 1 && radius > 0.0, "Illegal input parameters, the number of points and radius "
+                                                 "must be positive.");
+  *n_out = 0;
+  if (cloud->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const Grid* g = nullptr;  // cell = radius, cached on the cloud like the hybrid search's grid
+  int rc = ensure_grid(ctx, cloud, radius, st, &g);
+  if (rc) return rc;
+  char* scratch = nullptr;
+  rc = prep_buffer(ctx, clean_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  hipError_t e = radius_outliers(cloud, g, nb_points, radius, index_out, n_out, count_out, scratch, st);
+  if (e != hipSuccess) return clean_fail(ctx, "remove_radius_outlier", e, std::string());
+  return M3D_OK;
+}
+
 // ------------------------------------------------------------------------------- feature matching
 int m3d_feature_correspondences(m3d_ctx* ctx, const double* f_src, int64_t ns, const double* f_tgt,
                                 int64_t nt, int32_t dim, int32_t mutual_filter,

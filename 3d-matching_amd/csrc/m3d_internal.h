@@ -562,4 +562,18 @@ hipError_t launch_corres_inlier(const double* src, const double* tgt, const int3
 hipError_t launch_feat_hyp(const double* src, const double* tgt, const int32_t* corr, int64_t nc,
                            uint64_t seed, int64_t H, double edge, double dist, double* T_out,
                            int32_t* pass, hipStream_t st);
+// outlier removal (clean.hip): exact unbounded k-NN by a radius ladder, the statistical and radius
+// filters.  scratch: clean_scratch_bytes(n) bytes of device memory; every call returns after a
+// stream sync.  why: the message of a failure that is not a HIP error (hipErrorUnknown).
+size_t clean_scratch_bytes(int64_t n);
+hipError_t knn_search(m3d_ctx* ctx, const m3d_cloud* c, int k, int32_t* idx, double* d2, int32_t* cnt,
+                      void* scratch, hipStream_t st, std::string* why);
+// stats_out [host] 4 doubles: valid, mean, std_dev, threshold; avg_out [device] n doubles or null
+hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double std_ratio, int32_t* index_out,
+                                int64_t* n_out, double stats_out[4], double* avg_out, void* scratch,
+                                hipStream_t st, std::string* why);
+// g: the cloud's grid of cell `radius`; count_out [device] n int32 or null (early stop)
+hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius,
+                           int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
+                           hipStream_t st);
 }  // namespace m3d

@@ -77,6 +77,10 @@ class EvalResult(C.Structure):
                 ("information", dbl * 36)]
 
 
+class OutlierStats(C.Structure):
+    _fields_ = [("kept", i64), ("valid", i64), ("mean", dbl), ("std_dev", dbl), ("threshold", dbl)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "m3d_abi_version": (C.c_int, []),
@@ -132,6 +136,10 @@ SIGNATURES = {
     "m3d_hybrid_search": (C.c_int, [vp, vp, dbl, i32, vp, vp, vp, vp]),
     "m3d_estimate_normals": (C.c_int, [vp, vp, dbl, i32, vp, vp]),
     "m3d_compute_fpfh": (C.c_int, [vp, vp, vp, dbl, i32, vp, vp]),
+    "m3d_knn_search": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
+    "m3d_remove_statistical_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64),
+                                                 C.POINTER(OutlierStats), vp, vp]),
+    "m3d_remove_radius_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64), vp, vp]),
     "m3d_feature_correspondences": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, dbl, vp,
                                               C.POINTER(i64), vp]),
     "m3d_ransac_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FeatureRansacParams),

@@ -10,6 +10,9 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``compute_fpfh_feature(pcd, Hybrid(5v, 100))`` (:117)    | ``compute_fpfh`` (N×33)           |
 | ``correspondences_from_features`` (ransac.py:85)         | ``feature_correspondences``       |
 | ``RegistrationRANSACBasedOnCorrespondence`` (a6)         | ``ransac_on_correspondences``     |
+| ``KDTreeFlann.search_knn_vector_3d`` (not in the path)   | ``knn_search`` (every point)      |
+| ``pcd.remove_statistical_outlier(nb, ratio)`` (users)    | ``remove_statistical_outlier``    |
+| ``pcd.remove_radius_outlier(nb, r)`` (users)             | ``remove_radius_outlier``         |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -58,6 +61,86 @@ def hybrid_search(points, radius: float, max_nn: int):
     ctx.check(ctx.lib.m3d_hybrid_search(ctx.h, c.h, float(radius), int(max_nn), ptr(idx), ptr(d2),
                                         ptr(cnt), stream_handle()), "hybrid_search")
     return idx[: c.n].cpu().numpy(), d2[: c.n].cpu().numpy(), cnt[: c.n].cpu().numpy()
+
+
+def _empty(points) -> bool:
+    return (points.n if isinstance(points, Cloud) else len(points)) == 0
+
+
+def knn_search(points, k: int):
+    """KDTreeFlann::SearchKNN(p_i, k) for every point, the point itself included: the min(k, N)
+    smallest (d², index) pairs over the whole cloud → (idx N×k int32 (−1 pad), d2 N×k (inf pad),
+    count N)."""
+    if not 1 <= int(k) <= 256:
+        raise ValueError("knn_search: 1 <= k <= 256")
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    n = max(c.n, 1)
+    idx = device_empty((n, k), torch.int32)
+    d2 = device_empty((n, k), torch.float64)
+    cnt = device_empty((n,), torch.int32)
+    ctx.check(ctx.lib.m3d_knn_search(ctx.h, c.h, int(k), ptr(idx), ptr(d2), ptr(cnt), stream_handle()),
+              "knn_search")
+    return idx[: c.n].cpu().numpy(), d2[: c.n].cpu().numpy(), cnt[: c.n].cpu().numpy()
+
+
+@dataclass
+class OutlierStats:
+    """What RemoveStatisticalOutliers derives from the mean neighbour distances."""
+    kept: int
+    valid: int
+    mean: float
+    std_dev: float
+    threshold: float
+    mean_distance: np.ndarray | None = None  # per point, with ``with_mean_distance=True``
+
+
+def remove_statistical_outlier(points, nb_neighbors: int, std_ratio: float, with_mean_distance: bool = False):
+    """PointCloud::RemoveStatisticalOutliers → (kept indices int32 ascending, OutlierStats)."""
+    if int(nb_neighbors) < 1 or not float(std_ratio) > 0.0:
+        raise ValueError("Illegal input parameters, the number of neighbors and standard deviation ratio "
+                         "must be positive.")
+    if int(nb_neighbors) > 256:
+        raise ValueError("remove_statistical_outlier: nb_neighbors <= 256")
+    if _empty(points):  # an empty cloud gives an empty result, no device involved
+        return np.zeros(0, np.int32), OutlierStats(0, 0, 0.0, 0.0, 0.0,
+                                                   np.zeros(0) if with_mean_distance else None)
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    n = max(c.n, 1)
+    ind = device_empty((n,), torch.int32)
+    avg = device_empty((n,), torch.float64) if with_mean_distance else None
+    m = C.c_int64()
+    st = _lib.OutlierStats()
+    ctx.check(ctx.lib.m3d_remove_statistical_outlier(ctx.h, c.h, int(nb_neighbors), float(std_ratio), ptr(ind),
+                                                     C.byref(m), C.byref(st), ptr(avg), stream_handle()),
+              "remove_statistical_outlier")
+    return ind[: m.value].cpu().numpy(), OutlierStats(int(st.kept), int(st.valid), float(st.mean),
+                                                      float(st.std_dev), float(st.threshold),
+                                                      None if avg is None else avg[: c.n].cpu().numpy())
+
+
+def remove_radius_outlier(points, nb_points: int, radius: float, with_counts: bool = False):
+    """PointCloud::RemoveRadiusOutliers → kept indices int32 ascending (a point is kept iff more
+    than ``nb_points`` points, itself included, lie strictly within ``radius``);
+    ``with_counts=True`` → (indices, every point's full count)."""
+    if int(nb_points) < 1 or not float(radius) > 0.0:
+        raise ValueError("Illegal input parameters, the number of points and radius must be positive.")
+    if _empty(points):
+        return (np.zeros(0, np.int32), np.zeros(0, np.int32)) if with_counts else np.zeros(0, np.int32)
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    n = max(c.n, 1)
+    ind = device_empty((n,), torch.int32)
+    cnt = device_empty((n,), torch.int32) if with_counts else None
+    m = C.c_int64()
+    ctx.check(ctx.lib.m3d_remove_radius_outlier(ctx.h, c.h, int(nb_points), float(radius), ptr(ind), C.byref(m),
+                                                ptr(cnt), stream_handle()), "remove_radius_outlier")
+    kept = ind[: m.value].cpu().numpy()
+    return (kept, cnt[: c.n].cpu().numpy()) if with_counts else kept
 
 
 def estimate_normals(points, radius: float, max_nn: int = 30, normals=None):

@@ -56,6 +56,32 @@ class PointCloud:
 
         return compute_point_cloud_distance(self, target)
 
+    def select_by_index(self, indices, invert: bool = False) -> "PointCloud":
+        """Open3D ``PointCloud.select_by_index``: the points (and normals) at ``indices`` in index
+        order; ``invert`` selects every other point."""
+        n = len(self.points)
+        mask = np.zeros(n, bool)
+        mask[np.asarray(indices, np.int64).reshape(-1)] = True
+        if invert:
+            mask = ~mask
+        return PointCloud(self.points[mask], self.normals[mask] if self.has_normals() else None)
+
+    def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
+        """Open3D ``PointCloud.remove_statistical_outlier`` on the device (m3d.prep) →
+        (filtered cloud, kept indices)."""
+        from .prep import remove_statistical_outlier
+
+        ind, _ = remove_statistical_outlier(self.points, nb_neighbors, std_ratio)
+        return self.select_by_index(ind), ind
+
+    def remove_radius_outlier(self, nb_points: int, radius: float):
+        """Open3D ``PointCloud.remove_radius_outlier`` on the device (m3d.prep) →
+        (filtered cloud, kept indices)."""
+        from .prep import remove_radius_outlier
+
+        ind = remove_radius_outlier(self.points, nb_points, radius)
+        return self.select_by_index(ind), ind
+
     def transform(self, T):
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]

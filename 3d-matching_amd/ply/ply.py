@@ -4,6 +4,10 @@
 by the device path of ``m3d.prep``:
 
 1. read the PLY (``m3d.plyio``; Open3D ``read_point_cloud``)                       ply.py:80
+1a. optional, not in the reference: ``remove_outliers`` = ``{"nb_neighbors", "std_ratio"}`` or
+   ``{"nb_points", "radius"}`` filters ``pcd`` (points and file normals) on the device like
+   Open3D's ``remove_statistical_outlier`` / ``remove_radius_outlier`` before step 2; the
+   default ``None`` leaves every result as it is without it
 2. ``pcd_down`` = voxel down-sample (voxel_size); file normals, when present, are averaged
    per voxel like Open3D's VoxelDownSample                                           ply.py:106
 3. ``pcd_down`` normals: hybrid search (2·v, 30), oriented by those averaged normals ply.py:110-112
@@ -28,7 +32,7 @@ from m3d.types import Feature, PointCloud
 
 
 class Ply:
-    def __init__(self, path, voxel_size: float = 0.3) -> None:
+    def __init__(self, path, voxel_size: float = 0.3, remove_outliers: dict | None = None) -> None:
         self.path = Path(path)
         self.voxel_size = voxel_size
         if not self.path.exists():
@@ -43,9 +47,19 @@ class Ply:
         if len(pts) == 0:
             raise ValueError(f"Point cloud is empty: {self.path}")          # ply.py:81-84
         self.pcd = PointCloud(pts, nrm)
-        self._preprocess(voxel_size)
+        self._preprocess(voxel_size, remove_outliers)
 
-    def _preprocess(self, voxel_size: float) -> None:
+    def _remove_outliers(self, params: dict) -> None:
+        """``pcd`` ← the points (and file normals) one of Open3D's two outlier filters keeps."""
+        keys = set(params)
+        if keys == {"nb_neighbors", "std_ratio"}:
+            self.pcd, _ = self.pcd.remove_statistical_outlier(params["nb_neighbors"], params["std_ratio"])
+        elif keys == {"nb_points", "radius"}:
+            self.pcd, _ = self.pcd.remove_radius_outlier(params["nb_points"], params["radius"])
+        else:
+            raise ValueError("remove_outliers: {'nb_neighbors', 'std_ratio'} or {'nb_points', 'radius'}")
+
+    def _preprocess(self, voxel_size: float, remove_outliers: dict | None = None) -> None:
         """ply.py:53-66.  Wall time of each stage lands in ``stage_ms`` (every stage returns host
         arrays, so the device work is complete when its timer stops)."""
         from m3d import prep
@@ -63,6 +77,9 @@ class Ply:
             ms[name] = (now - t) * 1e3
             t = now
 
+        if remove_outliers is not None:
+            self._remove_outliers(remove_outliers)
+            lap("remove_outliers")
         # the full cloud goes to the device once (down-sampling, then its normals), the
         # down-sampled one once (its normals, then FPFH: the noise is added after, ply.py:61-62)
         p_dev = to_device(self.pcd.points)
@@ -86,13 +103,13 @@ class Ply:
 
     @classmethod
     def from_arrays(cls, points, normals=None, points_down=None, fpfh=None, voxel_size: float = 0.3,
-                    preprocess: bool = False):
+                    preprocess: bool = False, remove_outliers: dict | None = None):
         obj = cls.__new__(cls)
         obj.path = None
         obj.voxel_size = voxel_size
         obj.pcd = PointCloud(points, normals)
         if preprocess:
-            obj._preprocess(voxel_size)
+            obj._preprocess(voxel_size, remove_outliers)
             return obj
         obj.pcd_down = PointCloud(points if points_down is None else points_down)
         obj.pcd_fpfh = None if fpfh is None else Feature(np.asarray(fpfh, np.float64))

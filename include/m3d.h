@@ -433,6 +433,44 @@ int m3d_estimate_normals(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, in
 int m3d_compute_fpfh(m3d_ctx* ctx, const m3d_cloud* cloud, const double* normals, double radius,
                      int32_t max_nn, double* fpfh_out, void* stream);
 
+/* ------------------------------------------------------------------ outlier removal (clean.hip)
+ * What Open3D users run on a raw scan before registering it; the reference's Ply has no such step.
+ * Exact fp64, d² = (dx·dx + dy·dy) + dz·dz, finite coordinates assumed. */
+
+/* KDTreeFlann::SearchKNN(p_i, k) for every point of the cloud, the point itself included: the
+ * min(k, n) lexicographically smallest (d², index) pairs over ALL points (no radius bound; ties by
+ * lower index).  idx [device] n×k int32 (-1 pad), d2 [device] n×k f64 (INFINITY pad), count
+ * [device] n int32 (= min(k, n)).  1 <= k <= 256 (else M3D_ERR_INVALID).  Synchronous. */
+int m3d_knn_search(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, int32_t* idx, double* d2,
+                   int32_t* count, void* stream);
+
+/* PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) (Open3D 0.19):
+ *   avg[i]    = (Σ sqrt(d²) over point i's SearchKNN(nb_neighbors) list, in list order) / count,
+ *   valid     = points with a non-empty list (n), mean = Σ{avg > 0} / valid,
+ *   std_dev   = sqrt(Σ{(avg − mean)² : avg > 0} / (valid − 1)), threshold = mean + std_ratio·std_dev,
+ *   kept      iff avg > 0 && avg < threshold
+ * (so a point whose neighbours all coincide with it is dropped, nb_neighbors = 1 drops every point,
+ * n = 1 gives a NaN threshold and nothing kept, n = 0 nothing without touching the device).
+ * index_out [device] room for n int32: the kept indices in ascending order; *n_out [host] = their
+ * number; stats [host] or NULL; avg_out [device] n f64 or NULL.  The sums are fp64 in a fixed
+ * order: repeated calls return the same bits.  M3D_ERR_INVALID for nb_neighbors < 1 (or > 256)
+ * or std_ratio <= 0 (Open3D: "Illegal input parameters").  Synchronous. */
+typedef struct {
+  int64_t kept, valid;
+  double mean, std_dev, threshold;
+} m3d_outlier_stats;
+int m3d_remove_statistical_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_neighbors,
+                                   double std_ratio, int32_t* index_out, int64_t* n_out,
+                                   m3d_outlier_stats* stats, double* avg_out, void* stream);
+
+/* PointCloud::RemoveRadiusOutliers(nb_points, radius): count[i] = #{j : d²(i, j) < radius²}
+ * (strict, the point itself included); kept iff count[i] > nb_points.  index_out [device] room
+ * for n int32: the kept indices in ascending order; *n_out [host]; count_out [device] n int32 or
+ * NULL (given: every count is complete; NULL: a point's count stops once it exceeds nb_points).
+ * M3D_ERR_INVALID for nb_points < 1 or radius <= 0.  Synchronous. */
+int m3d_remove_radius_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_points, double radius,
+                              int32_t* index_out, int64_t* n_out, int32_t* count_out, void* stream);
+
 /* ------------------------------------------------------------------ feature matching (a5, a6) */
 
 /* CorrespondencesFromFeatures (src/matcher/ransac.py:85): exact fp64 1-NN in feature space
