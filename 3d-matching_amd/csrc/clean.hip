@@ -4,14 +4,14 @@
 //
 // All arithmetic is fp64 in the project's operation order (-ffp-contract=off):
 // d² = (dx·dx + dy·dy) + dz·dz on the cloud's original coordinates, lists in ascending (d², index)
-// order.  The centred fp32 grid points only screen candidates (clean_prefilter, the bound of
-// prep.hip prefilter_bound) and size the cell box (clean_box_half_width): a candidate the screen
-// passes is decided by its exact d², one it drops is provably outside the current threshold.
+// order.  The centred fp32 grid points only screen candidates (prefilter_bound) and size the cell
+// box (box_half_width): a candidate the screen passes is decided by its exact d², one it drops is
+// provably outside the current threshold.  The wave-held sorted list, the box scan that fills it
+// and their exactness argument live in knn_wave.h, shared with prep.hip's hybrid search.
 //
 // Unbounded k-NN = a radius ladder over uniform grids (knn_ladder).  Level ℓ searches the still
-// pending queries on a grid of cell r_ℓ (r₀, then at least doubling) with the hybrid search's rule (the k best with strict
-// d² < r²; one wave per query, the sorted list across the lanes as prep.hip
-// hybrid_search_wave_kernel holds it).  A query that holds kk = min(k, n) entries is FINISHED:
+// pending queries on a grid of cell r_ℓ (r₀, then at least doubling) with the hybrid search's rule
+// (the k best with strict d² < r²; one wave per query).  A query that holds kk = min(k, n) entries is FINISHED:
 // every point it did not take has d² ≥ r² > each entry, or lost the (d², index) compare inside
 // the radius, so the entries are its global kk nearest.  The others are appended to the next
 // level's list (an integer atomic on a counter; the order of that list changes no result, every
@@ -40,6 +40,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "m3d_internal.h"
+#include "knn_wave.h"
 
 namespace m3d {
 namespace {
@@ -48,60 +49,12 @@ constexpr int kCleanBlock = 256;
 constexpr int kMaxLevels = 64;     // host bound of the ladder (ladder radii span ≤ 2^41: see r0 clamp)
 constexpr int kProbeMax = 6;       // density probe grids at most
 constexpr uint32_t kFewPending = 1024;  // knn_ladder: so few unfinished queries speed the radius up
-constexpr double kU32 = 5.9604644775390625e-08;  // 2^-24
 
-__device__ __forceinline__ int cl_coord(float x, float o, float inv_h, int n) {
-  float f = (x - o) * inv_h;  // == grid.hip grid_coord
-  f = fminf(fmaxf(f, 0.0f), (float)(n - 1));
-  return (int)f;
-}
-
-__device__ __forceinline__ double cl_d2(const double* a, const double* b) {
-  const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
-// prep.hip prefilter_bound: the largest directly computed fp32 d² a point with fp64 d² ≤ thr can
-// have, e = the bound on |fp32 distance − fp64 distance| of two centred points
-__device__ __forceinline__ float clean_prefilter(double thr, double e) {
-  const double b = (sqrt(thr) + e) * (1.0 + 4e-6);
-  const float f = __double2float_ru(b * b * (1.0 + 4e-6));
-  return isfinite(f) ? f : FLT_MAX;
-}
-
-__device__ __forceinline__ bool cl_less(double d, int32_t t, double D, int32_t T) {
-  return d < D || (d == D && t < T);
-}
-
-// lane l ← lane l − 1 (DPP wave_shr:1; lane 0 keeps `old`)
-__device__ __forceinline__ int32_t cl_shr1(int32_t old, int32_t v) {
-  return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ double cl_shr1(double old, double v) {
-  const uint64_t o = (uint64_t)__double_as_longlong(old), x = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)cl_shr1((int32_t)(uint32_t)o, (int32_t)(uint32_t)x);
-  const uint32_t hi = (uint32_t)cl_shr1((int32_t)(uint32_t)(o >> 32), (int32_t)(uint32_t)(x >> 32));
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ double cl_readlane(double v, int l) {
-  const uint64_t x = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)x, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(x >> 32), l);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-__device__ __forceinline__ void cl_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// One level of the ladder, ONE WAVE per pending query (kk ≤ 64·kS entries, entry e in lane
-// e % 64, slot e / 64).  pend_in null: level 0, wave w takes the point at position w of the
+// One level of the ladder, ONE WAVE per pending query (kk ≤ 64·kS entries in a knn_wave.h
+// WaveKnnList).  pend_in null: level 0, wave w takes the point at position w of the
 // grid's cell order (neighbouring waves then read the same cell rows).  kMean: the output is the
 // query's mean neighbour distance (Σ sqrt(d²) in list order from 0.0, divided by the count)
-// instead of the list.  Every loop is bounded by the grid's dimensions, a cell row's length or the
-// 64 bits of a ballot.
+// instead of the list.
 //
 // kW = 1: four queries per 256-thread block (level 0: every point, small boxes).  kW > 1 (the
 // levels above: few queries, each with a box that grows to the whole cloud): ONE query per block of
@@ -128,169 +81,34 @@ __global__ __launch_bounds__(kW == 1 ? kCleanBlock : kW * kWave) void knn_level_
   const int64_t i = pend_in != nullptr ? (int64_t)pend_in[wq] : (int64_t)__float_as_int(g.pts[wq].w);
   const double q[3] = {xyz64[3 * i], xyz64[3 * i + 1], xyz64[3 * i + 2]};
   const float4 qf = xyz32[i];
-  double D[kS];
-  int32_t T[kS];
-#pragma unroll
-  for (int u = 0; u < kS; ++u) {
-    D[u] = 0.0;
-    T[u] = -1;
-  }
-  int cnt = 0;      // entries held (wave-uniform)
-  double thr = r2;  // exact threshold: r² until kk are held, then the kk-th entry (inclusive)
-  int32_t thr_t = INT32_MAX;
-  float bf = clean_prefilter(r2, eabs);
-  // one entry into the sorted list: its place = the held entries below it (a ballot), the
-  // entries from there on move up one lane, the kk-th entry sets the next threshold
-  auto insert = [&](double x, int32_t xt) {
-    int pos = 0;
-#pragma unroll
-    for (int u = 0; u < kS; ++u) {
-      const int e = u * 64 + lane;
-      pos += __popcll(__ballot(e < cnt && cl_less(D[u], T[u], x, xt)));
-    }
-#pragma unroll
-    for (int u = kS - 1; u >= 0; --u) {
-      // lane 0 of slot u takes lane 63 of slot u − 1, the others their left neighbour
-      const double d63 = u > 0 ? cl_readlane(D[u > 0 ? u - 1 : 0], 63) : 0.0;
-      const int32_t t63 = u > 0 ? __builtin_amdgcn_readlane(T[u > 0 ? u - 1 : 0], 63) : -1;
-      const double dc = cl_shr1(d63, D[u]);
-      const int32_t tc = cl_shr1(t63, T[u]);
-      const int e = u * 64 + lane;
-      if (e > pos) {
-        D[u] = dc;
-        T[u] = tc;
-      } else if (e == pos) {
-        D[u] = x;
-        T[u] = xt;
-      }
-    }
-    cnt = cnt < kk ? cnt + 1 : kk;
-    if (cnt == kk) {
-      const int u = (kk - 1) / 64, l = (kk - 1) % 64;
-      double dk = D[0];
-      int32_t tk = T[0];
-#pragma unroll
-      for (int v = 0; v < kS; ++v)
-        if (v == u) {
-          dk = D[v];
-          tk = T[v];
-        }
-      thr = cl_readlane(dk, l);
-      thr_t = __builtin_amdgcn_readlane(tk, l);
-    }
-  };
-  const int x0 = cl_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
-  const int x1 = cl_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
-  const int y0 = cl_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
-  const int y1 = cl_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
-  const int z0 = cl_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
-  const int z1 = cl_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
-  for (int cz = z0; cz <= z1; ++cz)
-    for (int cy = y0; cy <= y1; ++cy) {
-      const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
-      const int32_t j0 = g.start[row + x0], j1 = g.start[row + x1 + 1];
-      for (int32_t jb = j0 + 64 * sub; jb < j1; jb += 64 * kW) {
-        const int32_t j = jb + lane;
-        bool cand = false;
-        double d = 0.0;
-        int32_t t = -1;
-        if (j < j1) {
-          const float4 tp = g.pts[j];
-          const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
-          if ((fx * fx + fy * fy) + fz * fz <= bf) {
-            t = __float_as_int(tp.w);
-            d = cl_d2(xyz64 + 3 * (int64_t)t, q);
-            cand = d < r2 && (cnt < kk ? true : cl_less(d, t, thr, thr_t));
-          }
-        }
-        uint64_t m = __ballot(cand);
-        if constexpr (kS == 1) {
-          // several candidates at once: every element's place in the union of the held list and
-          // the chunk's candidates is its rank (the keys are distinct), written to LDS at that
-          // rank and read back (prep.hip hybrid_search_wave_kernel)
-          const int c = __popcll(m);
-          if (c >= 3) {
-            int rl = lane, rc = 0;
-            for (uint64_t mm = m; mm != 0; mm &= mm - 1) {
-              const int s = __builtin_ctzll(mm);
-              const double x = cl_readlane(d, s);
-              const int32_t xt = __builtin_amdgcn_readlane(t, s);
-              rl += cl_less(x, xt, D[0], T[0]) ? 1 : 0;
-              rc += cl_less(x, xt, d, t) ? 1 : 0;
-            }
-            int lo = 0, hi = cnt;  // list entries below this lane's candidate
-            for (int it = 0; it < 7; ++it) {
-              const int mid = (lo + hi) >> 1;
-              const int src = mid < 64 ? mid : 63;
-              const double dm = __shfl(D[0], src);
-              const int32_t tm = __shfl(T[0], src);
-              if (lo < hi) {
-                if (cl_less(dm, tm, d, t))
-                  lo = mid + 1;
-                else
-                  hi = mid;
-              }
-            }
-            rc += lo;
-            const int ncnt = cnt + c < kk ? cnt + c : kk;
-            if (lane < cnt && rl < kk) {
-              s_d[w][rl] = D[0];
-              s_t[w][rl] = T[0];
-            }
-            if (cand && rc < kk) {
-              s_d[w][rc] = d;
-              s_t[w][rc] = t;
-            }
-            cl_wave_sync();
-            if (lane < ncnt) {
-              D[0] = s_d[w][lane];
-              T[0] = s_t[w][lane];
-            }
-            cl_wave_sync();
-            cnt = ncnt;
-            if (cnt == kk) {
-              thr = cl_readlane(D[0], kk - 1);
-              thr_t = __builtin_amdgcn_readlane(T[0], kk - 1);
-            }
-            m = 0;
-          }
-        }
-        while (m != 0) {
-          const int src = __builtin_ctzll(m);
-          m &= m - 1;
-          const double x = cl_readlane(d, src);
-          const int32_t xt = __builtin_amdgcn_readlane(t, src);
-          if (cnt == kk && !cl_less(x, xt, thr, thr_t)) continue;  // the threshold moved
-          insert(x, xt);
-        }
-        if (cnt == kk) bf = clean_prefilter(thr, eabs);
-      }
-    }
+  WaveKnnList<kS> L;
+  L.reset(r2, eabs);
+  wave_knn_scan_box(L, xyz64, q, qf, g, Rf, r2, eabs, kk, 64 * sub, 64 * kW, s_d[w], s_t[w]);
   if constexpr (kW > 1) {
     if (w > 0) {
 #pragma unroll
       for (int u = 0; u < kS; ++u) {
         const int e = u * 64 + lane;
-        if (e < cnt) {
-          m_d[w][e] = D[u];
-          m_t[w][e] = T[u];
+        if (e < L.cnt) {
+          m_d[w][e] = L.D[u];
+          m_t[w][e] = L.T[u];
         }
       }
-      if (lane == 0) m_c[w] = cnt;
+      if (lane == 0) m_c[w] = L.cnt;
     }
     __syncthreads();
     if (w > 0) return;
     for (int ww = 1; ww < kW; ++ww) {
       const int c = __builtin_amdgcn_readfirstlane(m_c[ww]);
       for (int e = 0; e < c; ++e) {
-        const double x = cl_readlane(m_d[ww][e], 0);  // the same address in every lane
+        const double x = readlane_f64(m_d[ww][e], 0);  // the same address in every lane
         const int32_t xt = __builtin_amdgcn_readfirstlane(m_t[ww][e]);
-        if (cnt == kk && !cl_less(x, xt, thr, thr_t)) break;  // sorted: the rest is not below it either
-        insert(x, xt);
+        if (!L.accepts(x, xt, kk)) break;  // sorted: the rest is not below the threshold either
+        L.insert(x, xt, kk);
       }
     }
   }
-  if (cnt < kk) {  // fewer than kk points strictly inside the radius: the next level's
+  if (L.cnt < kk) {  // fewer than kk points strictly inside the radius: the next level's
     if (lane == 0) pend_out[atomicAdd(pend_cnt, 1u)] = (int32_t)i;
     return;
   }
@@ -298,21 +116,21 @@ __global__ __launch_bounds__(kW == 1 ? kCleanBlock : kW * kWave) void knn_level_
     double acc = 0.0;
 #pragma unroll
     for (int u = 0; u < kS; ++u) {
-      const double s = sqrt(D[u]);
-      const int m = cnt - u * 64 < 64 ? cnt - u * 64 : 64;
-      for (int l = 0; l < m; ++l) acc += cl_readlane(s, l);
+      const double s = sqrt(L.D[u]);
+      const int m = L.cnt - u * 64 < 64 ? L.cnt - u * 64 : 64;
+      for (int l = 0; l < m; ++l) acc += readlane_f64(s, l);
     }
-    if (lane == 0) out_avg[i] = acc / (double)cnt;
+    if (lane == 0) out_avg[i] = acc / (double)L.cnt;
   } else {
 #pragma unroll
     for (int u = 0; u < kS; ++u) {
       const int e = u * 64 + lane;
       if (e < k) {
-        out_idx[i * k + e] = e < cnt ? T[u] : -1;
-        out_d2[i * k + e] = e < cnt ? D[u] : INFINITY;
+        out_idx[i * k + e] = e < L.cnt ? L.T[u] : -1;
+        out_d2[i * k + e] = e < L.cnt ? L.D[u] : INFINITY;
       }
     }
-    if (lane == 0) out_cnt[i] = cnt;
+    if (lane == 0) out_cnt[i] = L.cnt;
   }
 }
 
@@ -329,12 +147,12 @@ __global__ __launch_bounds__(kCleanBlock) void radius_count_kernel(
   const int64_t i = (int64_t)__float_as_int(g.pts[wq].w);
   const double q[3] = {xyz64[3 * i], xyz64[3 * i + 1], xyz64[3 * i + 2]};
   const float4 qf = xyz32[i];
-  const int x0 = cl_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
-  const int x1 = cl_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
-  const int y0 = cl_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
-  const int y1 = cl_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
-  const int z0 = cl_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
-  const int z1 = cl_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
+  const int x0 = grid_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
+  const int x1 = grid_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
+  const int y0 = grid_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
+  const int y1 = grid_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
+  const int z0 = grid_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
+  const int z1 = grid_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
   int32_t total = 0;
   bool stop = false;  // wave-uniform
   for (int cz = z0; cz <= z1 && !stop; ++cz)
@@ -348,7 +166,7 @@ __global__ __launch_bounds__(kCleanBlock) void radius_count_kernel(
           const float4 tp = g.pts[j];
           const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
           if ((fx * fx + fy * fy) + fz * fz <= bf)
-            in = cl_d2(xyz64 + 3 * (int64_t)__float_as_int(tp.w), q) < r2;
+            in = d2_exact(xyz64 + 3 * (int64_t)__float_as_int(tp.w), q) < r2;
         }
         total += (int32_t)__popcll(__ballot(in));
         if (!kFull && total > nb_points) stop = true;
@@ -457,16 +275,6 @@ __global__ __launch_bounds__(kCleanBlock) void stat_flag_kernel(const double* __
 }
 
 // ------------------------------------------------------------------------------- host side
-// the fp32 box half-width that covers every point within `radius` (fp64) of a query
-// (prep.hip box_half_width)
-float clean_box_half_width(const m3d_cloud* c, double radius) {
-  const double Rd = (radius + 2.0 * c->rmax * kU32 * 1.01) * (1.0 + 1e-6);
-  const float f = (float)Rd * (1.0f + 1e-6f);
-  return std::isfinite(f) ? f : FLT_MAX;
-}
-// bound on |fp32 distance − fp64 distance| of two centred points (√3·2·u·rmax)
-double clean_eabs(const m3d_cloud* c) { return 3.4641016151377544 * c->rmax * kU32 * 1.01; }
-
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct CleanScratch {
@@ -521,7 +329,7 @@ double ladder_end(const m3d_cloud* c) {
     }
     diag = std::sqrt(s);
   }
-  return (diag + clean_eabs(c)) * (1.0 + 1e-6);
+  return (diag + pair_eabs(c)) * (1.0 + 1e-6);
 }
 
 // The box the call's grids span.  A grid spans its bounds with at most 2²⁵ cells, so a few points far
@@ -643,7 +451,7 @@ hipError_t ladder_r0(m3d_ctx* ctx, const m3d_cloud* c, int kk, double end, hipSt
   }
   // not below the fp32 resolution of the frame, nor so small that the ladder could not reach its
   // end within kMaxLevels doublings
-  r = std::max(r, 4.0 * clean_eabs(c));
+  r = std::max(r, 4.0 * pair_eabs(c));
   r = std::max(r, end * 0x1p-40);
   if (!(r > 0.0) || !std::isfinite(r)) r = 1.0;
   *r0 = r;
@@ -656,8 +464,8 @@ template <bool kMean>
 hipError_t launch_level(const m3d_cloud* c, const Grid& g, double radius, int k, int kk, const int32_t* pend_in,
                         int64_t npend, int32_t* pend_out, uint32_t* pend_cnt, int32_t* idx, double* d2,
                         int32_t* cnt, double* avg, hipStream_t st) {
-  const float Rf = clean_box_half_width(c, radius);
-  const double eabs = clean_eabs(c), r2 = radius * radius;
+  const float Rf = box_half_width(c, radius);
+  const double eabs = pair_eabs(c), r2 = radius * radius;
   const int kS = kk <= 64 ? 1 : (kk <= 128 ? 2 : 4);
 #define M3D_KNN_LEVEL(S, W, blocks, threads)                                                                  \
   knn_level_kernel<S, kMean, W><<<(blocks), (threads), 0, st>>>(c->xyz64, c->xyz32, g.dev, Rf, r2, eabs, k, kk, \
@@ -809,13 +617,9 @@ hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points,
   char* S = static_cast<char*>(scratch);
   const CleanScratch L = clean_layout(n);
   uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
-  const float Rf = clean_box_half_width(c, radius);
-  const double r2 = radius * radius, eabs = clean_eabs(c);
-  // clean_prefilter on the host: the largest fp32 d² a point with fp64 d² ≤ r² can have
-  const double b = (std::sqrt(r2) + eabs) * (1.0 + 4e-6);
-  float bf = (float)(b * b * (1.0 + 4e-6));
-  bf = std::nextafter(bf, FLT_MAX);  // round up
-  if (!std::isfinite(bf)) bf = FLT_MAX;
+  const float Rf = box_half_width(c, radius);
+  const double r2 = radius * radius;
+  const float bf = prefilter_bound(r2, pair_eabs(c));  // the threshold is r² throughout: one bound
   const unsigned blocks = (unsigned)((n + 3) / 4);
   if (count_out != nullptr)
     radius_count_kernel<true><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf,

@@ -42,13 +42,21 @@ def test_voxel_down_sample_rejects_bad_voxel():
         prep.voxel_down_sample(np.array([[0.0, 0, 0], [1e9, 0, 0]]), 1e-3)
 
 
-@pytest.mark.parametrize("case", ["surface", "duplicates", "plane", "offset", "dense"])
-def test_hybrid_search_exact(case):
+@pytest.mark.parametrize("case,radii", [
+    pytest.param(c, None, id=c) for c in ["surface", "duplicates", "plane", "offset", "dense"]] + [
+    # 128 < k ≤ 256 (four list slots per lane): some lists full and the rest short and padded; the
+    # first k of that form with no list full; ties by index across the 64-lane slot boundaries
+    pytest.param("surface", [(1.5, 200)], id="surface-k200"),
+    pytest.param("surface", [(1.0, 129)], id="surface-k129"),
+    pytest.param("duplicates", [(1.5, 200)], id="duplicates-k200")])
+def test_hybrid_search_exact(case, radii):
     """Lists equal the oracle's bit for bit.  "plane" and "dense" are dense enough for the
     two-stage search (prep.hip hybrid_fine_radius: a finer first grid, full search again when
-    fewer than k points lie within its radius), "plane" at k = 30 with many such repeats."""
+    fewer than k points lie within its radius), "plane" at k = 30 with many such repeats.  The
+    k > 128 cases by the oracle: surface-k200 21 % of the lists full, the rest 117 to 199 entries;
+    surface-k129 no list full (at most 119); duplicates-k200 84 % full."""
     rng = np.random.default_rng(3)
-    radii = [(0.6, 30), (1.5, 100)]
+    radii = radii or [(0.6, 30), (1.5, 100)]
     if case == "dense":
         pts, _ = synth.surface_points(60000, seed=7)
         radii = [(0.6, 30), (1.0, 100)]

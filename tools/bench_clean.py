@@ -13,6 +13,7 @@ import json
 import os
 import sys
 import time
+from pathlib import Path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.join(HERE, "..", "3d-matching_amd")]
@@ -42,6 +43,9 @@ def main():
     import torch
 
     from m3d import _lib, synth
+
+    if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+        _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
     from m3d.core import Cloud, device_empty, ptr, stream_handle
 
     k = a.k
