@@ -204,13 +204,14 @@ def _eigvec1(A, ev0, e1):
     return U
 
 
-def fast_eigen3x3(cov):
-    """Open3D FastEigen3x3 (Eberly, RobustEigenSymmetric3x3): eigenvector of the smallest
-    eigenvalue (not normalised to a sign)."""
+def fast_eigen3x3_path(cov, acos=math.acos, cos=math.cos):
+    """Open3D FastEigen3x3 (Eberly, RobustEigenSymmetric3x3) → (eigenvector of the smallest
+    eigenvalue, not normalised to a sign; the name of the return taken).  ``acos`` / ``cos`` are
+    the two libm calls of the solver, replaceable to model another libm (tests/prep_zoo.py)."""
     A = np.array(cov, np.float64)
     mx = A.max()
     if mx == 0:
-        return np.zeros(3)
+        return np.zeros(3), "zero"
     A = A / mx
     norm = A[0, 1] * A[0, 1] + A[0, 2] * A[0, 2] + A[1, 2] * A[1, 2]
     if norm > 0:
@@ -222,32 +223,37 @@ def fast_eigen3x3(cov):
         c02 = A[0, 1] * A[1, 2] - b11 * A[0, 2]
         det = (b00 * c00 - A[0, 1] * c01 + A[0, 2] * c02) / (p * p * p)
         half_det = min(max(det * 0.5, -1.0), 1.0)
-        angle = math.acos(half_det) / 3.0
+        angle = acos(half_det) / 3.0
         two_thirds_pi = 2.09439510239319549
-        beta2 = math.cos(angle) * 2
-        beta0 = math.cos(angle + two_thirds_pi) * 2
+        beta2 = cos(angle) * 2
+        beta0 = cos(angle + two_thirds_pi) * 2
         beta1 = -(beta0 + beta2)
         e0, e1, e2 = q + p * beta0, q + p * beta1, q + p * beta2
         if half_det >= 0:
             v2 = _eigvec0(A, e2)
             if e2 < e0 and e2 < e1:
-                return v2
+                return v2, "pos-v2"
             v1 = _eigvec1(A, v2, e1)
             if e1 < e0 and e1 < e2:
-                return v1
-            return _cross(v1, v2)
+                return v1, "pos-v1"
+            return _cross(v1, v2), "pos-cross"
         v0 = _eigvec0(A, e0)
         if e0 < e1 and e0 < e2:
-            return v0
+            return v0, "neg-v0"
         v1 = _eigvec1(A, v0, e1)
         if e1 < e0 and e1 < e2:
-            return v1
-        return _cross(v0, v1)
+            return v1, "neg-v1"
+        return _cross(v0, v1), "neg-cross"
     if A[0, 0] < A[1, 1] and A[0, 0] < A[2, 2]:
-        return np.array([1.0, 0.0, 0.0])
+        return np.array([1.0, 0.0, 0.0]), "diag-x"
     if A[1, 1] < A[0, 0] and A[1, 1] < A[2, 2]:
-        return np.array([0.0, 1.0, 0.0])
-    return np.array([0.0, 0.0, 1.0])
+        return np.array([0.0, 1.0, 0.0]), "diag-y"
+    return np.array([0.0, 0.0, 1.0]), "diag-z"
+
+
+def fast_eigen3x3(cov):
+    """The eigenvector of ``fast_eigen3x3_path``."""
+    return fast_eigen3x3_path(cov)[0]
 
 
 def estimate_normals(points, radius, max_nn, prev_normals=None, nbrs=None):
@@ -379,13 +385,19 @@ def feature_nn(fq, fr):
     fq = np.asarray(fq, np.float64)
     fr = np.asarray(fr, np.float64)
     out = np.zeros(len(fq), np.int64)
-    for a in range(0, len(fq), 256):
-        blk = fq[a:a + 256]
-        d = np.zeros((len(blk), len(fr)))
+    frT = np.ascontiguousarray(fr.T)               # one contiguous row per dimension
+    rows = max(1, min(256, 65536 // max(len(fr), 1)))  # query rows per pass: d and t stay in cache
+    d = np.empty((rows, len(fr)))
+    t = np.empty((rows, len(fr)))
+    for a in range(0, len(fq), rows):
+        blk = fq[a:a + rows]
+        dd, tt = d[:len(blk)], t[:len(blk)]
+        dd.fill(0.0)
         for j in range(fq.shape[1]):
-            t = blk[:, j, None] - fr[None, :, j]
-            d += t * t
-        out[a:a + 256] = np.argmin(d, axis=1)   # argmin: first (lowest) index on ties
+            np.subtract(blk[:, j, None], frT[j][None, :], out=tt)
+            np.multiply(tt, tt, out=tt)
+            dd += tt
+        out[a:a + rows] = np.argmin(dd, axis=1)   # argmin: first (lowest) index on ties
     return out
 
 
