@@ -30,6 +30,15 @@ size_t eval_scratch_bytes(int64_t ns);
 hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
                        double* out, hipStream_t st);
 hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st);
+// gicp.hip: covariances (6 doubles per point: the upper triangle) and the plane-to-plane terms pass
+// after a loop's NN scan; sums[0 .. 30) in the point-to-plane slot layout, sums[30 / 31] the
+// deferral count / fault when with_defer
+int64_t gicp_blocks(int64_t ns);
+hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, double* out, int width,
+                                   hipStream_t st);
+hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, double* out6, hipStream_t st);
+hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
+                             double* sums, bool with_defer, hipStream_t st);
 }  // namespace m3d
 
 using namespace m3d;
@@ -1990,6 +1999,190 @@ int m3d_evaluate_registration(m3d_ctx* ctx, const m3d_cloud* src, const m3d_clou
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- Generalized ICP
+// gicp.hip.  The loop object is the point-to-plane loop's (state, NN scan, solve); the
+// covariances and the terms pass's partials live in one block of their own beside it.
+int m3d_covariances_from_normals(m3d_ctx* ctx, const double* normals, int64_t n, double epsilon,
+                                 double* cov_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, n >= 0 && (n == 0 || (normals && cov_out)), "invalid arguments");
+  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
+  hipSetDevice(ctx->device);
+  HIPX(ctx, launch_cov_from_normals(normals, n, epsilon, cov_out, 9, S(stream)));
+  return M3D_OK;
+}
+
+namespace {
+// the covariance arrays of one Generalized-ICP call: the source's in the loop's Morton slot order
+// (rotated in place by every evaluation), the target's in target index order, 6 doubles per point
+struct GicpArrays {
+  void* block = nullptr;
+  double* cov_s = nullptr;
+  double* cov_t = nullptr;
+  double* partials = nullptr;
+  m3d_ctx* ctx = nullptr;
+  hipStream_t st = nullptr;
+  // back to the block cache, marked after the work this call enqueued on its stream
+  ~GicpArrays() {
+    if (block == nullptr) return;
+    ctx_touch(ctx, st);
+    ReleaseScope rs(ctx, ctx->id);
+    block_release(block);
+  }
+};
+
+int gicp_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+               const double* tgt_cov, double max_dist, int32_t nn_method, double epsilon) {
+  CHECK_ARG(ctx, src && tgt, "invalid arguments");
+  CHECK_ARG(ctx, max_dist > 0.0, "Invalid max_correspondence_distance.");
+  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
+  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
+  CHECK_ARG(ctx, src_cov != nullptr || src->nrm64 != nullptr || src->n == 0,
+            "Generalized ICP: the source has neither covariances nor normals");
+  CHECK_ARG(ctx, tgt_cov != nullptr || tgt->nrm64 != nullptr || tgt->n == 0,
+            "Generalized ICP: the target has neither covariances nor normals");
+  return M3D_OK;
+}
+
+// allocate the arrays and (re-)initialise the covariances: the caller's (its order → slot order
+// for the source), else from the normals — the Morton copy's are in slot order already
+int gicp_setup(m3d_icp* s, const double* src_cov, const double* tgt_cov, double epsilon, hipStream_t st,
+               GicpArrays* ga) {
+  m3d_ctx* ctx = s->ctx;
+  const int64_t ns = s->src->n, nt = s->tgt->n;
+  ga->ctx = ctx;
+  ga->st = st;
+  Carve cc;
+  cc.add(&ga->cov_s, 6 * (size_t)ns);
+  cc.add(&ga->cov_t, 6 * (size_t)nt);
+  cc.add(&ga->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(gicp_blocks(ns), 1));
+  size_t bytes = 0;
+  if (cc.alloc(&ga->block, &bytes, st) != hipSuccess)
+    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (Generalized ICP covariances)");
+  HIPX(ctx, src_cov != nullptr ? launch_cov_pack(src_cov, s->src->slot, ns, ga->cov_s, st)
+                               : launch_cov_from_normals(s->src->nrm64, ns, epsilon, ga->cov_s, 6, st));
+  HIPX(ctx, tgt_cov != nullptr ? launch_cov_pack(tgt_cov, nullptr, nt, ga->cov_t, st)
+                               : launch_cov_from_normals(s->tgt->nrm64, nt, epsilon, ga->cov_t, 6, st));
+  return M3D_OK;
+}
+
+// the loop object of a Generalized-ICP call: created as a point-to-point loop (no demand on the
+// target's normals — the covariances may be the caller's), then switched to the point-to-plane
+// estimator, whose state and solve the plane-to-plane sums feed (same slot layout)
+int gicp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist, double rel_fit,
+                double rel_rmse, int32_t max_iteration, int32_t nn_method, m3d_icp** out) {
+  m3d_icp_params p{rel_fit, rel_rmse, max_iteration, M3D_EST_POINT_TO_POINT, nn_method, 0};
+  const int rc = icp_create(ctx, src, tgt, max_dist, &p, out, true);
+  if (!rc) (*out)->params.estimation = M3D_EST_POINT_TO_PLANE;
+  return rc;
+}
+}  // namespace
+
+int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                   const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
+                   double epsilon, double* sums_out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  CHECK_ARG(ctx, sums_out != nullptr, "null output");
+  int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, nn_method, epsilon);
+  if (rc) return rc;
+  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
+  hipStream_t st = S(stream);
+  const int64_t ns = src->n, nt = tgt->n;
+  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
+    hipSetDevice(ctx->device);
+    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    return M3D_OK;
+  }
+  m3d_icp* s = nullptr;
+  rc = gicp_create(ctx, src, tgt, max_dist, 1e-6, 1e-6, 0, nn_method, &s);
+  if (rc) return rc;
+  GicpArrays ga;
+  rc = pin_ensure(ctx);
+  if (!rc) rc = gicp_setup(s, src_cov, tgt_cov, epsilon, st, &ga);
+  // pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and covariances
+  if (!rc) rc = icp_reset(s, T_host, true, stream);
+  double sums[kTermSlots] = {};
+  if (!rc) {
+    hipError_t e = enqueue_nn(s, 0, st);
+    if (e == hipSuccess) {
+      KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+      e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin_read<double>(ctx, true), true, st);
+    }
+    if (e == hipSuccess && corr_idx != nullptr) e = launch_scatter_i32(s->corr, s->src->slot, ns, corr_idx, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    const volatile double* h = pin_read<double>(ctx, false);
+    if (!rc)
+      for (int k = 0; k < kTermSlots; ++k) sums[k] = h[k];
+  }
+  m3d_icp_destroy(s);
+  if (rc) return rc;
+  if (sums[31] != 0.0)  // the grid scan's deferral fault word (m3d_icp_result_get)
+    return m3d_fail(ctx, M3D_ERR_HIP,
+                    "grid NN deferral list overflow (count " + std::to_string((uint32_t)sums[30]) +
+                        "): results since the last m3d_icp_reset are invalid");
+  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
+  return M3D_OK;
+}
+
+int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                 const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
+                 m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
+  int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, params->nn_method, params->epsilon);
+  if (rc) return rc;
+  m3d_icp* s = nullptr;
+  rc = gicp_create(ctx, src, tgt, max_dist, params->relative_fitness, params->relative_rmse,
+                   params->max_iteration, params->nn_method, &s);
+  if (rc) return rc;
+  hipStream_t st = S(stream);
+  const bool search = src->n > 0 && tgt->n > 0;  // else: no scan, zero sums, every source unmatched
+  GicpArrays ga;
+  rc = gicp_setup(s, src_cov, tgt_cov, params->epsilon, st, &ga);
+  if (!rc) rc = m3d_icp_reset(s, init, stream);
+  // max_iteration + 1 evaluations (NN scan, plane-to-plane terms + reduce, point-to-plane solve),
+  // enqueued in growing chunks with a look at `done` in between, as m3d_icp_run; evaluations
+  // after convergence are device no-ops
+  if (!rc) {
+    int32_t left = params->max_iteration + 1, chunk = 4;
+    while (!rc && left > 0) {
+      const int32_t k = std::min(chunk, left);
+      hipError_t e = hipSuccess;
+      for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
+        if (search) e = enqueue_nn(s, 0, st);
+        if (e == hipSuccess) {
+          KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+          e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, s->sums, false, st);
+        }
+        if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
+      }
+      if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, std::string("gicp step: ") + hipGetErrorString(e));
+      left -= k;
+      chunk *= 2;
+      if (rc || left == 0) break;
+      int32_t done = 0;
+      e = hipMemcpyAsync(&done, &s->state->done, sizeof(done), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+      if (done) break;
+    }
+  }
+  if (!rc) rc = m3d_icp_result_get(s, out, stream);
+  if (!rc && corr_idx && src->n > 0) {
+    hipError_t e = launch_scatter_i32(s->corr, s->src->slot, src->n, corr_idx, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+  }
+  if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
+  m3d_icp_destroy(s);
+  return rc;
+}
+
 // ------------------------------------------------------------------------------- preprocessing
 extern "C++" {
 namespace {
@@ -2168,6 +2361,33 @@ int m3d_knn_search(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, int32_t* idx
   std::string why;
   hipError_t e = knn_search(ctx, cloud, k, idx, d2, count, scratch, st, &why);
   if (e != hipSuccess) return clean_fail(ctx, "knn_search", e, why);
+  return M3D_OK;
+}
+
+int m3d_estimate_normals_knn(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, double* normals_out,
+                             void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && (normals_out || cloud->n == 0), "invalid arguments");
+  CHECK_ARG(ctx, k >= 1 && k <= 256, "1 <= k <= 256");
+  const int64_t n = cloud->n;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  // the k-NN lists and the ladder's scratch side by side in the context's preprocessing buffer
+  const size_t bi = tmp_align(sizeof(int32_t) * (size_t)n * k), bd = tmp_align(sizeof(double) * (size_t)n * k);
+  const size_t bc = tmp_align(sizeof(int32_t) * (size_t)n);
+  char* b = nullptr;
+  int rc = prep_buffer(ctx, bi + bd + bc + clean_scratch_bytes(n), &b);
+  if (rc) return rc;
+  int32_t* idx = reinterpret_cast<int32_t*>(b);
+  double* d2 = reinterpret_cast<double*>(b + bi);
+  int32_t* cnt = reinterpret_cast<int32_t*>(b + bi + bd);
+  std::string why;
+  hipError_t e = knn_search(ctx, cloud, k, idx, d2, cnt, b + bi + bd + bc, st, &why);
+  if (e != hipSuccess) return clean_fail(ctx, "knn_search", e, why);
+  HIPX(ctx, launch_normals(cloud, idx, k, cnt, cloud->nrm64, normals_out, st));
+  HIPX(ctx, hipStreamSynchronize(st));
   return M3D_OK;
 }
 

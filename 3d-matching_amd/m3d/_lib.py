@@ -77,6 +77,11 @@ class EvalResult(C.Structure):
                 ("information", dbl * 36)]
 
 
+class GicpParams(C.Structure):
+    _fields_ = [("relative_fitness", dbl), ("relative_rmse", dbl), ("max_iteration", i32),
+                ("nn_method", i32), ("epsilon", dbl)]
+
+
 class OutlierStats(C.Structure):
     _fields_ = [("kept", i64), ("valid", i64), ("mean", dbl), ("std_dev", dbl), ("threshold", dbl)]
 
@@ -112,6 +117,10 @@ SIGNATURES = {
     "m3d_nn1": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, i32, vp, vp, vp]),
     "m3d_evaluate_registration": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, i32, i32,
                                             C.POINTER(EvalResult), vp, vp, vp]),
+    "m3d_covariances_from_normals": (C.c_int, [vp, vp, i64, dbl, vp, vp]),
+    "m3d_gicp_terms": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, i32, dbl, C.POINTER(dbl), vp, vp]),
+    "m3d_gicp_run": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(GicpParams),
+                               C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams),
                               C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_create": (C.c_int, [vp, vp, vp, dbl, C.POINTER(IcpParams), C.POINTER(vp)]),
@@ -137,6 +146,7 @@ SIGNATURES = {
     "m3d_estimate_normals": (C.c_int, [vp, vp, dbl, i32, vp, vp]),
     "m3d_compute_fpfh": (C.c_int, [vp, vp, vp, dbl, i32, vp, vp]),
     "m3d_knn_search": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
+    "m3d_estimate_normals_knn": (C.c_int, [vp, vp, i32, vp, vp]),
     "m3d_remove_statistical_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64),
                                                  C.POINTER(OutlierStats), vp, vp]),
     "m3d_remove_radius_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64), vp, vp]),

@@ -507,6 +507,63 @@ def icp(src: Cloud, tgt: Cloud, max_dist: float, init=None, estimation=_lib.EST_
                       np.array(res.update[:]).reshape(4, 4))
 
 
+def _cov_device(cov, n: int, what: str):
+    """A cloud's explicit covariances (n×3×3, or None) as an (n, 9) cuda tensor."""
+    if cov is None:
+        return None
+    t = to_device(cov, "float64", (9,))
+    if t.shape[0] != n:
+        raise ValueError(f"{what} covariances must be {n}×3×3")
+    return t
+
+
+def gicp_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, src_cov=None, tgt_cov=None,
+               epsilon: float = 1e-3, nn: str = "grid", with_correspondences=True):
+    """One Generalized-ICP evaluation at the transform T (m3d_gicp_terms): the exact radius 1-NN,
+    then the plane-to-plane sums over the matched pairs → (sums (30,) f64: JᵀJ upper triangle
+    row-major, Jᵀr, Σr², count, Σd²; corr_idx (ns,) int32 torch cuda or None).  src_cov / tgt_cov:
+    n×3×3 covariances in the cloud's point order, or None = from the cloud's normals with epsilon."""
+    method = _nn_method(nn)
+    if not max_dist > 0.0:
+        raise ValueError("max_dist must be > 0")
+    if not epsilon > 0.0:
+        raise ValueError("epsilon must be > 0")
+    torch = _torch()
+    cs, ct = _cov_device(src_cov, src.n, "source"), _cov_device(tgt_cov, tgt.n, "target")
+    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    sums = (C.c_double * 32)()
+    src.ctx.check(src.ctx.lib.m3d_gicp_terms(
+        src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), _T16(np.eye(4) if T is None else T), float(max_dist),
+        method, float(epsilon), sums, ptr(idx), stream_handle()), "gicp_terms")
+    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
+
+
+def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_cov=None,
+         epsilon: float = 1e-3, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
+         with_correspondences=True, nn: str = "grid"):
+    """registration_generalized_icp on the device (m3d_gicp_run) → IcpOutcome.  src_cov / tgt_cov:
+    n×3×3 covariances in the cloud's point order, or None = from the cloud's normals with
+    epsilon (a cloud with neither raises ValueError)."""
+    method = _nn_method(nn)
+    if not max_dist > 0.0:
+        raise ValueError("Invalid max_correspondence_distance.")
+    if not epsilon > 0.0:
+        raise ValueError("epsilon must be > 0")
+    torch = _torch()
+    cs, ct = _cov_device(src_cov, src.n, "source"), _cov_device(tgt_cov, tgt.n, "target")
+    p = _lib.GicpParams(float(relative_fitness), float(relative_rmse), int(max_iteration), method,
+                        float(epsilon))
+    res = _lib.IcpResult()
+    corr = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    src.ctx.check(src.ctx.lib.m3d_gicp_run(src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct),
+                                           _T16(np.eye(4) if init is None else init), float(max_dist),
+                                           C.byref(p), C.byref(res), ptr(corr), stream_handle()), "gicp_run")
+    pairs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
+    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
+                      res.num_correspondences, res.iterations, bool(res.converged), pairs,
+                      np.array(res.update[:]).reshape(4, 4))
+
+
 class IcpLoop:
     """Step-wise device ICP (benchmarks, multi-GPU).  Every call only enqueues work."""
 

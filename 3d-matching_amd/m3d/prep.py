@@ -155,6 +155,37 @@ def estimate_normals(points, radius: float, max_nn: int = 30, normals=None):
     return out[: c.n].cpu().numpy()
 
 
+def estimate_normals_knn(points, knn: int = 20, normals=None):
+    """PointCloud::EstimateNormals(KDTreeSearchParamKNN(knn)) (m3d_estimate_normals_knn): the
+    covariance of each point's exact ``knn`` nearest points, itself included → N×3; fewer than
+    three neighbours give (0, 0, 1); existing ``normals`` orient the result like Open3D."""
+    if not 1 <= int(knn) <= 256:
+        raise ValueError("estimate_normals_knn: 1 <= knn <= 256")
+    torch = _torch()
+    c = _cloud(points, normals)
+    ctx = c.ctx
+    out = device_empty((max(c.n, 1), 3), torch.float64)
+    ctx.check(ctx.lib.m3d_estimate_normals_knn(ctx.h, c.h, int(knn), ptr(out), stream_handle()),
+              "estimate_normals_knn")
+    return out[: c.n].cpu().numpy()
+
+
+def covariances_from_normals(normals, epsilon: float = 1e-3):
+    """Generalized ICP's per-point covariances (InitializePointCloudForGeneralizedICP):
+    C = Rx·diag(ε, 1, 1)·Rxᵀ with Rx the rotation of e1 onto the normal → N×3×3, exactly
+    symmetric (m3d_covariances_from_normals)."""
+    if not float(epsilon) > 0.0:
+        raise ValueError("epsilon must be > 0")
+    torch = _torch()
+    ctx = context()
+    nrm = to_device(normals)
+    n = nrm.shape[0]
+    out = device_empty((max(n, 1), 9), torch.float64)
+    ctx.check(ctx.lib.m3d_covariances_from_normals(ctx.h, ptr(nrm), n, float(epsilon), ptr(out),
+                                                   stream_handle()), "covariances_from_normals")
+    return out[:n].cpu().numpy().reshape(n, 3, 3)
+
+
 def compute_fpfh(points, normals, radius: float, max_nn: int = 100):
     """ComputeFPFHFeature → N×33 (Open3D's Feature.data is the 33×N transpose)."""
     torch = _torch()

@@ -4,7 +4,8 @@
   uses it (`ransac.py:134-136`, `icp.py:42`): ``transformation`` (4×4 f64), ``fitness``,
   ``inlier_rmse``, ``correspondence_set`` (M×2 int32).
 * ``PointCloud`` — the two attributes the path reads from ``o3d.geometry.PointCloud``:
-  ``points`` (N×3 f64) and ``normals`` (N×3 f64 or empty).
+  ``points`` (N×3 f64) and ``normals`` (N×3 f64 or empty), and ``covariances`` (N×3×3 f64 or
+  empty) for Generalized ICP.
 """
 
 from __future__ import annotations
@@ -39,15 +40,21 @@ class Feature:
 
 
 class PointCloud:
-    def __init__(self, points=None, normals=None):
+    def __init__(self, points=None, normals=None, covariances=None):
         self.points = np.zeros((0, 3)) if points is None else np.asarray(points, np.float64).reshape(-1, 3)
         self.normals = np.zeros((0, 3)) if normals is None else np.asarray(normals, np.float64).reshape(-1, 3)
+        # per-point 3×3 covariances (Open3D ``PointCloud.covariances``, Generalized ICP), or none
+        self.covariances = (np.zeros((0, 3, 3)) if covariances is None
+                            else np.asarray(covariances, np.float64).reshape(-1, 3, 3))
 
     def has_points(self) -> bool:
         return len(self.points) > 0
 
     def has_normals(self) -> bool:
         return len(self.normals) == len(self.points) and len(self.points) > 0
+
+    def has_covariances(self) -> bool:
+        return len(self.covariances) == len(self.points) and len(self.points) > 0
 
     def compute_point_cloud_distance(self, target) -> np.ndarray:
         """Open3D ``PointCloud.compute_point_cloud_distance``: for each point the distance to its
@@ -57,14 +64,15 @@ class PointCloud:
         return compute_point_cloud_distance(self, target)
 
     def select_by_index(self, indices, invert: bool = False) -> "PointCloud":
-        """Open3D ``PointCloud.select_by_index``: the points (and normals) at ``indices`` in index
-        order; ``invert`` selects every other point."""
+        """Open3D ``PointCloud.select_by_index``: the points (and normals, covariances) at
+        ``indices`` in index order; ``invert`` selects every other point."""
         n = len(self.points)
         mask = np.zeros(n, bool)
         mask[np.asarray(indices, np.int64).reshape(-1)] = True
         if invert:
             mask = ~mask
-        return PointCloud(self.points[mask], self.normals[mask] if self.has_normals() else None)
+        return PointCloud(self.points[mask], self.normals[mask] if self.has_normals() else None,
+                          self.covariances[mask] if self.has_covariances() else None)
 
     def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
         """Open3D ``PointCloud.remove_statistical_outlier`` on the device (m3d.prep) →
@@ -87,4 +95,7 @@ class PointCloud:
         self.points = self.points @ T[:3, :3].T + T[:3, 3]
         if len(self.normals):
             self.normals = self.normals @ T[:3, :3].T
+        if len(self.covariances):  # C ← R·C·Rᵀ, as Open3D's PointCloud::Transform
+            R = T[:3, :3]
+            self.covariances = R @ self.covariances @ R.T
         return self

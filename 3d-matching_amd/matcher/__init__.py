@@ -14,6 +14,7 @@ from .evaluate import (
     evaluate_registration,
     get_information_matrix_from_point_clouds,
 )
+from .gicp import registration_generalized_icp
 from .icp import refine_registration, registration_icp
 from .ransac import (
     compute_feature_correspondences,
@@ -36,6 +37,7 @@ __all__ = [
     "global_registration",
     "run_ransac",
     "refine_registration",
+    "registration_generalized_icp",
     "registration_icp",
     "register",
 ]

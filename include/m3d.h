@@ -408,6 +408,66 @@ int m3d_icp_copy_corr(const m3d_icp* s, int32_t* dst, void* stream);
 /* dst [device] ns int32: dst[k] = the source point index held in slot k (ABI 8). */
 int m3d_icp_copy_slots(const m3d_icp* s, int32_t* dst, void* stream);
 
+/* ------------------------------------------------------------------ Generalized ICP (gicp.hip)
+ * Open3D 0.19 registration_generalized_icp (GeneralizedICP.cpp, plane-to-plane), restated in
+ * tests/gicp_restatement.py; added within ABI 13, the version number is unchanged.  It is
+ * RegistrationICP with another ComputeTransformation: the NN search, the loop's transformed copy
+ * of the source and the convergence rule are m3d_icp_run's.
+ *
+ * Covariances: every point carries a 3x3 covariance.  From a unit normal n
+ * (InitializePointCloudForGeneralizedICP):  C = Rx diag(epsilon, 1, 1) Rx^T with
+ * Rx = GetRotationFromE1ToX(n):  v = e1 x n, c = e1 . n;  Rx = I when c < -0.99, else
+ * Rx = I + [v]x + [v]x^2 / (1 + c).  The library holds a covariance as its upper triangle (the
+ * lower one is its mirror): of a caller's row-major 3x3 it reads entries 0 1 2 4 5 8.
+ *
+ * One update over the correspondence set, vs / Cs the loop's transformed source point and
+ * covariance (every update dT rotates the covariances too, C <- R C R^T), vt / Ct the target's:
+ *   d = vs - vt, M = Ct + Cs, J0 = [-[vs]x | I] (3x6),
+ *   JtJ = sum J0^T M^-1 J0, Jtr = sum J0^T M^-1 d, sum r^2 = sum d^T M^-1 d
+ * (Open3D's residual rows W d and Jacobian rows W J0 with W = M^(-1/2), unit weights), solved and
+ * turned into dT exactly as point-to-plane (JtJ x = -Jtr, LDLT, TransformVector6dToMatrix4d); the
+ * identity for an empty set.  fitness and inlier_rmse come from the NN distances.  All sums are
+ * fp64 and added in a fixed order: both nn_methods, and repeated calls, return the same bits. */
+
+/* cov_out[i] = the covariance of normals[i] (formula above).  normals [device] n x 3 f64, cov_out
+ * [device] n x 9 f64 row-major (exactly symmetric).  M3D_ERR_INVALID for epsilon <= 0.  Only
+ * enqueues work on stream. */
+int m3d_covariances_from_normals(m3d_ctx* ctx, const double* normals, int64_t n, double epsilon,
+                                 double* cov_out, void* stream);
+
+/* One evaluation: the source (points and covariances) transformed by T_host [host] 16 f64 (NULL =
+ * identity) only when T_host is not Eigen-isIdentity(), the radius-bounded exact 1-NN of m3d_nn1,
+ * then the 30 sums over the matched pairs in the point-to-plane slot layout: sums_out [host] 32
+ * f64 = JtJ upper triangle row-major (0..20), Jtr (21..26), sum r^2 (27), count (28), sum d^2
+ * (29), 0, 0 — what a Gauss-Newton step of the caller's own needs (m3d_icp_solve takes the same
+ * layout).  src_cov / tgt_cov [device] n x 9 f64 row-major in the cloud's point order, or NULL =
+ * from the cloud's normals with epsilon (M3D_ERR_INVALID when it has none).  corr_idx [device] ns
+ * int32 or NULL: the matched target per source in the caller's order (-1 = none).  An empty
+ * source or target gives zeros.  M3D_ERR_INVALID for epsilon <= 0, max_dist <= 0 or an unknown
+ * nn_method; M3D_ERR_HIP when the grid NN's deferral list overflowed.  Synchronous. */
+int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                   const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
+                   double epsilon, double* sums_out, int32_t* corr_idx, void* stream);
+
+typedef struct {
+  double relative_fitness; /* ICPConvergenceCriteria defaults 1e-6 */
+  double relative_rmse;    /* 1e-6 */
+  int32_t max_iteration;   /* 30 */
+  int32_t nn_method;       /* M3D_NN_* */
+  double epsilon;          /* covariances from normals: 1e-3 */
+} m3d_gicp_params;
+
+/* registration_generalized_icp.  init [host] 16 f64 (applied to points and covariances unless
+ * isIdentity()); src_cov / tgt_cov as in m3d_gicp_terms; out->T, fitness, inlier_rmse,
+ * num_correspondences, iterations, converged, update as m3d_icp_run fills them; corr_idx [device]
+ * ns int32 or NULL: the final correspondence per source (-1 = none).  The loop runs on one device,
+ * enqueued in growing chunks with a look at the state's `done` in between, as m3d_icp_run.
+ * M3D_ERR_INVALID as m3d_gicp_terms, and for max_iteration < 0; M3D_ERR_HIP for a deferral-list
+ * overflow, as m3d_icp_result_get reports it.  Synchronous. */
+int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                 const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
+                 m3d_icp_result* out, int32_t* corr_idx, void* stream);
+
 /* ------------------------------------------------------------------ preprocessing
  * Open3D 0.19 semantics restated (oracle/prep_oracle.py); all fp64. */
 
@@ -443,6 +503,14 @@ int m3d_compute_fpfh(m3d_ctx* ctx, const m3d_cloud* cloud, const double* normals
  * [device] n int32 (= min(k, n)).  1 <= k <= 256 (else M3D_ERR_INVALID).  Synchronous. */
 int m3d_knn_search(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, int32_t* idx, double* d2,
                    int32_t* count, void* stream);
+
+/* PointCloud::EstimateNormals(KDTreeSearchParamKNN(k)) — what registration_generalized_icp runs
+ * (k = 20) on a cloud that has neither covariances nor normals: the covariance of each point's
+ * m3d_knn_search list (the point itself included) -> FastEigen3x3, as m3d_estimate_normals does
+ * with its hybrid list; fewer than 3 neighbours (k < 3 or n < 3) give (0, 0, 1); the cloud's own
+ * normals, if any, orient the result.  normals_out [device] n x 3.  1 <= k <= 256.  Synchronous. */
+int m3d_estimate_normals_knn(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, double* normals_out,
+                             void* stream);
 
 /* PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) (Open3D 0.19):
  *   avg[i]    = (Σ sqrt(d²) over point i's SearchKNN(nb_neighbors) list, in list order) / count,
