@@ -18,29 +18,6 @@
 #include "m3d_internal.h"
 #include "ddmath.h"
 
-namespace m3d {
-hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st);
-hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st);
-hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st);
-hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStream_t st);
-int64_t terms_blocks(int64_t ns);
-// eval.hip: the evaluation pass after a loop's NN scan; out[0 .. 16) receives the sums
-// (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz) and, in words 14 / 15, the deferral count / fault
-size_t eval_scratch_bytes(int64_t ns);
-hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
-                       double* out, hipStream_t st);
-hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st);
-// gicp.hip: covariances (6 doubles per point: the upper triangle) and the plane-to-plane terms pass
-// after a loop's NN scan; sums[0 .. 30) in the point-to-plane slot layout, sums[30 / 31] the
-// deferral count / fault when with_defer
-int64_t gicp_blocks(int64_t ns);
-hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, double* out, int width,
-                                   hipStream_t st);
-hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, double* out6, hipStream_t st);
-hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
-                             double* sums, bool with_defer, hipStream_t st);
-}  // namespace m3d
-
 using namespace m3d;
 
 int m3d_fail(m3d_ctx* ctx, int code, const std::string& msg) {
@@ -1332,10 +1309,6 @@ int icp_shard_nn_range(m3d_icp* s, int64_t off, int64_t q0, int64_t q1, int64_t*
 namespace {
 int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist,
                const m3d_icp_params* params, m3d_icp** out, bool run_arena);
-constexpr int kLoopArrays = 11;
-struct LoopLayout {
-  bool heavy;
-};
 }
 
 int m3d_icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist,
@@ -1358,22 +1331,6 @@ int32_t heavy_cap(const m3d_icp_params* params, int64_t coarse_max_occ) {
   }();
   if (params->nn_method != M3D_NN_GRID) return 0;
   return heavy_env > 0 ? heavy_env : (heavy_env < 0 && coarse_max_occ >= kHeavyCell ? kHeavyCand : 0);
-}
-
-// the loop's arrays: state, keys, near2, dprev, ld64, lidx, corr, partials + sums, hlist, hcnt
-// (+ ticket), pcd64 — offsets into one block
-LoopLayout loop_layout(int64_t ns, int32_t cand_cap, size_t* off, size_t* tot) {
-  const size_t n1 = (size_t)std::max<int64_t>(ns, 1);
-  const size_t nh = cand_cap > 0 ? n1 : 0;
-  const size_t sz[kLoopArrays] = {sizeof(IcpState), 8 * n1, 4 * n1, 8 * n1, 8 * n1, 4 * n1, 4 * n1,
-                                  sizeof(double) * (size_t)(terms_blocks(ns) * kTermSlots + kTermSlots), 4 * nh,
-                                  kDeferWords * sizeof(uint32_t), 24 * n1};
-  *tot = 0;
-  for (int k = 0; k < kLoopArrays; ++k) {
-    off[k] = *tot;
-    *tot += tmp_align(sz[k]);
-  }
-  return LoopLayout{nh > 0};
 }
 
 // run_arena: the loop's arrays come from the context's run arena (kept between calls) instead of
@@ -1399,9 +1356,7 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
   const m3d_cloud* src_m = nullptr;
   int64_t coarse_max_occ = 0;  // most target points in one cell at cell ≈ r (grid NN)
   int32_t cand_cap = 0;
-  size_t off[kLoopArrays] = {}, tot = 0;
-  LoopLayout layout{};
-  void* blk = nullptr;
+  m3d_icp* s = new m3d_icp();
   {
     // Grid NN: cell ≈ the search radius, a query visits 3 cells per axis.  Brute force: the
     // same grids only ORDER the points (targets and queries in cell order make the MFMA
@@ -1450,20 +1405,34 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
     // waited for on the null stream, and so covered by the sync below)
     if (!grc) {
       cand_cap = heavy_cap(params, coarse_max_occ);
-      layout = loop_layout(src->n, cand_cap, off, &tot);
-      if (!run_arena && block_alloc(&blk, tot, nullptr) != hipSuccess)
-        grc = m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (ICP loop arrays)");
-      if (!grc && run_arena && ctx->run.reserve(tot) != hipSuccess)
-        grc = m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (ICP loop arrays)");
+      const size_t n1 = (size_t)std::max<int64_t>(src->n, 1);
+      Carve cv;
+      cv.add(&s->state, 1);
+      cv.add(&s->keys, n1);
+      cv.add(&s->near2, n1);
+      cv.add(&s->dprev, n1);
+      cv.add(&s->ld64, n1);
+      cv.add(&s->lidx, n1);
+      cv.add(&s->corr, n1);
+      cv.add(&s->partials, (size_t)(terms_blocks(src->n) * kTermSlots + kTermSlots));  // + the sums
+      if (cand_cap > 0) {  // the deferral list and its header (count, ticket, fault)
+        cv.add(&s->hlist, n1);
+        cv.add(&s->hcnt, kDeferWords);
+        s->hcap = (int32_t)n1;
+      }
+      cv.add(&s->pcd64, 3 * n1);
+      size_t tot = 0;
+      hipError_t e = run_arena ? ctx->run.reserve(cv.bytes()) : cv.alloc(&s->block, &tot, nullptr);
+      if (e != hipSuccess) grc = m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (ICP loop arrays)");
+      if (!grc && run_arena) cv.place(ctx->run.base);
     }
     // the deferral list's count / ticket / fault word start at zero BEFORE the sync below: a block
     // from the cache may hold any bytes of its previous owner (e.g. 0xFF fills), and a memset left
     // queued on the null stream is not ordered before a caller's non-blocking stream
-    if (!grc && layout.heavy) {
-      char* b0 = run_arena ? ctx->run.base : static_cast<char*>(blk);
-      if (hipMemsetAsync(b0 + off[9], 0, kDeferWords * sizeof(uint32_t), nullptr) != hipSuccess)
-        grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: deferral counter");
-    }
+    // (grid_nn_heavy_kernel re-zeroes count + ticket, icp_reset all)
+    if (!grc && s->hcnt != nullptr &&
+        hipMemsetAsync(s->hcnt, 0, kDeferWords * sizeof(uint32_t), nullptr) != hipSuccess)
+      grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: deferral counter");
     // the setup above ran asynchronously on the null stream: finish it before the loop object is
     // used on the caller's streams
     if (!grc) {
@@ -1471,11 +1440,11 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
       if (e != hipSuccess) grc = m3d_fail(ctx, M3D_ERR_HIP, std::string("loop setup: ") + hipGetErrorString(e));
     }
     if (grc) {
-      block_release(blk);
+      block_release(s->block);
+      delete s;
       return grc;
     }
   }
-  m3d_icp* s = new m3d_icp();
   s->ctx = ctx;
   s->ctx_id = ctx->id;
   s->src = src_m;
@@ -1497,36 +1466,7 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
   if (src->has_bounds && tgt->has_bounds)
     for (int k = 0; k < 3; ++k)
       if ((double)(tgt->hi[k] - tgt->lo[k]) * 2.0 < (double)(src->hi[k] - src->lo[k])) s->scan_xchunk = 8;
-  int rc = M3D_OK;
-  char* b = static_cast<char*>(blk);
-  if (run_arena) {
-    b = ctx->run.base;  // reserved (and its deferral words zeroed) before the setup sync
-  } else {
-    s->block = blk;
-  }
-  if (b == nullptr) {
-    rc = m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (ICP loop arrays)");
-  } else {
-    s->state = reinterpret_cast<IcpState*>(b + off[0]);
-    s->keys = reinterpret_cast<int64_t*>(b + off[1]);
-    s->near2 = reinterpret_cast<uint32_t*>(b + off[2]);
-    s->dprev = reinterpret_cast<int64_t*>(b + off[3]);
-    s->ld64 = reinterpret_cast<int64_t*>(b + off[4]);
-    s->lidx = reinterpret_cast<int32_t*>(b + off[5]);
-    s->corr = reinterpret_cast<int32_t*>(b + off[6]);
-    s->partials = reinterpret_cast<double*>(b + off[7]);
-    s->sums = s->partials + s->nblocks * kTermSlots;
-    s->pcd64 = reinterpret_cast<double*>(b + off[10]);
-    if (layout.heavy) {  // zeroed above; grid_nn_heavy_kernel re-zeroes count + ticket, icp_reset all
-      s->hlist = reinterpret_cast<int32_t*>(b + off[8]);
-      s->hcnt = reinterpret_cast<uint32_t*>(b + off[9]);
-      s->hcap = (int32_t)std::max<int64_t>(src->n, 1);
-    }
-  }
-  if (rc) {
-    m3d_icp_destroy(s);
-    return rc;
-  }
+  s->sums = s->partials + s->nblocks * kTermSlots;
   *out = s;
   return M3D_OK;
 }
@@ -1788,6 +1728,18 @@ int m3d_icp_set_source_total(m3d_icp* s, int64_t ns_total) {
   return M3D_OK;
 }
 
+namespace {
+// the grid scan's deferral list overflowed (a count the scan found larger than the list — the
+// loop's own writes were dropped, never out of bounds): the keys of this run are not trustworthy.
+// count / fault: the list header's words (m3d_icp::hcnt), however they reached the host
+int defer_fault(m3d_ctx* ctx, uint32_t count, bool fault) {
+  if (!fault) return M3D_OK;
+  return m3d_fail(ctx, M3D_ERR_HIP,
+                  "grid NN deferral list overflow (count " + std::to_string(count) +
+                      "): results since the last m3d_icp_reset are invalid");
+}
+}  // namespace
+
 int m3d_icp_result_get(m3d_icp* s, m3d_icp_result* out, void* stream) {
   if (!s || !out) return M3D_ERR_INVALID;
   Touch tch{s->ctx, S(stream)};
@@ -1798,12 +1750,7 @@ int m3d_icp_result_get(m3d_icp* s, m3d_icp_result* out, void* stream) {
   if (s->hcnt != nullptr)
     HIPX(ctx, hipMemcpyAsync(defer, s->hcnt, sizeof(defer), hipMemcpyDeviceToHost, S(stream)));
   HIPX(ctx, hipStreamSynchronize(S(stream)));
-  // the grid scan's deferral list overflowed (a count the scan found larger than the list — the
-  // loop's own writes were dropped, never out of bounds): the keys of this run are not trustworthy
-  if (defer[kDeferFault] != 0)
-    return m3d_fail(ctx, M3D_ERR_HIP,
-                    "grid NN deferral list overflow (count " + std::to_string(defer[0]) +
-                        "): results since the last m3d_icp_reset are invalid");
+  if (const int rc = defer_fault(ctx, defer[0], defer[kDeferFault] != 0)) return rc;
   for (int k = 0; k < 16; ++k) {
     out->T[k] = h.T[k];
     out->update[k] = h.last_upd[k];
@@ -1863,46 +1810,90 @@ int m3d_icp_copy_slots(const m3d_icp* s, int32_t* dst, void* stream) {
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- one-shot loops
+// The synchronous entry points that make a loop object, use it once and drop it.
+extern "C++" {
+namespace {
+// the throw-away loop of one call: destroyed when the call returns, on every path
+struct ScopedLoop {
+  m3d_icp* s = nullptr;
+  ~ScopedLoop() { m3d_icp_destroy(s); }
+  m3d_icp* operator->() const { return s; }
+  operator m3d_icp*() const { return s; }
+};
+
+// `total` evaluations, step(k) enqueueing the next k of them, in growing chunks (4, 8, 16, …)
+// with a look at the state's `done` between chunks — a converged loop (often after a handful of
+// evaluations) then does not enqueue the remaining ~2 launches per evaluation that would only
+// read `done` and return.  The evaluations that run are the same; only the early-exit launches
+// are skipped.
+template <class Step>
+int run_chunked(m3d_icp* s, int32_t total, Step step, hipStream_t st) {
+  int32_t left = total, chunk = 4;
+  while (left > 0) {
+    const int32_t k = std::min(chunk, left);
+    const int rc = step(k);
+    left -= k;
+    chunk *= 2;
+    if (rc || left == 0) return rc;
+    int32_t done = 0;
+    hipError_t e = hipMemcpyAsync(&done, &s->state->done, sizeof(done), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return m3d_fail(s->ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    if (done) break;
+  }
+  return M3D_OK;
+}
+
+// after the evaluations: the result, and the correspondences in the caller's source order
+int finish_run(m3d_icp* s, m3d_icp_result* out, int32_t* corr_idx, hipStream_t st) {
+  const int rc = m3d_icp_result_get(s, out, st);
+  if (rc || !corr_idx || s->src->n == 0) return rc;
+  hipError_t e = launch_scatter_i32(s->corr, s->src->slot, s->src->n, corr_idx, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e == hipSuccess ? M3D_OK : m3d_fail(s->ctx, M3D_ERR_HIP, hipGetErrorString(e));
+}
+
+// One evaluation at the transform T: reset, NN scan, the caller's pass over the scan, the
+// correspondences in the caller's source order (corr_idx null: none), one stream sync.
+// n > 0: pass(out) leaves n doubles in `out`, the context's mapped pinned memory, the last two the
+// grid scan's deferral count and fault word (launch_reduce) — the sums and the fault word land
+// together, one stream sync brings both back with no device-to-host copy — copied into sums
+// unless the fault word is set.  n = 0: pass(nullptr), nothing read back.
+template <class Pass>
+int one_evaluation(m3d_icp* s, const double* T, bool open3d_init, Pass pass, int32_t* corr_idx, int n,
+                   double* sums, hipStream_t st) {
+  m3d_ctx* ctx = s->ctx;
+  int rc = n > 0 ? pin_ensure(ctx) : M3D_OK;
+  if (!rc) rc = icp_reset(s, T, open3d_init, st);
+  if (rc) return rc;
+  hipError_t e = enqueue_nn(s, 0, st);
+  if (e == hipSuccess) e = pass(n > 0 ? pin_read<double>(ctx, true) : nullptr);
+  if (e == hipSuccess && corr_idx != nullptr) e = launch_scatter_i32(s->corr, s->src->slot, s->src->n, corr_idx, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+  if (n == 0) return M3D_OK;
+  const volatile double* h = pin_read<double>(ctx, false);
+  for (int k = 0; k < n; ++k) sums[k] = h[k];
+  return defer_fault(ctx, (uint32_t)sums[n - 2], sums[n - 1] != 0.0);
+}
+}  // namespace
+}  // extern "C++"
+
 int m3d_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* init,
                 double max_dist, const m3d_icp_params* params, m3d_icp_result* out,
                 int32_t* corr_idx, void* stream) {
   if (!ctx) return M3D_ERR_INVALID;
   Touch tch{ctx, S(stream)};
   CHECK_ARG(ctx, out != nullptr, "null output");
-  m3d_icp* s = nullptr;
-  int rc = icp_create(ctx, src, tgt, max_dist, params, &s, true);
+  ScopedLoop s;
+  int rc = icp_create(ctx, src, tgt, max_dist, params, &s.s, true);
   if (rc) return rc;
   rc = m3d_icp_reset(s, init, stream);
-  // max_iteration + 1 evaluations, enqueued in
-  // growing chunks (4, 8, 16, …) with a look at the state's `done` between chunks — a converged
-  // loop (often after a handful of evaluations) then does not enqueue the remaining ~2 launches
-  // per evaluation that would only read `done` and return.  The evaluations that run are the
-  // same; only the early-exit launches are skipped.
-  if (!rc) {
-    const int32_t total = params->max_iteration + 1;
-    s->graph_off = true;  // a one-shot loop: no HIP graph capture (two equal chunks would trigger one)
-    int32_t left = total, chunk = 4;
-    while (!rc && left > 0) {
-      const int32_t k = std::min(chunk, left);
-      rc = m3d_icp_steps(s, k, stream);
-      left -= k;
-      chunk *= 2;
-      if (rc || left == 0) break;
-      int32_t done = 0;
-      hipError_t e = hipMemcpyAsync(&done, &s->state->done, sizeof(done), hipMemcpyDeviceToHost, S(stream));
-      if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-      if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-      if (done) break;
-    }
-  }
-  if (!rc) rc = m3d_icp_result_get(s, out, stream);
-  if (!rc && corr_idx && src->n > 0) {
-    hipError_t e = launch_scatter_i32(s->corr, s->src->slot, src->n, corr_idx, S(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-  }
-  m3d_icp_destroy(s);
-  return rc;
+  s->graph_off = true;  // a one-shot loop: no HIP graph capture (two equal chunks would trigger one)
+  // max_iteration + 1 evaluations
+  if (!rc) rc = run_chunked(s, params->max_iteration + 1, [&](int32_t k) { return m3d_icp_steps(s, k, stream); }, S(stream));
+  return rc ? rc : finish_run(s, out, corr_idx, S(stream));
 }
 
 int m3d_nn1(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* T_host,
@@ -1912,18 +1903,13 @@ int m3d_nn1(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const doub
   CHECK_ARG(ctx, src && tgt && (idx || src->n == 0), "invalid arguments");
   CHECK_ARG(ctx, max_dist > 0.0, "max_dist must be > 0");
   m3d_icp_params p{1e-6, 1e-6, 0, M3D_EST_POINT_TO_POINT, nn_method, 0};
-  m3d_icp* s = nullptr;
-  int rc = icp_create(ctx, src, tgt, max_dist, &p, &s, true);
+  ScopedLoop s;
+  const int rc = icp_create(ctx, src, tgt, max_dist, &p, &s.s, true);
   if (rc) return rc;
   hipStream_t st = S(stream);
-  rc = icp_reset(s, T_host, false, stream);  // the 1-NN of T·src for any T
-  hipError_t e = hipSuccess;
-  if (!rc) e = enqueue_nn(s, 0, st);
-  if (e == hipSuccess) e = launch_nn_finalize(s, idx, d2, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (!rc && e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-  m3d_icp_destroy(s);
-  return rc;
+  // the 1-NN of T·src for any T (no isIdentity() rule); the winners go straight to idx / d2
+  return one_evaluation(s, T_host, false, [&](double*) { return launch_nn_finalize(s, idx, d2, st); }, nullptr, 0,
+                        nullptr, st);
 }
 
 namespace {
@@ -1962,35 +1948,20 @@ int m3d_evaluate_registration(m3d_ctx* ctx, const m3d_cloud* src, const m3d_clou
     return M3D_OK;
   }
   m3d_icp_params p{1e-6, 1e-6, 0, M3D_EST_POINT_TO_POINT, nn_method, 0};
-  m3d_icp* s = nullptr;
-  int rc = icp_create(ctx, src, tgt, max_dist, &p, &s, true);
+  ScopedLoop s;
+  int rc = icp_create(ctx, src, tgt, max_dist, &p, &s.s, true);
   if (rc) return rc;
   // (after icp_create: its setup used the same arena and has been synchronised)
   if (ctx->tmp.reserve(eval_scratch_bytes(ns)) != hipSuccess)
-    rc = m3d_fail(ctx, M3D_ERR_OOM, "evaluation scratch");
-  if (!rc) rc = pin_ensure(ctx);
+    return m3d_fail(ctx, M3D_ERR_OOM, "evaluation scratch");
   double sums[16] = {};
-  // EvaluateRegistration: pcd = source; if (!T.isIdentity()) pcd.Transform(T)
-  if (!rc) rc = icp_reset(s, T_host, true, stream);
-  if (!rc) {
-    // the sums and the scan's fault word land together in the context's mapped pinned memory:
-    // one stream sync brings both back, with no device-to-host copy
-    hipError_t e = enqueue_nn(s, 0, st);
-    if (e == hipSuccess)
-      e = launch_eval(s, (flags & M3D_EVAL_INFORMATION) != 0, corr_idx, d2,
-                      reinterpret_cast<double*>(ctx->tmp.base), pin_read<double>(ctx, true), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-    const volatile double* h = pin_read<double>(ctx, false);
-    if (!rc)
-      for (int k = 0; k < 16; ++k) sums[k] = h[k];
-  }
-  m3d_icp_destroy(s);
+  // EvaluateRegistration: pcd = source; if (!T.isIdentity()) pcd.Transform(T).  The pass writes
+  // idx / d² in the caller's order itself: no scatter
+  rc = one_evaluation(s, T_host, true, [&](double* pin) {
+    return launch_eval(s, (flags & M3D_EVAL_INFORMATION) != 0, corr_idx, d2,
+                       reinterpret_cast<double*>(ctx->tmp.base), pin, st);
+  }, nullptr, 16, sums, st);
   if (rc) return rc;
-  if (sums[15] != 0.0)  // the grid scan's deferral fault word (m3d_icp_result_get)
-    return m3d_fail(ctx, M3D_ERR_HIP,
-                    "grid NN deferral list overflow (count " + std::to_string((uint32_t)sums[14]) +
-                        "): results since the last m3d_icp_reset are invalid");
   const int64_t matched = (int64_t)sums[0];
   out->num_correspondences = matched;
   out->fitness = (double)matched / (double)ns;
@@ -2096,34 +2067,19 @@ int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, con
     if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
     return M3D_OK;
   }
-  m3d_icp* s = nullptr;
-  rc = gicp_create(ctx, src, tgt, max_dist, 1e-6, 1e-6, 0, nn_method, &s);
+  ScopedLoop s;
+  rc = gicp_create(ctx, src, tgt, max_dist, 1e-6, 1e-6, 0, nn_method, &s.s);
   if (rc) return rc;
   GicpArrays ga;
-  rc = pin_ensure(ctx);
-  if (!rc) rc = gicp_setup(s, src_cov, tgt_cov, epsilon, st, &ga);
-  // pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and covariances
-  if (!rc) rc = icp_reset(s, T_host, true, stream);
-  double sums[kTermSlots] = {};
-  if (!rc) {
-    hipError_t e = enqueue_nn(s, 0, st);
-    if (e == hipSuccess) {
-      KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-      e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin_read<double>(ctx, true), true, st);
-    }
-    if (e == hipSuccess && corr_idx != nullptr) e = launch_scatter_i32(s->corr, s->src->slot, ns, corr_idx, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-    const volatile double* h = pin_read<double>(ctx, false);
-    if (!rc)
-      for (int k = 0; k < kTermSlots; ++k) sums[k] = h[k];
-  }
-  m3d_icp_destroy(s);
+  rc = gicp_setup(s, src_cov, tgt_cov, epsilon, st, &ga);
   if (rc) return rc;
-  if (sums[31] != 0.0)  // the grid scan's deferral fault word (m3d_icp_result_get)
-    return m3d_fail(ctx, M3D_ERR_HIP,
-                    "grid NN deferral list overflow (count " + std::to_string((uint32_t)sums[30]) +
-                        "): results since the last m3d_icp_reset are invalid");
+  double sums[kTermSlots] = {};
+  // pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and covariances
+  rc = one_evaluation(s, T_host, true, [&](double* pin) {
+    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+    return launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin, true, st);
+  }, corr_idx, kTermSlots, sums, st);
+  if (rc) return rc;
   for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
   return M3D_OK;
 }
@@ -2136,9 +2092,9 @@ int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const
   CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
   int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, params->nn_method, params->epsilon);
   if (rc) return rc;
-  m3d_icp* s = nullptr;
+  ScopedLoop s;
   rc = gicp_create(ctx, src, tgt, max_dist, params->relative_fitness, params->relative_rmse,
-                   params->max_iteration, params->nn_method, &s);
+                   params->max_iteration, params->nn_method, &s.s);
   if (rc) return rc;
   hipStream_t st = S(stream);
   const bool search = src->n > 0 && tgt->n > 0;  // else: no scan, zero sums, every source unmatched
@@ -2148,38 +2104,21 @@ int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const
   // max_iteration + 1 evaluations (NN scan, plane-to-plane terms + reduce, point-to-plane solve),
   // enqueued in growing chunks with a look at `done` in between, as m3d_icp_run; evaluations
   // after convergence are device no-ops
-  if (!rc) {
-    int32_t left = params->max_iteration + 1, chunk = 4;
-    while (!rc && left > 0) {
-      const int32_t k = std::min(chunk, left);
-      hipError_t e = hipSuccess;
-      for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
-        if (search) e = enqueue_nn(s, 0, st);
-        if (e == hipSuccess) {
-          KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-          e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, s->sums, false, st);
-        }
-        if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
+  auto step = [&](int32_t k) {
+    hipError_t e = hipSuccess;
+    for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
+      if (search) e = enqueue_nn(s, 0, st);
+      if (e == hipSuccess) {
+        KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+        e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, s->sums, false, st);
       }
-      if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, std::string("gicp step: ") + hipGetErrorString(e));
-      left -= k;
-      chunk *= 2;
-      if (rc || left == 0) break;
-      int32_t done = 0;
-      e = hipMemcpyAsync(&done, &s->state->done, sizeof(done), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-      if (done) break;
+      if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
     }
-  }
-  if (!rc) rc = m3d_icp_result_get(s, out, stream);
-  if (!rc && corr_idx && src->n > 0) {
-    hipError_t e = launch_scatter_i32(s->corr, s->src->slot, src->n, corr_idx, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-  }
+    return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("gicp step: ") + hipGetErrorString(e));
+  };
+  if (!rc) rc = run_chunked(s, params->max_iteration + 1, step, st);
+  if (!rc) rc = finish_run(s, out, corr_idx, st);
   if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
-  m3d_icp_destroy(s);
   return rc;
 }
 
@@ -2217,6 +2156,7 @@ struct NbrLists {
   double* d2 = nullptr;
   int32_t* cnt = nullptr;
   double* extra = nullptr;  // caller's n × extra_per_point doubles (FPFH: the SPFH rows)
+  char* scratch = nullptr;  // caller's scratch_bytes behind the lists (k-NN normals: the ladder's)
 };
 
 // the context's preprocessing buffer with at least `need` bytes (grown, never shrunk)
@@ -2235,18 +2175,17 @@ int prep_buffer(m3d_ctx* ctx, size_t need, char** out) {
   return M3D_OK;
 }
 
-int prep_lists(m3d_ctx* ctx, int64_t n, int k, int64_t extra_per_point, NbrLists* L) {
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t bi = up(sizeof(int32_t) * (size_t)n * k), bd = up(sizeof(double) * (size_t)n * k);
-  const size_t bc = up(sizeof(int32_t) * (size_t)n), be = up(sizeof(double) * (size_t)(n * extra_per_point));
+int prep_lists(m3d_ctx* ctx, int64_t n, int k, int64_t extra_per_point, NbrLists* L, size_t scratch_bytes = 0) {
+  Carve cv;
+  cv.add(&L->idx, (size_t)n * k);
+  cv.add(&L->d2, (size_t)n * k);
+  cv.add(&L->cnt, (size_t)n);
+  if (extra_per_point > 0) cv.add(&L->extra, (size_t)(n * extra_per_point));
+  if (scratch_bytes > 0) cv.add(&L->scratch, scratch_bytes);
   char* b = nullptr;
-  const int rc = prep_buffer(ctx, bi + bd + bc + be, &b);
-  if (rc) return rc;
-  L->idx = reinterpret_cast<int32_t*>(b);
-  L->d2 = reinterpret_cast<double*>(b + bi);
-  L->cnt = reinterpret_cast<int32_t*>(b + bi + bd);
-  L->extra = reinterpret_cast<double*>(b + bi + bd + bc);
-  return M3D_OK;
+  const int rc = prep_buffer(ctx, cv.bytes(), &b);
+  if (!rc) cv.place(b);
+  return rc;
 }
 
 // hybrid neighbourhoods of every point of `c` (grid cell = radius)
@@ -2375,18 +2314,13 @@ int m3d_estimate_normals_knn(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t k, do
   hipStream_t st = S(stream);
   Touch tch{ctx, st};
   // the k-NN lists and the ladder's scratch side by side in the context's preprocessing buffer
-  const size_t bi = tmp_align(sizeof(int32_t) * (size_t)n * k), bd = tmp_align(sizeof(double) * (size_t)n * k);
-  const size_t bc = tmp_align(sizeof(int32_t) * (size_t)n);
-  char* b = nullptr;
-  int rc = prep_buffer(ctx, bi + bd + bc + clean_scratch_bytes(n), &b);
+  NbrLists L;
+  int rc = prep_lists(ctx, n, k, 0, &L, clean_scratch_bytes(n));
   if (rc) return rc;
-  int32_t* idx = reinterpret_cast<int32_t*>(b);
-  double* d2 = reinterpret_cast<double*>(b + bi);
-  int32_t* cnt = reinterpret_cast<int32_t*>(b + bi + bd);
   std::string why;
-  hipError_t e = knn_search(ctx, cloud, k, idx, d2, cnt, b + bi + bd + bc, st, &why);
+  hipError_t e = knn_search(ctx, cloud, k, L.idx, L.d2, L.cnt, L.scratch, st, &why);
   if (e != hipSuccess) return clean_fail(ctx, "knn_search", e, why);
-  HIPX(ctx, launch_normals(cloud, idx, k, cnt, cloud->nrm64, normals_out, st));
+  HIPX(ctx, launch_normals(cloud, L.idx, k, L.cnt, cloud->nrm64, normals_out, st));
   HIPX(ctx, hipStreamSynchronize(st));
   return M3D_OK;
 }
@@ -2491,8 +2425,8 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
   HIPX(ctx, hipMemcpyAsync(hpass.data(), pass.p, 4 * H, hipMemcpyDeviceToHost, st));
   HIPX(ctx, hipStreamSynchronize(st));
   m3d_icp_params ip{1e-6, 1e-6, 0, M3D_EST_POINT_TO_POINT, M3D_NN_GRID, 0};
-  m3d_icp* s = nullptr;
-  rc = m3d_icp_create(ctx, src, tgt, p->max_correspondence_distance, &ip, &s);
+  ScopedLoop s;
+  rc = m3d_icp_create(ctx, src, tgt, p->max_correspondence_distance, &ip, &s.s);
   if (rc) return rc;
   // Validation of the checker-passing hypotheses in batches (grid.hip validate_kernel: one launch
   // evaluates a whole batch), each batch followed by Open3D's sequential selection over it:
@@ -2515,10 +2449,7 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
     if (!rc) rc = dev_alloc(ctx, &vpart.p, cap * nbq * 2);
     if (!rc) rc = dev_alloc(ctx, &vres.p, cap * 2);
     if (!rc) rc = dev_alloc(ctx, &vcorr.p, cap);
-    if (rc) {
-      m3d_icp_destroy(s);
-      return rc;
-    }
+    if (rc) return rc;
   }
   hipError_t e = hipSuccess;
   if (npass > 0)
@@ -2573,10 +2504,7 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
       }
     }
   }
-  if (e != hipSuccess) {
-    m3d_icp_destroy(s);
-    return m3d_fail(ctx, M3D_ERR_HIP, std::string("feature RANSAC: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, std::string("feature RANSAC: ") + hipGetErrorString(e));
   if (best >= 0) {
     e = hipMemcpyAsync(out->T, T.p + 16 * best, sizeof(double) * 16, hipMemcpyDeviceToHost, st);
     out->fitness = best_fit;
@@ -2592,7 +2520,6 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
-  m3d_icp_destroy(s);
   if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
   return M3D_OK;
 }

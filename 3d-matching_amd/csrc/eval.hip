@@ -10,12 +10,9 @@
 // The host assembles the 6×6 GᵀG of the rows G₁ = (0, z, −y, 1, 0, 0), G₂ = (−z, 0, x, 0, 1, 0),
 // G₃ = (y, −x, 0, 0, 0, 1) from them (api.cpp eval_information).
 //
-// Order of summation (fixed, so two runs — and the brute-force and grid scans, which leave the
-// same winners on the same Morton slots — give the same bits): a block holds 256 consecutive
-// slots; each wave adds its 64 lanes in an xor butterfly (32, 16, …, 1: every lane ends with the
-// same sum), the block adds its four wave sums in wave order into partials[block]; then one
-// block adds the partials as icp.hip reduce_kernel does — group g takes blocks g, g + 32, … in
-// increasing order, the 32 group sums are added in group order.  No floating-point atomics.
+// Order of summation: the loop's fixed order (icp.hip, "reduce"; nnkey.h block_partial per block
+// of 256 consecutive slots, launch_reduce over the block partials) — two runs, and the brute-force
+// and grid scans, which leave the same winners on the same Morton slots, give the same bits.
 #include "m3d_internal.h"
 #include "nnkey.h"
 
@@ -24,16 +21,6 @@ namespace m3d {
 constexpr int kEvalSlots = 16;
 constexpr int kEvalUsed = 11;
 constexpr int kEvalBlock = 256;
-constexpr int kEvalGroups = 32;
-// eval_reduce_kernel's output words past the sums: the grid scan's deferral count and fault word
-constexpr int kEvalDeferCount = 14;
-constexpr int kEvalDeferFault = 15;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += xor_lane_f64(v, o);
-  return v;
-}
 
 // ns > 0 and nt > 0 (launch_eval keeps the empty cases away: no slot 0 to load)
 __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const double* __restrict__ pcd64,
@@ -45,30 +32,21 @@ __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const double* __restri
                                                           const int32_t* __restrict__ slot, int with_info,
                                                           int32_t* __restrict__ idx, double* __restrict__ d2out,
                                                           double* __restrict__ partials) {
-  __shared__ double red[kEvalBlock / kWave][kEvalSlots];
-  const int64_t i0 = (int64_t)blockIdx.x * kEvalBlock + threadIdx.x;
-  const bool valid = i0 < ns;
-  const int64_t i = valid ? i0 : 0;
-  double Q[3];
-  q64_of(s->dT, pcd64 + 3 * i, Q);
-  int64_t gj;
-  double d;
-  winner_fp64(valid, valid ? (uint64_t)keys[i] : (uint64_t)kKeyNone,
-              valid ? __uint_as_float(near2[i]) : kInf, s, g, tgt64, 0, nt, src32[i], Q, gj, d);
-  const bool hit = valid && gj >= 0 && gj < nt;
-  if (valid) {
-    const int64_t o = slot != nullptr ? (int64_t)slot[i] : i;  // slot → the caller's source order
-    if (idx != nullptr) idx[o] = hit ? (int32_t)gj : -1;
-    if (d2out != nullptr) d2out[o] = hit ? d : INFINITY;
+  const SlotWinner w = slot_winner((int64_t)blockIdx.x * kEvalBlock + threadIdx.x, pcd64, src32, ns, tgt64, nt, g, s,
+                                   keys, near2);
+  if (w.valid) {
+    const int64_t o = slot != nullptr ? (int64_t)slot[w.i] : w.i;  // slot → the caller's source order
+    if (idx != nullptr) idx[o] = w.hit ? (int32_t)w.gj : -1;
+    if (d2out != nullptr) d2out[o] = w.hit ? w.d : INFINITY;
   }
   double v[kEvalUsed];
 #pragma unroll
   for (int k = 0; k < kEvalUsed; ++k) v[k] = 0.0;
-  if (hit) {
+  if (w.hit) {
     v[0] = 1.0;
-    v[1] = d;
+    v[1] = w.d;
     if (with_info) {
-      const double* q = tgt64 + 3 * gj;
+      const double* q = tgt64 + 3 * w.gj;
       const double x = q[0], y = q[1], z = q[2];
       v[2] = x;
       v[3] = y;
@@ -81,40 +59,7 @@ __global__ __launch_bounds__(kEvalBlock) void eval_kernel(const double* __restri
       v[10] = y * z;
     }
   }
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kEvalUsed; ++k) {
-    const double t = wave_sum(v[k]);
-    if (lane == 0) red[w][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kEvalSlots) {
-    double t = 0.0;
-    if (threadIdx.x < kEvalUsed)
-      for (int k = 0; k < kEvalBlock / kWave; ++k) t += red[k][threadIdx.x];
-    partials[(int64_t)blockIdx.x * kEvalSlots + threadIdx.x] = t;
-  }
-}
-
-// out[0 .. kEvalUsed) = the sums over the nblocks partials (nblocks = 0: zeros), and the deferral
-// header of the grid scan (hcnt null: zeros): result and fault word reach the host together
-__global__ __launch_bounds__(kEvalGroups * kEvalSlots) void eval_reduce_kernel(
-    const double* __restrict__ partials, int64_t nblocks, const uint32_t* __restrict__ hcnt,
-    double* __restrict__ out) {
-  __shared__ double red[kEvalGroups][kEvalSlots];
-  const int sl = threadIdx.x & (kEvalSlots - 1);
-  const int g = threadIdx.x / kEvalSlots;
-  double v = 0.0;
-  for (int64_t b = g; b < nblocks; b += kEvalGroups) v += partials[b * kEvalSlots + sl];
-  red[g][sl] = v;
-  __syncthreads();
-  if (threadIdx.x < kEvalSlots) {
-    double t = 0.0;
-    for (int k = 0; k < kEvalGroups; ++k) t += red[k][threadIdx.x];
-    if (threadIdx.x == kEvalDeferCount) t = hcnt != nullptr ? (double)hcnt[0] : 0.0;
-    if (threadIdx.x == kEvalDeferFault) t = hcnt != nullptr ? (double)hcnt[kDeferFault] : 0.0;
-    out[threadIdx.x] = t;
-  }
+  block_partial<kEvalSlots, kEvalUsed, kEvalBlock>(v, partials);
 }
 
 // no target: every source is unmatched
@@ -132,7 +77,9 @@ size_t eval_scratch_bytes(int64_t ns) {
 }
 
 // partials: eval_scratch_bytes(ns) bytes of device scratch; out: kEvalSlots doubles the host can
-// read after a stream sync (the context's mapped pinned memory).  The loop's NN scan for the
+// read after a stream sync (the context's mapped pinned memory): the sums over the partials (no
+// blocks: zeros) and, in its last two words, the grid scan's deferral count and fault word (brute
+// force: zeros) — result and fault word reach the host together.  The loop's NN scan for the
 // current transform must have been enqueued on st before.
 hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
                        double* out, hipStream_t st) {
@@ -142,8 +89,7 @@ hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2
     eval_kernel<<<(unsigned)nb, kEvalBlock, 0, st>>>(s->pcd64, s->src->xyz32, ns, s->tgt->xyz64, nt,
                                                     s->tgrid->dev, s->state, s->keys, s->near2,
                                                     s->src->slot, with_info, idx, d2, partials);
-  eval_reduce_kernel<<<1, kEvalGroups * kEvalSlots, 0, st>>>(partials, nb, s->hcnt, out);
-  return hipGetLastError();
+  return launch_reduce(partials, nb, kEvalSlots, out, nullptr, s->hcnt, st);
 }
 
 hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st) {

@@ -19,11 +19,9 @@
 // Slots: 0..20 JᵀJ (upper, row-major), 21..26 Jᵀr, 27 Σr², 28 count, 29 Σd² — icp.hip's
 // point-to-plane layout, so launch_icp_solve consumes the sums unchanged.
 //
-// Order of summation (eval.hip's, fixed: two runs, and the brute-force and grid scans, give the
-// same bits): a block holds 256 consecutive slots; each wave adds its 64 lanes in an xor
-// butterfly (32, 16, …, 1), the block adds its four wave sums in wave order into
-// partials[block]; one block then adds the partials — group g takes blocks g, g + 32, … in
-// increasing order, the 32 group sums are added in group order.  No floating-point atomics.
+// Order of summation: the loop's fixed order (icp.hip, "reduce"; nnkey.h block_partial per block
+// of 256 consecutive slots, launch_reduce over the block partials) — two runs, and the brute-force
+// and grid scans, give the same bits.
 //
 // Bytes per source the terms pass must move: its point read and written (24 + 24), its
 // covariance read and written (48 + 48), key, runner-up and correspondence (8 + 4 + 4), and the
@@ -34,11 +32,7 @@
 namespace m3d {
 
 constexpr int kGicpBlock = 256;
-constexpr int kGicpGroups = 32;
 constexpr int kGicpUsed = 30;
-// gicp_reduce_kernel's output words past the sums: the grid scan's deferral count and fault word
-constexpr int kGicpDeferCount = 30;
-constexpr int kGicpDeferFault = 31;
 
 // upper triangle of Rx·diag(ε, 1, 1)·Rxᵀ for the normal (nx, ny, nz)
 __device__ __forceinline__ void cov6_of_normal(double nx, double ny, double nz, double eps, double (&C)[6]) {
@@ -100,12 +94,6 @@ __global__ __launch_bounds__(256) void cov_pack_kernel(const double* __restrict_
   o[5] = c[8];
 }
 
-__device__ __forceinline__ double gicp_wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += xor_lane_f64(v, o);
-  return v;
-}
-
 // (J₀[:, a])·g for a 3-vector g: a < 3 the column (e_a × vs), i.e. (vs × g)_a; a ≥ 3 the unit column
 template <int a>
 __device__ __forceinline__ double j0_dot(double x, double y, double z, const double (&g)[3]) {
@@ -143,12 +131,11 @@ __global__ __launch_bounds__(kGicpBlock) void gicp_terms_kernel(
     const IcpState* __restrict__ s, const int64_t* __restrict__ keys, const uint32_t* __restrict__ near2,
     int32_t* __restrict__ corr, double* __restrict__ partials) {
   if (s->done) return;
-  __shared__ double red[kGicpBlock / kWave][kTermSlots];
-  const int64_t i0 = (int64_t)blockIdx.x * kGicpBlock + threadIdx.x;
-  const bool valid = i0 < ns;
-  const int64_t i = valid ? i0 : 0;
-  double Q[3];
-  q64_of(s->dT, pcd64 + 3 * i, Q);
+  const SlotWinner sw = slot_winner((int64_t)blockIdx.x * kGicpBlock + threadIdx.x, pcd64, src32, ns, tgt64, nt, g, s,
+                                    keys, near2);
+  const bool valid = sw.valid, hit = sw.hit;
+  const int64_t i = sw.i, gj = sw.gj;
+  const double(&Q)[3] = sw.Q;
   // Cs ← R·Cs·Rᵀ: A = R·Cs, then the upper triangle of A·Rᵀ
   double cs[6], Cs[6];
 #pragma unroll
@@ -174,11 +161,6 @@ __global__ __launch_bounds__(kGicpBlock) void gicp_terms_kernel(
 #pragma unroll
     for (int k = 0; k < 6; ++k) cov_s[6 * i + k] = Cs[k];
   }
-  int64_t gj;
-  double d2;
-  winner_fp64(valid, valid ? (uint64_t)keys[i] : (uint64_t)kKeyNone,
-              valid ? __uint_as_float(near2[i]) : kInf, s, g, tgt64, 0, nt, src32[i], Q, gj, d2);
-  const bool hit = valid && gj >= 0 && gj < nt;
   if (valid) corr[i] = hit ? (int32_t)gj : -1;
   double v[kGicpUsed];
 #pragma unroll
@@ -208,44 +190,9 @@ __global__ __launch_bounds__(kGicpBlock) void gicp_terms_kernel(
     jtj_rows<0>(v, x, y, z, G, w);
     v[27] = (d[0] * w[0] + d[1] * w[1]) + d[2] * w[2];
     v[28] = 1.0;
-    v[29] = d2;
+    v[29] = sw.d;
   }
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kGicpUsed; ++k) {
-    const double t = gicp_wave_sum(v[k]);
-    if (lane == 0) red[wv][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < kTermSlots) {
-    double t = 0.0;
-    if (threadIdx.x < kGicpUsed)
-      for (int k = 0; k < kGicpBlock / kWave; ++k) t += red[k][threadIdx.x];
-    partials[(int64_t)blockIdx.x * kTermSlots + threadIdx.x] = t;
-  }
-}
-
-// sums[0 .. 30) = the sums over the nblocks partials (nblocks = 0: zeros); sums[30], sums[31]:
-// the deferral header of the grid scan (hcnt null: zeros), so that a one-evaluation call gets its
-// result and the fault word in one read.  The solve reads slots 0..29 only.
-__global__ __launch_bounds__(kGicpGroups * kTermSlots) void gicp_reduce_kernel(
-    const double* __restrict__ partials, int64_t nblocks, const uint32_t* __restrict__ hcnt,
-    double* __restrict__ sums, const IcpState* __restrict__ s) {
-  if (s->done) return;
-  __shared__ double red[kGicpGroups][kTermSlots];
-  const int sl = threadIdx.x & (kTermSlots - 1);
-  const int gr = threadIdx.x / kTermSlots;
-  double v = 0.0;
-  for (int64_t b = gr; b < nblocks; b += kGicpGroups) v += partials[b * kTermSlots + sl];
-  red[gr][sl] = v;
-  __syncthreads();
-  if (threadIdx.x < kTermSlots) {
-    double t = 0.0;
-    for (int k = 0; k < kGicpGroups; ++k) t += red[k][threadIdx.x];
-    if (threadIdx.x == kGicpDeferCount) t = hcnt != nullptr ? (double)hcnt[0] : 0.0;
-    if (threadIdx.x == kGicpDeferFault) t = hcnt != nullptr ? (double)hcnt[kDeferFault] : 0.0;
-    sums[threadIdx.x] = t;
-  }
+  block_partial<kTermSlots, kGicpUsed, kGicpBlock>(v, partials);
 }
 
 int64_t gicp_blocks(int64_t ns) { return ns > 0 ? (ns + kGicpBlock - 1) / kGicpBlock : 0; }
@@ -266,8 +213,10 @@ hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, d
 // The plane-to-plane terms of the loop's current evaluation (its NN scan must have been enqueued
 // on st) and their reduction into sums (kTermSlots doubles).  cov_s: the loop's source covariances
 // in slot order, 6 per point, rotated in place; cov_t: the target's in index order; partials:
-// gicp_blocks(ns) × kTermSlots doubles.  with_defer: sums[30 / 31] carry the grid scan's deferral
-// count and fault word.
+// gicp_blocks(ns) × kTermSlots doubles.  sums[0 .. 30) = the sums over the partials (no blocks:
+// zeros), all the solve reads; with_defer: the last two words carry the grid scan's deferral count
+// and fault word (else, and for brute force, zeros), so that a one-evaluation call gets its result
+// and the fault word in one read.
 hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
                              double* sums, bool with_defer, hipStream_t st) {
   const int64_t ns = s->src->n, nt = s->tgt->n;
@@ -276,9 +225,7 @@ hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_
     gicp_terms_kernel<<<(unsigned)nb, kGicpBlock, 0, st>>>(s->pcd64, cov_s, s->src->xyz32, ns, s->tgt->xyz64,
                                                           cov_t, nt, s->tgrid->dev, s->state, s->keys,
                                                           s->near2, s->corr, partials);
-  gicp_reduce_kernel<<<1, kGicpGroups * kTermSlots, 0, st>>>(partials, nb, with_defer ? s->hcnt : nullptr, sums,
-                                                             s->state);
-  return hipGetLastError();
+  return launch_reduce(partials, nb, kTermSlots, sums, s->state, with_defer ? s->hcnt : nullptr, st);
 }
 
 }  // namespace m3d

@@ -580,29 +580,44 @@ __global__ __launch_bounds__(256) void shard_claim_kernel(int64_t ns, const IcpS
 }
 
 // ------------------------------------------------------------------------------- reduce
-// 32 groups × 32 slots: group g sums blocks g, g+32, … (independent loads in flight), then the
-// 32 group sums are added in group order — a fixed order, so the result is deterministic.
+// Order of summation of every pass over a loop's source slots (the ICP terms, eval.hip, gicp.hip).
+// It is fixed, so two runs — and the brute-force and grid scans, which leave the same winners on
+// the same Morton slots — give the same bits (tests/test_gpu_sum_order.py restates it in numpy):
+// a block holds consecutive slots and writes one row of partials (eval.hip, gicp.hip: 256 slots,
+// nnkey.h block_partial — each wave adds its 64 lanes in an xor butterfly 32, 16, …, 1, the block
+// adds its four wave sums in wave order; the ICP terms: terms_block); then reduce_kernel, one
+// block of 32 groups × kSlots columns: group g adds rows g, g + 32, … in increasing order
+// (independent loads in flight), and the 32 group sums are added in group order.  No
+// floating-point atomics.
+// s: a loop state whose `done` skips the kernel, or null.  hcnt: the grid scan's deferral header
+// (m3d_icp::hcnt), or null; given, the LAST TWO words of sums are overwritten with its count and
+// its fault word, so that a one-evaluation call reads its result and the fault word together
+// (those columns of the partials are padding: zeros).
 constexpr int kReduceGroups = 32;
+template <int kSlots>
 __device__ __forceinline__ double group_sum(const double* __restrict__ partials, int64_t nblocks,
                                             int g, int slot) {
   double v = 0.0;
 #pragma unroll 4
-  for (int64_t b = g; b < nblocks; b += kReduceGroups) v += partials[b * kTermSlots + slot];
+  for (int64_t b = g; b < nblocks; b += kReduceGroups) v += partials[b * kSlots + slot];
   return v;
 }
 
-__global__ __launch_bounds__(kReduceGroups * kTermSlots) void reduce_kernel(
+template <int kSlots>
+__global__ __launch_bounds__(kReduceGroups * kSlots) void reduce_kernel(
     const double* __restrict__ partials, int64_t nblocks, double* __restrict__ sums,
-    const IcpState* __restrict__ s) {
+    const IcpState* __restrict__ s, const uint32_t* __restrict__ hcnt) {
   if (s != nullptr && s->done) return;
-  __shared__ double red[kReduceGroups][kTermSlots];
-  const int slot = threadIdx.x & (kTermSlots - 1);
-  const int g = threadIdx.x / kTermSlots;
-  red[g][slot] = group_sum(partials, nblocks, g, slot);
+  __shared__ double red[kReduceGroups][kSlots];
+  const int slot = threadIdx.x & (kSlots - 1);
+  const int g = threadIdx.x / kSlots;
+  red[g][slot] = group_sum<kSlots>(partials, nblocks, g, slot);
   __syncthreads();
-  if (threadIdx.x < kTermSlots) {
+  if (threadIdx.x < kSlots) {
     double t = 0.0;
     for (int k = 0; k < kReduceGroups; ++k) t += red[k][threadIdx.x];
+    if (hcnt != nullptr && threadIdx.x == kSlots - 2) t = (double)hcnt[0];
+    if (hcnt != nullptr && threadIdx.x == kSlots - 1) t = (double)hcnt[kDeferFault];
     sums[threadIdx.x] = t;
   }
 }
@@ -966,19 +981,12 @@ __global__ __launch_bounds__(256) void nn_finalize_kernel(const double* __restri
                                                           const int32_t* __restrict__ slot,
                                                           int32_t* __restrict__ idx,
                                                           double* __restrict__ d2out) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool valid = i0 < ns;
-  const int64_t i = valid ? i0 : 0;
-  double Q[3];
-  q64_of(s->dT, pcd64 + 3 * i, Q);
-  int64_t gj;
-  double d;
-  winner_fp64(valid, valid ? (uint64_t)keys[i] : (uint64_t)kKeyNone,
-              valid ? __uint_as_float(near2[i]) : kInf, s, g, tgt64, 0, nt, src32[i], Q, gj, d);
-  if (!valid) return;
-  const int64_t o = slot != nullptr ? (int64_t)slot[i] : i;  // slot → the caller's source order
-  idx[o] = (int32_t)gj;
-  if (d2out != nullptr) d2out[o] = gj >= 0 ? d : INFINITY;
+  const SlotWinner w = slot_winner((int64_t)blockIdx.x * 256 + threadIdx.x, pcd64, src32, ns, tgt64, nt, g, s, keys,
+                                   near2);
+  if (!w.valid) return;
+  const int64_t o = slot != nullptr ? (int64_t)slot[w.i] : w.i;  // slot → the caller's source order
+  idx[o] = (int32_t)w.gj;
+  if (d2out != nullptr) d2out[o] = w.gj >= 0 ? w.d : INFINITY;
 }
 
 __global__ void scatter_i32_kernel(const int32_t* __restrict__ v, const int32_t* __restrict__ slot,
@@ -1288,11 +1296,22 @@ static void launch_reduce_groups(const m3d_icp* s, double* sums, int do_solve, h
   });
 }
 
-hipError_t launch_icp_reduce(const m3d_icp* s, double* sums, hipStream_t st) {
-  if (s->nblocks > 256)  // group g's first row is block g's: rows 0..31 exist
-    launch_reduce_groups(s, sums, 0, st);
+// out[0 .. slots) = the sums of the `rows` rows of `slots` (16 or 32) columns in partials
+// (reduce_kernel: rows = 0 gives zeros)
+hipError_t launch_reduce(const double* partials, int64_t rows, int slots, double* out, const IcpState* s,
+                         const uint32_t* hcnt, hipStream_t st) {
+  if (slots == 16)
+    reduce_kernel<16><<<1, kReduceGroups * 16, 0, st>>>(partials, rows, out, s, hcnt);
+  else if (slots == kTermSlots)
+    reduce_kernel<kTermSlots><<<1, kReduceGroups * kTermSlots, 0, st>>>(partials, rows, out, s, hcnt);
   else
-    reduce_kernel<<<1, kReduceGroups * kTermSlots, 0, st>>>(s->partials, s->nblocks, sums, s->state);
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_icp_reduce(const m3d_icp* s, double* sums, hipStream_t st) {
+  if (s->nblocks <= 256) return launch_reduce(s->partials, s->nblocks, kTermSlots, sums, s->state, nullptr, st);
+  launch_reduce_groups(s, sums, 0, st);  // group g's first row is block g's: rows 0..31 exist
   return hipGetLastError();
 }
 

@@ -204,27 +204,33 @@ hipError_t dev_malloc(T** p, size_t bytes) {
 }
 
 // Several device arrays in ONE allocation (256-B aligned pieces): the setup paths make one
-// hipMalloc per object instead of one per array, and the owner one hipFree.
+// hipMalloc per object instead of one per array, and the owner one hipFree.  Or the layout alone:
+// bytes(), then place() onto memory the caller already has (a context's arena or buffer).
 struct Carve {
   std::vector<std::pair<void**, size_t>> parts;
   template <class T>
   void add(T** p, size_t count) {
     parts.emplace_back(reinterpret_cast<void**>(p), tmp_align(sizeof(T) * std::max<size_t>(count, 1)));
   }
-  hipError_t alloc(void** block, size_t* bytes, hipStream_t st = nullptr) {
+  size_t bytes() const {
     size_t tot = 0;
     for (auto& q : parts) tot += q.second;
-    void* b = nullptr;
-    const hipError_t e = block_alloc(&b, std::max<size_t>(tot, 1), st);
-    *block = e == hipSuccess ? b : nullptr;
-    *bytes = e == hipSuccess ? tot : 0;
-    if (e != hipSuccess) return e;
+    return tot;
+  }
+  void place(void* base) const {
     size_t o = 0;
     for (auto& q : parts) {
-      *q.first = static_cast<char*>(b) + o;
+      *q.first = static_cast<char*>(base) + o;
       o += q.second;
     }
-    return hipSuccess;
+  }
+  hipError_t alloc(void** block, size_t* bytes_out, hipStream_t st = nullptr) {
+    void* b = nullptr;
+    const hipError_t e = block_alloc(&b, std::max<size_t>(bytes(), 1), st);
+    *block = e == hipSuccess ? b : nullptr;
+    *bytes_out = e == hipSuccess ? bytes() : 0;
+    if (e == hipSuccess) place(b);
+    return e;
   }
 };
 // whether p lies inside [block, block + bytes) (the arrays a Carve block holds)
@@ -481,8 +487,34 @@ hipError_t launch_icp_keyinit(const m3d_icp* s, int64_t shard_offset, hipStream_
                               int64_t q1 = -1);
 hipError_t launch_icp_nn(const m3d_icp* s, int64_t shard_offset, bool self_seed, hipStream_t st,
                          int64_t q0 = 0, int64_t q1 = -1);
+hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st);
+hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st);
+hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st);
+hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStream_t st);
+int64_t terms_blocks(int64_t ns);
+// the fixed-order sum of `rows` rows of `slots` (16 or 32) doubles → out[0 .. slots) (icp.hip
+// reduce_kernel).  s: a loop state whose `done` skips the kernel, or null; hcnt: the grid scan's
+// deferral header, or null — given, the last two words of out are its count and its fault word
+hipError_t launch_reduce(const double* partials, int64_t rows, int slots, double* out, const IcpState* s,
+                         const uint32_t* hcnt, hipStream_t st);
 hipError_t launch_icp_reduce(const m3d_icp* s, double* sums, hipStream_t st);
 hipError_t launch_icp_reduce_solve(const m3d_icp* s, hipStream_t st);
+// eval.hip: the evaluation pass after a loop's NN scan; out[0 .. 16) receives the sums
+// (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz) and, in its last two words, the deferral
+// count / fault
+size_t eval_scratch_bytes(int64_t ns);
+hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
+                       double* out, hipStream_t st);
+hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st);
+// gicp.hip: covariances (6 doubles per point: the upper triangle) and the plane-to-plane terms pass
+// after a loop's NN scan; sums[0 .. 30) in the point-to-plane slot layout, the last two words the
+// deferral count / fault when with_defer
+int64_t gicp_blocks(int64_t ns);
+hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, double* out, int width,
+                                   hipStream_t st);
+hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, double* out6, hipStream_t st);
+hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
+                             double* sums, bool with_defer, hipStream_t st);
 // claim/dmin: target-shard exchange results (m3d_icp_shard_claim), or null
 hipError_t launch_icp_terms_mode(const m3d_icp* s, int64_t off, const int32_t* claim,
                                  const int64_t* dmin, hipStream_t st);

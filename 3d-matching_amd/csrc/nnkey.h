@@ -398,6 +398,60 @@ __device__ __forceinline__ void winner_fp64(bool valid, uint64_t k1, float near2
   }
 }
 
+// The winner of a loop's source slot after its NN scan, as every pass that consumes a whole scan
+// on one device opens (icp.hip nn_finalize_kernel, eval.hip eval_kernel, gicp.hip
+// gicp_terms_kernel): the same expressions in the same order, hence the same bits in all three.
+// i0 = the thread's slot; every lane of the wave calls it, a lane past ns (valid false) with
+// slot 0's loads.  Q = dT·pcd64[i], gj / d = winner_fp64's winner and its fp64 d², hit = the slot
+// has a target inside the radius.  ns > 0.
+struct SlotWinner {
+  bool valid, hit;
+  int64_t i, gj;
+  double Q[3], d;
+};
+__device__ __forceinline__ SlotWinner slot_winner(int64_t i0, const double* __restrict__ pcd64,
+                                                  const float4* __restrict__ src32, int64_t ns,
+                                                  const double* __restrict__ tgt64, int64_t nt, const GridDev& g,
+                                                  const IcpState* __restrict__ s,
+                                                  const int64_t* __restrict__ keys,
+                                                  const uint32_t* __restrict__ near2) {
+  SlotWinner w;
+  w.valid = i0 < ns;
+  w.i = w.valid ? i0 : 0;
+  q64_of(s->dT, pcd64 + 3 * w.i, w.Q);
+  winner_fp64(w.valid, w.valid ? (uint64_t)keys[w.i] : (uint64_t)kKeyNone,
+              w.valid ? __uint_as_float(near2[w.i]) : kInf, s, g, tgt64, 0, nt, src32[w.i], w.Q, w.gj, w.d);
+  w.hit = w.valid && w.gj >= 0 && w.gj < nt;
+  return w;
+}
+
+// One block's share of a fixed-order sum (the order: icp.hip, "reduce"): thread t holds the kUsed
+// values v of slot blockIdx.x·kBlock + t; each wave adds its 64 lanes in an xor butterfly (32,
+// 16, …, 1: every lane ends with the same sum), then the wave sums are added in wave order into
+// partials[blockIdx.x·kSlots + k].  Columns kUsed .. kSlots are written as 0.0.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) v += xor_lane_f64(v, o);
+  return v;
+}
+template <int kSlots, int kUsed, int kBlock>
+__device__ __forceinline__ void block_partial(const double (&v)[kUsed], double* __restrict__ partials) {
+  __shared__ double red[kBlock / kWave][kSlots];
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+#pragma unroll
+  for (int k = 0; k < kUsed; ++k) {
+    const double t = wave_sum(v[k]);
+    if (lane == 0) red[w][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSlots) {
+    double t = 0.0;
+    if (threadIdx.x < kUsed)
+      for (int k = 0; k < kBlock / kWave; ++k) t += red[k][threadIdx.x];
+    partials[(int64_t)blockIdx.x * kSlots + threadIdx.x] = t;
+  }
+}
+
 // Distance-bound pseudo key for a query whose previous winner lies in another shard: d64o ≥ the
 // previous global winner's fp64 d² (rounded up to fp32); see seed_key.
 __device__ __forceinline__ int64_t bound_key(const IcpState* __restrict__ s, float d64o, float4 p,
