@@ -2373,6 +2373,61 @@ int m3d_remove_radius_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_p
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- plane segmentation
+// plane.hip; scratch from the context's arena (m3d_plane_score only enqueues: the arena orders
+// calls on different streams on the device)
+int32_t m3d_plane_chunk(void) { return kPlaneChunk; }
+
+int m3d_plane_score(m3d_ctx* ctx, const m3d_cloud* cloud, const double* planes, int64_t H,
+                    double distance_threshold, int32_t* counts, double* err, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && H >= 0 && H < ((int64_t)1 << 31), "invalid arguments");
+  if (H == 0 || cloud->n == 0) return M3D_OK;  // nothing to score: no array is touched
+  CHECK_ARG(ctx, planes && counts, "null device pointer");
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  Arena a(ctx, st);
+  const size_t o = a.take(plane_score_scratch_bytes(cloud->n, H));
+  int rc = a.commit();
+  if (rc) return rc;
+  HIPX(ctx, plane_score(cloud, planes, H, distance_threshold, counts, err, a.at<char>(o), st));
+  return M3D_OK;
+}
+
+int m3d_segment_plane(m3d_ctx* ctx, const m3d_cloud* cloud, const m3d_plane_params* p, const int32_t* samples,
+                      m3d_plane_result* out, int32_t* inliers_out, int32_t* counts_out, double* err_out,
+                      void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && p && out, "invalid arguments");
+  CHECK_ARG(ctx, p->ransac_n >= 3, "ransac_n should be set to higher than or equal to 3.");
+  CHECK_ARG(ctx, p->ransac_n <= 32, "ransac_n <= 32");
+  CHECK_ARG(ctx, p->probability > 0.0 && p->probability <= 1.0, "Probability must be > 0 and <= 1.0");
+  CHECK_ARG(ctx, p->num_iterations >= 0, "num_iterations >= 0");
+  CHECK_ARG(ctx, std::isfinite(p->distance_threshold) && p->distance_threshold >= 0.0,
+            "distance_threshold must be finite and >= 0");
+  CHECK_ARG(ctx, cloud->n >= p->ransac_n, "There must be at least 'ransac_n' points.");
+  CHECK_ARG(ctx, inliers_out != nullptr, "null device pointer");
+  *out = m3d_plane_result{};
+  out->best_index = -1;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const int batch = segment_plane_batch(cloud->n, p);
+  Arena a(ctx, st);
+  const size_t o = a.take(segment_plane_scratch_bytes(cloud->n, batch));
+  int rc = a.commit();
+  if (rc) return rc;
+  int bad = 0;
+  HIPX(ctx, segment_plane(cloud, p, batch, samples, out, inliers_out, counts_out, err_out, a.at<char>(o), st, &bad));
+  if (bad) {
+    *out = m3d_plane_result{};
+    out->best_index = -1;
+    return m3d_fail(ctx, M3D_ERR_INVALID, "segment_plane: a sample index is outside [0, n)");
+  }
+  return M3D_OK;
+}
+
 // ------------------------------------------------------------------------------- feature matching
 int m3d_feature_correspondences(m3d_ctx* ctx, const double* f_src, int64_t ns, const double* f_tgt,
                                 int64_t nt, int32_t dim, int32_t mutual_filter,

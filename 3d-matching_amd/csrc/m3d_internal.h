@@ -608,4 +608,19 @@ hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double 
 hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius,
                            int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
                            hipStream_t st);
+// plane segmentation (plane.hip).  kPlaneChunk points per chunk of the score kernel (a constant of
+// the library: a plane's err bits depend on n alone); a launch scores at most plane_batch_cap(n)
+// planes (its per-chunk partials stay within a fixed budget).
+constexpr int kPlaneChunk = 512;  // (1024 and 256 timed beside it: docs/EXPERIMENTS.md)
+int64_t plane_batch_cap(int64_t n);
+size_t plane_score_scratch_bytes(int64_t n, int64_t H);
+// enqueue only; scratch: plane_score_scratch_bytes(n, H) bytes; n == 0 or H == 0: no launch
+hipError_t plane_score(const m3d_cloud* c, const double* planes, int64_t H, double thr, int32_t* counts,
+                       double* err, void* scratch, hipStream_t st);
+int segment_plane_batch(int64_t n, const m3d_plane_params* p);  // the batch the loop runs with
+size_t segment_plane_scratch_bytes(int64_t n, int batch);
+// the whole call (synchronous); *bad_sample: a supplied index was outside [0, n)
+hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batch, const int32_t* samples,
+                         m3d_plane_result* out, int32_t* inliers_out, int32_t* counts_out, double* err_out,
+                         void* scratch, hipStream_t st, int* bad_sample);
 }  // namespace m3d

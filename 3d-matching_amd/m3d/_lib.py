@@ -32,6 +32,7 @@ DT_I32, DT_I64, DT_F64 = 0, 1, 2
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
 NN_METHODS = {"brute": NN_BRUTE, "grid": NN_GRID}
 ABI_VERSION = 13
+PLANE_CHUNK = 512  # plane.hip kPlaneChunk (m3d_plane_chunk): points per chunk of the score kernel's partial sums
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -84,6 +85,16 @@ class GicpParams(C.Structure):
 
 class OutlierStats(C.Structure):
     _fields_ = [("kept", i64), ("valid", i64), ("mean", dbl), ("std_dev", dbl), ("threshold", dbl)]
+
+
+class PlaneParams(C.Structure):
+    _fields_ = [("distance_threshold", dbl), ("probability", dbl), ("seed", u64), ("ransac_n", i32),
+                ("num_iterations", i32), ("batch", i32), ("reserved", i32)]
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [("plane", dbl * 4), ("ransac_plane", dbl * 4), ("num_inliers", i64), ("best_index", i64),
+                ("best_count", i64), ("evaluated", i64), ("iterations", i64), ("best_rmse", dbl)]
 
 
 # name -> (restype, argtypes)
@@ -150,6 +161,9 @@ SIGNATURES = {
     "m3d_remove_statistical_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64),
                                                  C.POINTER(OutlierStats), vp, vp]),
     "m3d_remove_radius_outlier": (C.c_int, [vp, vp, i32, dbl, vp, C.POINTER(i64), vp, vp]),
+    "m3d_segment_plane": (C.c_int, [vp, vp, C.POINTER(PlaneParams), vp, C.POINTER(PlaneResult), vp, vp, vp, vp]),
+    "m3d_plane_score": (C.c_int, [vp, vp, vp, i64, dbl, vp, vp, vp]),
+    "m3d_plane_chunk": (i32, []),
     "m3d_feature_correspondences": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, dbl, vp,
                                               C.POINTER(i64), vp]),
     "m3d_ransac_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FeatureRansacParams),

@@ -13,6 +13,7 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``KDTreeFlann.search_knn_vector_3d`` (not in the path)   | ``knn_search`` (every point)      |
 | ``pcd.remove_statistical_outlier(nb, ratio)`` (users)    | ``remove_statistical_outlier``    |
 | ``pcd.remove_radius_outlier(nb, r)`` (users)             | ``remove_radius_outlier``         |
+| ``pcd.segment_plane(thr, ransac_n, iterations)`` (users) | ``segment_plane``, ``plane_score`` |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -141,6 +142,91 @@ def remove_radius_outlier(points, nb_points: int, radius: float, with_counts: bo
                                                 ptr(cnt), stream_handle()), "remove_radius_outlier")
     kept = ind[: m.value].cpu().numpy()
     return (kept, cnt[: c.n].cpu().numpy()) if with_counts else kept
+
+
+PLANE_CHUNK = _lib.PLANE_CHUNK  # points per chunk of the plane score kernel's partial sums
+
+
+@dataclass
+class PlaneOutcome:
+    """What ``segment_plane`` found besides the refitted plane and the inliers."""
+    ransac_plane: np.ndarray  # the best hypothesis's own plane: the inliers are tested against it
+    best_index: int           # its hypothesis number (−1: none)
+    best_count: int
+    best_rmse: float
+    evaluated: int            # non-degenerate hypotheses evaluated
+    iterations: int           # the hypothesis number at which the loop left
+    counts: np.ndarray        # per hypothesis, −1 = degenerate or not reached
+    err: np.ndarray           # Σ dist² over its inliers (−1 on the same rows)
+
+
+def _check_plane_args(distance_threshold, ransac_n, num_iterations, probability):
+    if not (0.0 < float(probability) <= 1.0):
+        raise ValueError("Probability must be > 0 and <= 1.0")
+    if int(ransac_n) < 3:
+        raise ValueError("ransac_n should be set to higher than or equal to 3.")
+    if int(ransac_n) > 32:
+        raise ValueError("segment_plane: ransac_n <= 32")
+    if int(num_iterations) < 0:
+        raise ValueError("segment_plane: num_iterations >= 0")
+    if not (np.isfinite(float(distance_threshold)) and float(distance_threshold) >= 0.0):
+        raise ValueError("segment_plane: distance_threshold must be finite and >= 0")
+
+
+def segment_plane(points, distance_threshold: float = 0.01, ransac_n: int = 3, num_iterations: int = 100,
+                  probability: float = 0.99999999, *, seed: int = 0, samples=None, batch: int = 0,
+                  with_details: bool = False):
+    """PointCloud::SegmentPlane on the device (m3d_segment_plane; the contract is in include/m3d.h)
+    → (plane_model (4,) float64, inliers int64 ascending); ``with_details=True`` adds a
+    ``PlaneOutcome``.  ``samples`` (num_iterations × ransac_n indices) replaces the native counter
+    sampler (``seed``); ``batch`` (hypotheses per device batch, 0 = automatic) changes no result."""
+    _check_plane_args(distance_threshold, ransac_n, num_iterations, probability)
+    n_pts = points.n if isinstance(points, Cloud) else len(points)
+    if n_pts < int(ransac_n):
+        raise ValueError("There must be at least 'ransac_n' points.")
+    smp = None
+    if samples is not None:
+        smp = np.ascontiguousarray(np.asarray(samples, np.int64).reshape(-1, int(ransac_n)))
+        if smp.shape[0] != int(num_iterations):
+            raise ValueError("segment_plane: samples must be num_iterations × ransac_n")
+        if smp.size and (smp.min() < -(1 << 31) or smp.max() >= (1 << 31)):
+            raise ValueError("segment_plane: a sample index is outside [0, n)")
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    H = int(num_iterations)
+    p = _lib.PlaneParams(float(distance_threshold), float(probability), int(seed) & ((1 << 64) - 1),
+                         int(ransac_n), H, int(batch), 0)
+    r = _lib.PlaneResult()
+    smp_dev = None if smp is None else to_device(smp.astype(np.int32), dtype="int32", shape_tail=(int(ransac_n),))
+    inl = device_empty((max(c.n, 1),), torch.int32)
+    cnt = device_empty((max(H, 1),), torch.int32) if with_details else None
+    err = device_empty((max(H, 1),), torch.float64) if with_details else None
+    ctx.check(ctx.lib.m3d_segment_plane(ctx.h, c.h, C.byref(p), ptr(smp_dev), C.byref(r), ptr(inl), ptr(cnt),
+                                        ptr(err), stream_handle()), "segment_plane")
+    plane = np.array(r.plane[:], np.float64)
+    inliers = inl[: int(r.num_inliers)].cpu().numpy().astype(np.int64)
+    if not with_details:
+        return plane, inliers
+    return plane, inliers, PlaneOutcome(np.array(r.ransac_plane[:], np.float64), int(r.best_index),
+                                        int(r.best_count), float(r.best_rmse), int(r.evaluated),
+                                        int(r.iterations), cnt[:H].cpu().numpy(), err[:H].cpu().numpy())
+
+
+def plane_score(points, planes, distance_threshold: float):
+    """For each of the H planes (H×4: a, b, c, d) the number of points with
+    |((a·x + b·y) + c·z) + d| < distance_threshold and the sum of their squared distances
+    (m3d_plane_score) → (counts int32 H, err float64 H); an empty cloud gives zeros."""
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    pl = to_device(np.asarray(planes, np.float64).reshape(-1, 4), shape_tail=(4,))
+    H = pl.shape[0]
+    cnt = torch.zeros((max(H, 1),), dtype=torch.int32, device=pl.device)
+    err = torch.zeros((max(H, 1),), dtype=torch.float64, device=pl.device)
+    ctx.check(ctx.lib.m3d_plane_score(ctx.h, c.h, ptr(pl), H, float(distance_threshold), ptr(cnt), ptr(err),
+                                      stream_handle()), "plane_score")
+    return cnt[:H].cpu().numpy(), err[:H].cpu().numpy()
 
 
 def estimate_normals(points, radius: float, max_nn: int = 30, normals=None):

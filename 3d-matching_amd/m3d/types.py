@@ -90,6 +90,14 @@ class PointCloud:
         ind = remove_radius_outlier(self.points, nb_points, radius)
         return self.select_by_index(ind), ind
 
+    def segment_plane(self, distance_threshold: float = 0.01, ransac_n: int = 3, num_iterations: int = 100,
+                      probability: float = 0.99999999):
+        """Open3D ``PointCloud.segment_plane`` on the device (m3d.prep) → (plane_model (4,),
+        inlier indices ascending); ``select_by_index(inliers, invert=True)`` drops the plane."""
+        from .prep import segment_plane
+
+        return segment_plane(self.points, distance_threshold, ransac_n, num_iterations, probability)
+
     def transform(self, T):
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]

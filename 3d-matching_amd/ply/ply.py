@@ -8,6 +8,10 @@ by the device path of ``m3d.prep``:
    ``{"nb_points", "radius"}`` filters ``pcd`` (points and file normals) on the device like
    Open3D's ``remove_statistical_outlier`` / ``remove_radius_outlier`` before step 2; the
    default ``None`` leaves every result as it is without it
+1b. optional, not in the reference: ``remove_plane`` = ``{"distance_threshold"}`` plus optional
+   ``ransac_n``, ``num_iterations``, ``probability``, ``seed`` drops the inliers of Open3D's
+   ``segment_plane`` (the table or floor a scanned part stands on) from ``pcd`` after 1a;
+   ``plane_model`` and ``plane_removed`` keep the plane and the number of points dropped
 2. ``pcd_down`` = voxel down-sample (voxel_size); file normals, when present, are averaged
    per voxel like Open3D's VoxelDownSample                                           ply.py:106
 3. ``pcd_down`` normals: hybrid search (2·v, 30), oriented by those averaged normals ply.py:110-112
@@ -32,7 +36,8 @@ from m3d.types import Feature, PointCloud
 
 
 class Ply:
-    def __init__(self, path, voxel_size: float = 0.3, remove_outliers: dict | None = None) -> None:
+    def __init__(self, path, voxel_size: float = 0.3, remove_outliers: dict | None = None,
+                 remove_plane: dict | None = None) -> None:
         self.path = Path(path)
         self.voxel_size = voxel_size
         if not self.path.exists():
@@ -47,7 +52,7 @@ class Ply:
         if len(pts) == 0:
             raise ValueError(f"Point cloud is empty: {self.path}")          # ply.py:81-84
         self.pcd = PointCloud(pts, nrm)
-        self._preprocess(voxel_size, remove_outliers)
+        self._preprocess(voxel_size, remove_outliers, remove_plane)
 
     def _remove_outliers(self, params: dict) -> None:
         """``pcd`` ← the points (and file normals) one of Open3D's two outlier filters keeps."""
@@ -59,7 +64,27 @@ class Ply:
         else:
             raise ValueError("remove_outliers: {'nb_neighbors', 'std_ratio'} or {'nb_points', 'radius'}")
 
-    def _preprocess(self, voxel_size: float, remove_outliers: dict | None = None) -> None:
+    _PLANE_KEYS = {"distance_threshold", "ransac_n", "num_iterations", "probability", "seed"}
+
+    def _remove_plane(self, params: dict) -> None:
+        """``pcd`` ← the points (and file normals) outside the segmented plane's inliers."""
+        from m3d import prep
+
+        keys = set(params)
+        if "distance_threshold" not in keys or not keys <= self._PLANE_KEYS:
+            raise ValueError("remove_plane: {'distance_threshold'} plus optional 'ransac_n', 'num_iterations', "
+                             "'probability', 'seed'")
+        plane, inliers, out = prep.segment_plane(self.pcd.points, params["distance_threshold"],
+                                                 params.get("ransac_n", 3), params.get("num_iterations", 100),
+                                                 params.get("probability", 0.99999999),
+                                                 seed=params.get("seed", 0), with_details=True)
+        self.plane_model = plane
+        self.plane_ransac = out.ransac_plane  # the plane the removed points were tested against
+        self.plane_removed = len(inliers)
+        self.pcd = self.pcd.select_by_index(inliers, invert=True)
+
+    def _preprocess(self, voxel_size: float, remove_outliers: dict | None = None,
+                    remove_plane: dict | None = None) -> None:
         """ply.py:53-66.  Wall time of each stage lands in ``stage_ms`` (every stage returns host
         arrays, so the device work is complete when its timer stops)."""
         from m3d import prep
@@ -80,6 +105,9 @@ class Ply:
         if remove_outliers is not None:
             self._remove_outliers(remove_outliers)
             lap("remove_outliers")
+        if remove_plane is not None:
+            self._remove_plane(remove_plane)
+            lap("remove_plane")
         # the full cloud goes to the device once (down-sampling, then its normals), the
         # down-sampled one once (its normals, then FPFH: the noise is added after, ply.py:61-62)
         p_dev = to_device(self.pcd.points)
@@ -103,13 +131,14 @@ class Ply:
 
     @classmethod
     def from_arrays(cls, points, normals=None, points_down=None, fpfh=None, voxel_size: float = 0.3,
-                    preprocess: bool = False, remove_outliers: dict | None = None):
+                    preprocess: bool = False, remove_outliers: dict | None = None,
+                    remove_plane: dict | None = None):
         obj = cls.__new__(cls)
         obj.path = None
         obj.voxel_size = voxel_size
         obj.pcd = PointCloud(points, normals)
         if preprocess:
-            obj._preprocess(voxel_size, remove_outliers)
+            obj._preprocess(voxel_size, remove_outliers, remove_plane)
             return obj
         obj.pcd_down = PointCloud(points if points_down is None else points_down)
         obj.pcd_fpfh = None if fpfh is None else Feature(np.asarray(fpfh, np.float64))

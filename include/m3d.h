@@ -539,6 +539,62 @@ int m3d_remove_statistical_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t
 int m3d_remove_radius_outlier(m3d_ctx* ctx, const m3d_cloud* cloud, int32_t nb_points, double radius,
                               int32_t* index_out, int64_t* n_out, int32_t* count_out, void* stream);
 
+/* ------------------------------------------------------------------ plane segmentation (plane.hip)
+ * PointCloud::SegmentPlane(distance_threshold, ransac_n, num_iterations, probability) (Open3D 0.19)
+ * — the support plane of a scan, removed before the scan is registered.  All arithmetic is fp64 on
+ * the cloud's original coordinates, every operation rounded on its own, in the order written:
+ *   dist(π, p) = |((a·x + b·y) + c·z) + d|
+ *   ransac_n == 3: e0 = p1 − p0, e1 = p2 − p0, abc = e0 × e1, norm = sqrt((abc.x² + abc.y²) + abc.z²);
+ *                  norm == 0: the zero plane, else abc /= norm, d = −((abc.x·p0.x + abc.y·p0.y) + abc.z·p0.z)
+ *   ransac_n  > 3: GetPlaneFromPoints over the sample in sample order — centroid = (Σp)/m, the six
+ *                  sums of products of r = p − centroid, the largest of det_x, det_y, det_z picks the
+ *                  axis, norm == 0: the zero plane, else abc /= norm, d = −abc·centroid
+ * The loop is sequential over h = 0 … num_iterations − 1 with best_count = 0, best_rmse = 0,
+ * best_index = −1, break_it = +inf, evaluated = 0:
+ *   if evaluated > break_it: stop
+ *   π = plane of sample h; all zero: continue (not counted)
+ *   count = #{i : dist < thr}, err = Σ dist² over those, rmse = count ? err / sqrt(count) : 0
+ *   count > best_count or (count == best_count and rmse < best_rmse):
+ *     best ← (count, rmse, π, h); f = count / n;
+ *     break_it = f < 1 ? trunc(min(log(1 − probability) / log(1 − pow(f, ransac_n)), num_iterations)) : 0
+ *   evaluated += 1
+ * then inliers = {i : dist(best plane, p_i) < thr} ascending and plane = GetPlaneFromPoints(inliers)
+ * (two fixed-order fp64 reductions: repeated calls return the same bits); no best, or fewer than 3
+ * inliers: the zero plane.  Samples: the caller's (`samples`) or the counter sampler of
+ * m3d_kabsch3_batch generalised to ransac_n distinct indices. */
+typedef struct {
+  double distance_threshold;  /* Open3D default 0.01 */
+  double probability;         /* 0.99999999 */
+  uint64_t seed;              /* native sampler; ignored with samples */
+  int32_t ransac_n;           /* 3 */
+  int32_t num_iterations;     /* 100 */
+  int32_t batch;              /* hypotheses per device batch, 0 = automatic; changes no result */
+  int32_t reserved;
+} m3d_plane_params;
+typedef struct {
+  double plane[4];         /* refit over the inliers (what Open3D returns) */
+  double ransac_plane[4];  /* the best hypothesis's own plane (the one the inliers are tested against) */
+  int64_t num_inliers, best_index, best_count, evaluated, iterations /* h at exit */;
+  double best_rmse;
+} m3d_plane_result;
+/* samples [device] num_iterations × ransac_n int32 or NULL (native sampler); inliers_out [device]
+ * room for n int32; counts_out [device] num_iterations int32 or NULL (−1 = degenerate or not
+ * reached); err_out [device] num_iterations f64 or NULL (same rows, −1 likewise).
+ * M3D_ERR_INVALID: ransac_n < 3 or > 32, n < ransac_n, probability <= 0 or > 1, num_iterations < 0,
+ * distance_threshold negative or not finite, a sample index outside [0, n) (found on the device
+ * before any point is read).  Synchronous. */
+int m3d_segment_plane(m3d_ctx* ctx, const m3d_cloud* cloud, const m3d_plane_params* params,
+                      const int32_t* samples, m3d_plane_result* out, int32_t* inliers_out,
+                      int32_t* counts_out, double* err_out, void* stream);
+/* Score H given planes: planes [device] H×4 f64 → counts [device] H int32, err [device] H f64 or
+ * NULL.  A plane's count and err do not depend on H or on the planes beside it.  Only enqueues
+ * work on stream; H == 0 or an empty cloud: nothing is touched. */
+int m3d_plane_score(m3d_ctx* ctx, const m3d_cloud* cloud, const double* planes, int64_t H,
+                    double distance_threshold, int32_t* counts, double* err, void* stream);
+/* points per chunk of the score kernel's partial sums: a constant of the library (err is the
+ * sequential sum inside a chunk, the chunk sums are added in a fixed order) */
+int32_t m3d_plane_chunk(void);
+
 /* ------------------------------------------------------------------ feature matching (a5, a6) */
 
 /* CorrespondencesFromFeatures (src/matcher/ransac.py:85): exact fp64 1-NN in feature space
