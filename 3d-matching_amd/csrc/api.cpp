@@ -1408,6 +1408,13 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
       const size_t n1 = (size_t)std::max<int64_t>(src->n, 1);
       Carve cv;
       cv.add(&s->state, 1);
+      if (params->nn_method == M3D_NN_BRUTE) nn_plan_shape(src->n, &s->nn_qblocks, &s->nn_budget);
+      if (s->nn_qblocks > 0) {  // the brute-force NN's slice plan (nn_plan.h), on the state's page: the fused
+                                // tail's last block reads both
+        cv.add(&s->nn_cnt, (size_t)s->nn_qblocks);
+        cv.add(&s->nn_seen, (size_t)s->nn_qblocks);
+        cv.add(&s->nn_table, (size_t)s->nn_budget);
+      }
       cv.add(&s->keys, n1);
       cv.add(&s->near2, n1);
       cv.add(&s->dprev, n1);
@@ -1433,6 +1440,11 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
     if (!grc && s->hcnt != nullptr &&
         hipMemsetAsync(s->hcnt, 0, kDeferWords * sizeof(uint32_t), nullptr) != hipSuccess)
       grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: deferral counter");
+    // likewise the NN plan's tile counters (the planner re-zeroes them, and every reset of the loop's
+    // state: launch_icp_reset, launch_icp_set_T)
+    if (!grc && s->nn_cnt != nullptr &&
+        hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t), nullptr) != hipSuccess)
+      grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: NN plan counters");
     // the setup above ran asynchronously on the null stream: finish it before the loop object is
     // used on the caller's streams
     if (!grc) {
@@ -2633,6 +2645,51 @@ int m3d_debug_icp_defer_count(m3d_icp* s, uint32_t count, void* stream) {
   CHECK_ARG(s->ctx, s->hcnt != nullptr, "this loop has no deferral list (grid NN with a candidate cap only)");
   Touch tch{s->ctx, S(stream)};
   HIPX(s->ctx, hipMemcpyAsync(s->hcnt, &count, sizeof(count), hipMemcpyHostToDevice, S(stream)));
+  HIPX(s->ctx, hipStreamSynchronize(S(stream)));
+  return M3D_OK;
+}
+
+int m3d_debug_nn_plan_host(const uint32_t* counts, int64_t n, int64_t budget, int64_t smax, int64_t ntiles,
+                           uint32_t* out) {
+  if (!counts || !out || smax < 1 || ntiles < 1) return M3D_ERR_INVALID;
+  const uint32_t tau = plan_host(counts, n, budget, smax, ntiles, nullptr, out);
+  return tau == 0 ? M3D_ERR_INVALID : (int)tau;
+}
+
+int m3d_debug_icp_nn_plan(m3d_icp* s, const int32_t* S_, int64_t n, void* stream) {
+  if (!s || !S_) return M3D_ERR_INVALID;
+  CHECK_ARG(s->ctx, s->nn_qblocks > 0 && nn_plan_on(), "this loop's NN launch takes no plan");
+  CHECK_ARG(s->ctx, n == s->nn_qblocks, "one S per query block of 512 sources");
+  const int64_t ntiles = s->tgrid->mf_npad / 1024;  // nn_brute.hip: tiles of 1024 targets
+  std::vector<uint32_t> Sv((size_t)n), table((size_t)s->nn_budget);
+  int64_t sum = 0;
+  for (int64_t x = 0; x < n; ++x) {
+    CHECK_ARG(s->ctx, S_[x] >= 1 && S_[x] <= ntiles && S_[x] <= 255, "S out of range [1, min(ntiles, 255)]");
+    Sv[(size_t)x] = (uint32_t)S_[x];
+    sum += S_[x];
+  }
+  CHECK_ARG(s->ctx, sum <= s->nn_budget, "more slices than resident block slots");
+  plan_table_of(Sv.data(), n, s->nn_budget, table.data());
+  Touch tch{s->ctx, S(stream)};
+  const int32_t forced = 2;
+  HIPX(s->ctx, hipMemcpyAsync(s->nn_table, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice, S(stream)));
+  HIPX(s->ctx, hipMemcpyAsync(&s->state->plan_ok, &forced, sizeof(forced), hipMemcpyHostToDevice, S(stream)));
+  HIPX(s->ctx, hipStreamSynchronize(S(stream)));
+  return M3D_OK;
+}
+
+int m3d_debug_icp_nn_plan_read(m3d_icp* s, uint32_t* counts, uint32_t* table, int32_t* shape3, void* stream) {
+  if (!s || !shape3) return M3D_ERR_INVALID;
+  shape3[0] = s->nn_qblocks;
+  shape3[1] = s->nn_budget;
+  shape3[2] = 0;
+  if (s->nn_qblocks <= 0) return M3D_OK;
+  Touch tch{s->ctx, S(stream)};
+  if (counts)
+    HIPX(s->ctx, hipMemcpyAsync(counts, s->nn_seen, sizeof(uint32_t) * (size_t)s->nn_qblocks, hipMemcpyDeviceToHost, S(stream)));
+  if (table)
+    HIPX(s->ctx, hipMemcpyAsync(table, s->nn_table, sizeof(uint32_t) * (size_t)s->nn_budget, hipMemcpyDeviceToHost, S(stream)));
+  HIPX(s->ctx, hipMemcpyAsync(&shape3[2], &s->state->plan_ok, sizeof(int32_t), hipMemcpyDeviceToHost, S(stream)));
   HIPX(s->ctx, hipStreamSynchronize(S(stream)));
   return M3D_OK;
 }

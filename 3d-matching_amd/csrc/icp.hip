@@ -156,6 +156,7 @@ __device__ __forceinline__ void reset_eval(IcpState* s, double r2, const FramePa
   s->count = 0;
   s->evals = s->iters = s->done = s->converged = 0;
   s->ticket = 0;
+  s->plan_ok = 0;  // the next NN launch runs the uniform slices: a run's launch shapes are its own
   s->r2 = r2;
   s->bound_ok = 0;
   refresh_rt32(s, f);
@@ -880,16 +881,103 @@ __global__ __launch_bounds__(kTermSlots) void reduce_groups_kernel(double* __res
   if (do_solve) solve_state<kEst>(out, s, sp, in);
 }
 
+// The brute-force NN's slice plan for the next evaluation (nn_plan.h), by ONE wave: wave 1 of the
+// fused tail's last block, which otherwise idles while wave 0 runs solve_state.  A lane holds the
+// counts of query blocks lane, lane + 64, … (kPlanMaxQ / 64 of them), loaded by plan_in before the
+// partial sums as SolveIn is; plan_wave zeroes the counters (the reader does), keeps the counts it
+// read in `seen`, bisects τ with a wave sum per probe and writes the table in the uniform launch's
+// order — slice y of every query block that has one, by ballot ranks — then the empty entries and
+// the flag.  A forced plan (plan_ok = 2) keeps its table.  No block waits for it: the next NN
+// launch reads table and flag after this kernel ends.
+constexpr int kPlanPer = kPlanMaxQ / kWave;
+struct PlanIn {
+  uint32_t t[kPlanPer];
+  int32_t flag;
+};
+__device__ __forceinline__ void plan_in(const PlanArgs& pa, const IcpState* s, int lane, PlanIn& in) {
+  in.flag = __hip_atomic_load(&s->plan_ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+  for (int k = 0; k < kPlanPer; ++k) {
+    // branch-free (a clamped index, selected after): under a per-lane branch every load would be
+    // waited for inside its own branch, eight round trips one after the other
+    const int x = k * kWave + lane;
+    in.t[k] = __hip_atomic_load(&pa.cnt[min(x, pa.n - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int k = 0; k < kPlanPer; ++k) in.t[k] = k * kWave + lane < pa.n ? min(in.t[k], kPlanTmax) : 0u;
+}
+// sum / max of v over the wave's 64 lanes (all active), wave-uniform: DPP inside each row of 16
+// lanes, then the four rows by v_readlane — no LDS round trips (a probe of the bisection is
+// one of these)
+template <bool kMax>
+__device__ __forceinline__ uint32_t plan_wave_red(uint32_t v) {
+  const auto op = [](uint32_t a, uint32_t b) { return kMax ? max(a, b) : a + b; };
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) v = op(v, (uint32_t)xor_lane((int)v, o, kWave));
+  const auto rl = [&](int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); };
+  return op(op(rl(0), rl(16)), op(rl(32), rl(48)));
+}
+__device__ void plan_wave(const PlanArgs& pa, IcpState* s, int lane, const PlanIn& in) {
+  uint32_t tmax = 0, tsum = 0;
+#pragma unroll
+  for (int k = 0; k < kPlanPer; ++k) {
+    const int x = k * kWave + lane;
+    if (x < pa.n) {
+      pa.cnt[x] = 0u;
+      pa.seen[x] = in.t[k];
+    }
+    tmax = max(tmax, in.t[k]);
+    tsum += in.t[k];
+  }
+  if (in.flag == 2) return;
+  tmax = plan_wave_red<true>(tmax);
+  tsum = plan_wave_red<false>(tsum);
+  const uint32_t cap = (uint32_t)pa.cap;
+  const uint32_t tau = plan_tau(tmax, tsum, (uint32_t)pa.n, (uint32_t)pa.budget, [&](uint32_t m) {
+    uint32_t a = 0;
+#pragma unroll
+    for (int k = 0; k < kPlanPer; ++k)
+      if (k * kWave < pa.n)  // (wave-uniform: the chunks past n cost nothing)
+        a += k * kWave + lane < pa.n ? plan_slices(in.t[k], m, cap) : 0u;
+    return plan_wave_red<false>(a);
+  });
+  uint32_t S[kPlanPer];
+#pragma unroll
+  for (int k = 0; k < kPlanPer; ++k) S[k] = k * kWave + lane < pa.n ? plan_slices(in.t[k], tau, cap) : 0u;
+  int pos = 0;
+  for (uint32_t y = 0; y < cap; ++y) {
+    const int pos0 = pos;
+#pragma unroll
+    for (int k = 0; k < kPlanPer; ++k) {
+      if (k * kWave >= pa.n) break;
+      const bool has = S[k] > y;
+      const uint64_t m = __ballot(has);
+      const int at = pos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (has && at < pa.budget) pa.table[at] = plan_entry((uint32_t)(k * kWave + lane), y, S[k]);
+      pos += __builtin_popcountll(m);
+    }
+    if (pos == pos0) break;  // no query block has a slice y
+  }
+  for (int i = pos + lane; i < pa.budget; i += kWave) pa.table[i] = kPlanEmpty;
+  if (lane == 0) s->plan_ok = 1;
+}
+
 // Fused single-device iteration tail: terms → block partial → the last block to finish (ticket)
 // reduces all partials in reduce_kernel's exact order and runs solve_state.  Cross-XCD hand-off
 // (MI355X_MICROARCH.md, visibility table, "last adder" row): each block stores its partial
 // write-through (sc1), drains it (vmcnt(0)) and one lane adds to the agent-scope ticket; the
 // block whose add returned nblocks − 1 reads every partial with sc1 loads.  No L2 write-back or
 // invalidate fences are needed.
-template <int kEst>
+// kPlanner: with the NN slice planner in wave 1 of the last block (loops whose NN launch takes a plan);
+// false: without it, the kernel of every other loop — grid NN, the 1M source — as it was (PlanNone
+// is empty).
+struct PlanNone {
+  static constexpr int32_t n = 0;
+};
+template <int kEst, bool kPlanner>
 __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
     TermsArgs a, IcpState* s, double* partials, int64_t nblocks, double* __restrict__ sums,
-    SolveParams sp, int do_solve) {
+    SolveParams sp, int do_solve, std::conditional_t<kPlanner, PlanArgs, PlanNone> pa) {
   // do_solve = 0: the sharded tail (m3d_icp_shard_terms) — terms + the fixed-order reduce into
   // `sums` in one launch; the caller all-reduces them and runs m3d_icp_solve
   if (s->done) return;
@@ -922,6 +1010,11 @@ __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
   M3D_TCLK(0);
   SolveIn in;
   if (do_solve && threadIdx.x < kWave) solve_in(s, in);
+  // wave 1: the NN slice planner's counts (plan_wave below), in flight with the partials as well
+  const bool planner = kPlanner && pa.n > 0 && threadIdx.x >= kWave && threadIdx.x < 2 * kWave;
+  PlanIn pin;
+  if constexpr (kPlanner)
+    if (planner) plan_in(pa, s, threadIdx.x - kWave, pin);
   // every load of the other blocks' partials is an sc1 load (L2-coherent, bypasses L1)
   const int slot = threadIdx.x & (kTermSlots - 1);
   constexpr int kG = kReduceGroups / (kTermsBlock / kTermSlots);  // groups per thread
@@ -965,6 +1058,8 @@ __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
   if (threadIdx.x < kWave) {
     if (threadIdx.x == 0) s->ticket = 0;
     if (do_solve) solve_state<kEst>(red[0], s, sp, in);
+  } else if (planner) {
+    if constexpr (kPlanner) plan_wave(pa, s, threadIdx.x - kWave, pin);
   }
   M3D_TCLK(2);
 }
@@ -1127,8 +1222,18 @@ static hipError_t reset_points(const m3d_icp* s, hipStream_t st) {
   return hipMemcpyAsync(s->pcd64, s->src->xyz64, sizeof(double) * 3 * s->src->n, hipMemcpyDeviceToDevice, st);
 }
 
+// The NN plan's tile counters start a run at zero, like the flag (reset_eval): the run's first plan
+// counts the run's own evaluations only.  (Where no planner reads them — GICP, M3D_ICP_FUSED=0 — they
+// add up until the next reset; a planner that runs later in the same run reads them clamped at
+// kPlanTmax, and sums over evaluations size the slices like one evaluation's counts.)
+static hipError_t reset_plan_counts(const m3d_icp* s, hipStream_t st) {
+  if (s->nn_cnt == nullptr) return hipSuccess;
+  return hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t), st);
+}
+
 hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st) {
   hipError_t e = reset_points(s, st);
+  if (e == hipSuccess) e = reset_plan_counts(s, st);
   if (e != hipSuccess) return e;
   icp_init_kernel<<<1, 64, 0, st>>>(s->state, T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7],
                                     T[8], T[9], T[10], T[11], s->max_dist * s->max_dist,
@@ -1138,6 +1243,7 @@ hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, 
 
 hipError_t launch_icp_set_T(const m3d_icp* s, const double* T_dev, hipStream_t st) {
   hipError_t e = reset_points(s, st);
+  if (e == hipSuccess) e = reset_plan_counts(s, st);
   if (e != hipSuccess) return e;
   icp_set_T_kernel<<<1, 64, 0, st>>>(s->state, T_dev, s->max_dist * s->max_dist, frame_of(s));
   return hipGetLastError();
@@ -1332,9 +1438,14 @@ static void launch_terms_solve(const TermsArgs& ta, const m3d_icp* s, double* su
                                hipStream_t st) {
   const unsigned nb = (unsigned)s->nblocks;
   const SolveParams sp = solve_params(s);
+  const PlanArgs pa = nn_plan_args(s);
   with_est(ta.est, [&](auto e) {
-    terms_solve_kernel<decltype(e)::value><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks, sums, sp,
-                                                                       do_solve);
+    if (pa.n > 0)
+      terms_solve_kernel<decltype(e)::value, true><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks,
+                                                                               sums, sp, do_solve, pa);
+    else
+      terms_solve_kernel<decltype(e)::value, false><<<nb, kTermsBlock, 0, st>>>(ta, s->state, s->partials, s->nblocks,
+                                                                                sums, sp, do_solve, PlanNone{});
   });
 }
 

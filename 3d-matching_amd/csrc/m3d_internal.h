@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/m3d.h"
+#include "nn_plan.h"
 
 // Uniform (wave-invariant) loads: a pointer in the constant address space makes the AMDGPU
 // backend emit scalar s_load / s_buffer_load, which put the data in SGPRs and broadcast it to
@@ -80,6 +81,10 @@ struct IcpState {
   float band_e;         // 2·e_q·1.01: absolute term of nnkey.h band_of (fp32 → fp64 ambiguity)
   float eq;             // e_q: bound on |fp32 distance − fp64 distance| for the current T
   float eq_prev;        // e_q of the previous evaluation (seed_key bounds)
+  // brute-force NN slice plan (nn_plan.h): 0 = none, the launch derives the uniform slices;
+  // 1 = the table the fused tail's planner wrote from the last evaluation's tile counts;
+  // 2 = forced (m3d_debug_icp_nn_plan), which the planner leaves alone.  Cleared by reset_eval.
+  int32_t plan_ok;
   // the transform the next evaluation applies to the loop's points: its fp64 queries are
   // dT·pcd64[i], written back (Open3D transforms its copy of the source by every update,
   // pcd.Transform(update)); after a reset, init (or I when init isIdentity()), then each ΔT
@@ -361,6 +366,14 @@ struct m3d_icp {
   // source's extent (a spatial shard), whose queries' work sits in a few Morton ranges
   int32_t scan_xchunk = 0;
   bool keys_clean = false;         // host view: every key is kKeyNone (fused tail reset them)
+  // brute-force NN slice plan (nn_plan.h, nn_brute.hip): per query block the tiles kept, the
+  // counts the planner last read, the table of nn_budget entries; nn_qblocks = 0: no plan (grid
+  // NN, or as many query blocks as resident block slots)
+  uint32_t* nn_cnt = nullptr;
+  uint32_t* nn_seen = nullptr;
+  uint32_t* nn_table = nullptr;
+  int32_t nn_qblocks = 0;
+  int32_t nn_budget = 0;
   int32_t* corr = nullptr;         // ns current correspondence (-1 none)
   double* pcd64 = nullptr;         // ns×3: the source as Open3D's RegistrationICP holds it — the
                                    // points after every update but the last (dT, IcpState)
@@ -487,6 +500,12 @@ hipError_t launch_icp_keyinit(const m3d_icp* s, int64_t shard_offset, hipStream_
                               int64_t q1 = -1);
 hipError_t launch_icp_nn(const m3d_icp* s, int64_t shard_offset, bool self_seed, hipStream_t st,
                          int64_t q0 = 0, int64_t q1 = -1);
+// the blocks of nn_mfma_kernel resident on the device at once (0: unknown), and the plan shape of a
+// brute-force loop over ns sources: query blocks and budget, 0 / 0 when no plan can apply
+int64_t nn_resident_slots();
+bool nn_plan_on();  // M3D_NN_PLAN in the environment (0: the uniform 2-D launch everywhere)
+void nn_plan_shape(int64_t ns, int32_t* qblocks, int32_t* budget);
+PlanArgs nn_plan_args(const m3d_icp* s);
 hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st);
 hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st);
 hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st);

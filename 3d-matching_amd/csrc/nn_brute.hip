@@ -10,6 +10,24 @@
 #include "m3d_internal.h"
 #include "nnkey.h"
 
+// Two translation units.  nn_mfma_kernel (the 2-D launch) and nn_mfma_plan_kernel (the planned 1-D
+// launch) instantiate one body (nn_mfma_body), and each sits at 128 VGPRs without scratch only when
+// it is the one NN kernel of its translation unit: with both in one, the 2-D kernel — otherwise the
+// code from before the plan but for nine scalar instructions, same descriptor — spills 12 B and the planned one 8 B (the shared
+// helpers are inlined in another order).  So nn_brute_plan.hip compiles this file again with
+// M3D_NN_BRUTE_PLAN_TU=1 and keeps only the device code, the planned kernel and its launcher;
+// this file's own compilation keeps everything else.  Clock builds (M3D_NN_CLOCK, one record array)
+// keep both kernels here and leave nn_brute_plan.hip empty.
+#ifndef M3D_NN_BRUTE_PLAN_TU
+#define M3D_NN_BRUTE_PLAN_TU 0
+#endif
+#ifndef M3D_NN_CLOCK
+#define M3D_NN_CLOCK 0
+#endif
+#define M3D_NN_TU_MAIN (!M3D_NN_BRUTE_PLAN_TU)
+#define M3D_NN_TU_PLAN_KERNEL (M3D_NN_BRUTE_PLAN_TU ? !M3D_NN_CLOCK : M3D_NN_CLOCK)
+#if M3D_NN_TU_MAIN || M3D_NN_TU_PLAN_KERNEL
+
 namespace m3d {
 
 // ------------------------------------------------------------------------------- NN, MFMA screen
@@ -81,6 +99,7 @@ __device__ __forceinline__ void thr_operand(half8& b, float thr0, bool& force) {
   b[4] = -tl;
 }
 
+#if M3D_NN_TU_MAIN
 // target operand rows in Morton order of the grid's cells (build_mfma_tiles); 0 (A/B builds):
 // row-major cells
 #ifndef M3D_NN_TILE_MORTON
@@ -185,6 +204,8 @@ hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, TmpArena* ta, hipStream
   return hipGetLastError();  // asynchronous (stream order); m3d_icp_create synchronises once
 }
 
+#endif  // M3D_NN_TU_MAIN
+
 // Self-seeding (single-device fused loop, m3d_icp_step): the fused tail of the previous
 // iteration left every key at kKeyNone, so instead of a keyinit launch every block computes
 // its queries' starting key itself (nnkey.h seed_key: the previous correspondence, exact — one
@@ -203,10 +224,23 @@ __device__ __forceinline__ int64_t start_key(const SeedArgs& sa, const IcpState*
   return sa.on ? seed_key(s, i, p, qx, qy, qz, sa.tgt, sa.nt, off, sa.prev, nullptr) : keys[i];
 }
 
-// whether a block publishes its k1: it changed, or (self-seeding) the grid.y = 0 blocks publish
+// A block's place in the launch: slice y of the S slices of query block x (NnSlice, below)
+struct NnSlice {
+  unsigned x, y, S;
+};
+// The planned (1-D) launch of nn_mfma_kernel: the loop's table of `budget` entries and per query
+// block tile counts (nn_plan.h), and the uniform assignment — nq query blocks × S slices, what
+// nn_grid_y gives — for a loop state without a valid plan.  table = null: the 2-D launch.
+struct NnPlan {
+  const uint32_t* table;
+  uint32_t* cnt;
+  int nq, S;
+};
+
+// whether a block publishes its k1: it changed, or (self-seeding) the slice 0 blocks publish
 // the seed every block started from
-__device__ __forceinline__ bool publish_k1(const SeedArgs& sa, uint64_t k1, bool changed) {
-  return changed || (sa.on && blockIdx.y == 0 && key_real(k1));
+__device__ __forceinline__ bool publish_k1(const SeedArgs& sa, unsigned y, uint64_t k1, bool changed) {
+  return changed || (sa.on && y == 0 && key_real(k1));
 }
 
 // Exact fallback of nn_mfma_kernel when the scaled operands do not fit fp16 (mfma_ok == 0, a
@@ -215,11 +249,11 @@ __device__ __forceinline__ bool publish_k1(const SeedArgs& sa, uint64_t k1, bool
 __device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, const float4* __restrict__ tgt32,
                               int64_t jb, int64_t je, int64_t off, const IcpState* __restrict__ s,
                               int64_t* __restrict__ keys, uint32_t* __restrict__ near2,
-                              const SeedArgs& sa, int64_t q0) {
+                              const SeedArgs& sa, int64_t q0, unsigned bsx, unsigned bsy) {
   const float* Rt = s->Rt32;
   const float r2_hi = s->r2_hi;
   for (int qs = threadIdx.x; qs < kMQueries; qs += kMBlock) {
-    const int64_t slot = q0 + (int64_t)blockIdx.x * kMQueries + qs;
+    const int64_t slot = q0 + (int64_t)bsx * kMQueries + qs;
     if (slot >= ns) return;
     const int64_t i = slot;
     float qx, qy, qz;
@@ -235,7 +269,7 @@ __device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, cons
       const float d2 = d2f(qx, qy, qz, t.x, t.y, t.z);
       if (d2 <= r2_hi) near_push(k1, k1d, n2, make_key(d2, (uint32_t)(off + __float_as_int(t.w))), d2);
     }
-    const bool pk = publish_k1(sa, k1, k1 != k10);
+    const bool pk = publish_k1(sa, bsy, k1, k1 != k10);
     if (pk || n2 < kInf) near_publish((unsigned long long*)&keys[i], &near2[i], k1, n2, pk);
   }
 }
@@ -346,9 +380,6 @@ __device__ __forceinline__ float wave_minmax(float v) {
 #endif
 // diagnostic builds only (tools/nn_clock.py): per-block timeline and tile counts of the last
 // nn_mfma_kernel launch, s_memrealtime (100 MHz: one clock for every block, whichever XCD runs it)
-#ifndef M3D_NN_CLOCK
-#define M3D_NN_CLOCK 0
-#endif
 #if M3D_NN_CLOCK
 constexpr int kClkBlocks = 16384, kClkWords = 8;
 __device__ unsigned long long g_nn_clock[kClkWords * kClkBlocks];
@@ -513,7 +544,7 @@ struct TileCursor {
   const float4* tbox;   // Grid::mfbox
   const float4* wbox;   // this wave's box, qbox[wave] (LDS)
   QBox bx;              // the block's box
-  int lane, ntile, ty;  // tiles in all, the set's stride (gridDim.y)
+  int lane, ntile, ty;  // tiles in all, the set's stride (the query block's slices S)
   int tc;               // first tile of the current round
   uint64_t mb, mw;
   int par = 0;          // parity of the round (ReachArgs::slot)
@@ -731,26 +762,46 @@ __device__ __forceinline__ void nn_push_hits(uint32_t m, const float4* rows, int
   }
 }
 
-__global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(const float4* __restrict__ src32,
-                                                          int64_t ns,
-                                                          const uint4* __restrict__ tgt16,
-                                                          const float4* __restrict__ tgt32,
-                                                          const float4* __restrict__ tbox,
-                                                          int64_t nt_pad, int64_t off,
-                                                          const IcpState* __restrict__ s,
-                                                          int64_t* __restrict__ keys,
-                                                          uint32_t* __restrict__ near2,
-                                                          SeedArgs sa, int64_t q0) {
+// The body of the two NN kernels below.  kPlan = false is nn_mfma_kernel, the 2-D launch: the
+// block's slice is (blockIdx.x, blockIdx.y) of gridDim.y, from the hardware at every use, and none
+// of the plan's code is in it — no table, no LDS word, no counter: the launches the plan does not
+// apply to (the 1M source: 1954 query blocks; any grid.x) run the code they ran before the plan.
+// kPlan = true is nn_mfma_plan_kernel, the 1-D launch of pl.budget blocks (at most kPlanMaxQ
+// query blocks: x fits the 16 bits of a table entry and of the LDS word).
+template <bool kPlan>
+__device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, int64_t ns,
+                                             const uint4* __restrict__ tgt16, const float4* __restrict__ tgt32,
+                                             const float4* __restrict__ tbox, int64_t nt_pad, int64_t off,
+                                             const IcpState* __restrict__ s, int64_t* __restrict__ keys,
+                                             uint32_t* __restrict__ near2, const SeedArgs& sa, int64_t q0,
+                                             const NnPlan& pl) {
   if (s->done) return;
 #if M3D_NN_CLOCK
   const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  // grid.y block y takes every gridDim.y-th target tile (strided: a query block's few candidate
-  // tiles, adjacent in row order, spread over gridDim.y blocks instead of landing in one)
+  // The block's slice.  2-D launch: block (x, y) of grid (query blocks, S).
+  // 1-D launch of pl.budget blocks: the loop's plan table entry (IcpState::plan_ok; one scalar
+  // load, the round trip of s->done), or without a valid plan the uniform assignment the 2-D
+  // launch has — y = b / nq, x = b % nq, S = pl.S; an empty entry, or y ≥ S, has nothing to do.
+  NnSlice bs{0u, 0u, 0u};  // (2-D launch: unused — the hardware's values at every use, as before the plan)
+  if (kPlan && pl.table != nullptr) {
+    if (s->plan_ok) {
+      const uint32_t e = pl.table[blockIdx.x];
+      if (e == kPlanEmpty) return;
+      bs = NnSlice{plan_x(e), plan_y(e), plan_S(e)};
+    } else {
+      const unsigned y = blockIdx.x / (unsigned)pl.nq;
+      if (y >= (unsigned)pl.S) return;
+      bs = NnSlice{blockIdx.x - y * (unsigned)pl.nq, y, (unsigned)pl.S};
+    }
+  }
+  // slice y takes every S-th target tile (strided: a query block's few candidate tiles, adjacent
+  // in row order, spread over its S blocks instead of landing in one)
   if (!s->mfma_ok) {  // the same tiles by a plain scan, unculled
-    const int64_t tstep = (int64_t)gridDim.y * kTT;
-    for (int64_t t0 = (int64_t)blockIdx.y * kTT; t0 < nt_pad; t0 += tstep)
-      nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTT), off, s, keys, near2, sa, q0);
+    const int64_t tstep = (int64_t)(kPlan ? bs.S : gridDim.y) * kTT;
+    for (int64_t t0 = (int64_t)(kPlan ? bs.y : blockIdx.y) * kTT; t0 < nt_pad; t0 += tstep)
+      nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTT), off, s, keys, near2, sa, q0,
+                    kPlan ? bs.x : blockIdx.x, kPlan ? bs.y : blockIdx.y);
     return;
   }
   __shared__ uint4 t16[2][2][kTT];
@@ -766,8 +817,13 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     clk_ticket = 0;
     clk_exit = 0;
   }
-  uint32_t clk_tiles = 0, clk_halves = 0;
+  uint32_t clk_halves = 0;
 #endif
+  // tiles the block kept (block-uniform): the planner's count, and its parity the LDS buffer
+  uint32_t kept = 0;
+  // (x, y) again at the publish, from LDS: held in SGPRs across the sweep they cost spills
+  __shared__ uint32_t slice_xy;
+  if (kPlan && threadIdx.x == 0) slice_xy = bs.x | (bs.y << 16);  // (visible after the boxes' barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const float r2_hi = s->r2_hi, eps = s->screen_eps_m, S = s->mfma_scale, be = s->band_e;
@@ -781,7 +837,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   QBox lq{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}, -1.0f};
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
-    const int64_t slot = q0 + (int64_t)blockIdx.x * kMQueries + (wave * kMG + g) * 32 + c;
+    const int64_t slot = q0 + (kPlan ? (int64_t)bs.x : (int64_t)blockIdx.x) * kMQueries + (wave * kMG + g) * 32 + c;
     const float X = load_query(q[g], lq, slot, h, src32, ns, s, sa, off, keys);
     if (q[g].qi >= 0) act |= 1u << g;
     if (__any(refresh_threshold(q[g], h, X, eps, S2))) force |= 1u << g;
@@ -807,7 +863,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   const QBox bx = reduce_boxes(lq, qbox, lane, wave);
   const int ntile = (int)(nt_pad / kTT);
   const ReachArgs ra{q, act, be, r2_hi, rslot, wave};
-  TileCursor cur{tbox, qbox[wave], bx, lane, ntile, (int)gridDim.y, (int)blockIdx.y, 0, 0};
+  TileCursor cur{tbox, qbox[wave], bx, lane, ntile, (int)(kPlan ? bs.S : gridDim.y), (int)(kPlan ? bs.y : blockIdx.y), 0, 0};
   cur.cull_round(ra);
   int t0, t1;
   uint32_t h0, h1;  // the wave's half-tile masks of tiles t0, t1
@@ -818,11 +874,12 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 #if M3D_NN_CLOCK
   const unsigned long long clk1 = __builtin_amdgcn_s_memrealtime();
 #endif
-  int buf = 0;
+  int tog = 0;
   for (; t0 < ntile; t0 = t1, h0 = h1) {
+    const int buf = kPlan ? (int)(kept & 1u) : tog;
     const int64_t j0 = (int64_t)t0 * kTT;
+    if (kPlan || M3D_NN_CLOCK) ++kept;
 #if M3D_NN_CLOCK
-    ++clk_tiles;
     clk_halves += (uint32_t)__builtin_popcount(h0);
 #endif
     cur.next(t1, h1, ra);
@@ -849,7 +906,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     }
     lds_dma_wait();
     __syncthreads();
-    buf ^= 1;
+    if (!kPlan) tog ^= 1;
   }
 #if M3D_NN_CLOCK
   const unsigned long long clk2 = __builtin_amdgcn_s_memrealtime();
@@ -990,6 +1047,12 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 #if M3D_NN_CLOCK
   const unsigned long long clk2b = __builtin_amdgcn_s_memrealtime();
 #endif
+  const uint32_t sxy = kPlan ? slice_xy : 0u;
+  const int64_t sxl = (int64_t)(sxy & 0xFFFFu);
+  const unsigned syl = sxy >> 16;
+// (macros, not values: the 2-D kernel reads the hardware's coordinates at each use, as before)
+#define M3D_NN_SX (kPlan ? sxl : (int64_t)blockIdx.x)
+#define M3D_NN_SY (kPlan ? syl : blockIdx.y)
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
     if (h != 0 || q[g].qi < 0) continue;
@@ -1000,13 +1063,16 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
     // would spill
     int cq = c;
     asm volatile("" : "+v"(cq));
-    const int64_t qi = q0 + (int64_t)blockIdx.x * kMQueries + (wave * kMG + g) * 32 + cq;
+    const int64_t qi = q0 + M3D_NN_SX * kMQueries + (wave * kMG + g) * 32 + cq;
 #else
     const int64_t qi = q[g].qi;
 #endif
-    const bool pk = publish_k1(sa, q[g].k1, (chg >> g) & 1u);
+    const bool pk = publish_k1(sa, M3D_NN_SY, q[g].k1, (chg >> g) & 1u);
     if (pk || q[g].n2 < kInf) near_publish((unsigned long long*)&keys[qi], &near2[qi], q[g].k1, q[g].n2, pk);
   }
+  // the tiles this block kept, into its query block's count (the planner of the fused tail reads
+  // and zeroes it): one word per block, beside the publish
+  if (kPlan && pl.cnt != nullptr && threadIdx.x == 0) atomicAdd(&pl.cnt[M3D_NN_SX], kept);
 #if M3D_NN_CLOCK
   // the block's record, written by its last wave out (LDS ticket; a wave's LDS operations execute
   // in order, so every earlier wave's maximum is in): entry, setup done, tile loop done (the
@@ -1014,7 +1080,7 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
   // the block kept, the half tiles its slowest wave swept
   {
     const unsigned long long clk3 = __builtin_amdgcn_s_memrealtime();
-    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;  // launch order in both forms
     if (lane == 0) {
       atomicMax(&clk_exit, clk3);
       if (atomicAdd(&clk_ticket, 1u) == kMBlock / 64 - 1 && blk < kClkBlocks) {
@@ -1023,15 +1089,49 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
         rec[1] = clk1;
         rec[2] = clk2;
         rec[3] = atomicMax(&clk_exit, 0ull);
-        rec[4] = clk_tiles;
+        rec[4] = kept;
         rec[5] = atomicMax(&clk_slow, 0u);
-        rec[6] = (unsigned long long)blockIdx.x | ((unsigned long long)blockIdx.y << 32);
+        rec[6] = (unsigned long long)M3D_NN_SX | ((unsigned long long)M3D_NN_SY << 32) | ((unsigned long long)cur.ty << 48);
         rec[7] = clk2b;  // the deferred passes done (the writer's own: the last wave out)
       }
     }
   }
 #endif
 }
+
+#undef M3D_NN_SX
+#undef M3D_NN_SY
+#define M3D_NN_KERNEL_ARGS                                                                            \
+  const float4 *__restrict__ src32, int64_t ns, const uint4 *__restrict__ tgt16,                      \
+      const float4 *__restrict__ tgt32, const float4 *__restrict__ tbox, int64_t nt_pad, int64_t off, \
+      const IcpState *__restrict__ s, int64_t *__restrict__ keys, uint32_t *__restrict__ near2, SeedArgs sa, int64_t q0
+#if M3D_NN_TU_MAIN
+__global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_kernel(M3D_NN_KERNEL_ARGS) {
+  nn_mfma_body<false>(src32, ns, tgt16, tgt32, tbox, nt_pad, off, s, keys, near2, sa, q0, NnPlan{nullptr, nullptr, 0, 0});
+}
+#endif
+// the planned kernel's launch (grid = the plan's budget) and its resident blocks per CU (0: unknown),
+// from whichever translation unit holds the kernel
+hipError_t launch_nn_plan_kernel(unsigned blocks, hipStream_t st, M3D_NN_KERNEL_ARGS, NnPlan pl);
+int nn_plan_kernel_blocks_per_cu();
+#if M3D_NN_TU_PLAN_KERNEL
+__global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_plan_kernel(
+    M3D_NN_KERNEL_ARGS, NnPlan pl) {
+  nn_mfma_body<true>(src32, ns, tgt16, tgt32, tbox, nt_pad, off, s, keys, near2, sa, q0, pl);
+}
+hipError_t launch_nn_plan_kernel(unsigned blocks, hipStream_t st, M3D_NN_KERNEL_ARGS, NnPlan pl) {
+  nn_mfma_plan_kernel<<<dim3(blocks), kMBlock, 0, st>>>(src32, ns, tgt16, tgt32, tbox, nt_pad, off, s, keys, near2, sa,
+                                                        q0, pl);
+  return hipGetLastError();
+}
+int nn_plan_kernel_blocks_per_cu() {
+  int per = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_plan_kernel, kMBlock, 0) != hipSuccess) return 0;
+  return per > 0 ? per : 1;
+}
+#endif
+#undef M3D_NN_KERNEL_ARGS
+#if M3D_NN_TU_MAIN
 
 // grid.y of nn_mfma_kernel for bx query blocks and ntiles target tiles (block y takes every
 // grid.y-th tile); slots = the blocks resident on the device at once, 0 = unknown.
@@ -1049,6 +1149,10 @@ __global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) vo
 // shapes only.  With few query blocks it degenerates to one tile per block (grid.x = 1 gives
 // S = ntiles, the clamp): every block then pays the setup for at most one tile.
 // Unknown slots: S0 blocks per query block, evened out to equal tile counts.
+// Since the slice plan (nn_plan.h, launch_icp_nn below) this is the DEFAULT assignment: the 2-D
+// launch's grid.y, and in the planned 1-D launch what every block derives from its index while the
+// loop state has no valid plan (the first evaluation after a reset, one-shot paths); with a plan,
+// query block x gets S_x blocks from the table instead, Σ S_x ≤ slots.
 static int64_t nn_grid_y(int64_t bx, int64_t ntiles, int64_t slots, bool cull) {
   const auto clamped = [&](int64_t S) { return std::min(std::max<int64_t>(S, 1), ntiles); };
   const int64_t s0 = clamped((2048 + bx - 1) / bx);
@@ -1098,20 +1202,71 @@ hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStrea
   const Grid* tg = s->tgrid;
   const int64_t tt = (int64_t)kTH * kMTile;
   if (!icp_nn_uses_mfma(s) || tg->mf_npad % tt != 0) return hipErrorInvalidValue;  // pack16 pads to kMTilePad
+  const int64_t slots = nn_resident_slots();
+  const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
+  const int64_t gy = nn_grid_y(bx, tg->mf_npad / tt, slots, M3D_NN_CULL != 0);
+  const SeedArgs sa{s->corr, s->tgt->xyz32, s->tgt->n, self_seed ? 1 : 0};
+  // The planned launch whenever the loop's plan can apply: the whole source, M3D_NN_PLAN on, and
+  // (nn_plan_shape, at create) resident slots known and more of them than query blocks.
+  const bool planned = nn_plan_on() && s->nn_qblocks > 0 && q0 == 0 && ns == s->src->n && bx == s->nn_qblocks &&
+                       bx * gy <= s->nn_budget;
+  if (planned)
+    return launch_nn_plan_kernel((unsigned)s->nn_budget, st, s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox,
+                                 tg->mf_npad, off, s->state, s->keys, s->near2, sa, q0,
+                                 NnPlan{s->nn_table, s->nn_cnt, (int)bx, (int)gy});
+  nn_mfma_kernel<<<dim3((unsigned)bx, (unsigned)gy), kMBlock, 0, st>>>(
+        s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox, tg->mf_npad, off, s->state, s->keys, s->near2, sa, q0);
+  return hipGetLastError();
+}
+
+int64_t nn_resident_slots() {
   static const int64_t slots = [] {
     int dev = 0, per = 0;
     hipDeviceProp_t p;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return (int64_t)0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_kernel, kMBlock, 0) != hipSuccess)
       return (int64_t)0;
-    return (int64_t)p.multiProcessorCount * (per > 0 ? per : 1);
+    // both kernels hold two blocks per CU (128 VGPRs, 67 KB of LDS); the smaller count if they ever differ
+    const int pp = nn_plan_kernel_blocks_per_cu();
+    per = per > 0 ? per : 1;
+    if (pp > 0 && pp < per) per = pp;
+    return (int64_t)p.multiProcessorCount * per;
   }();
-  const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
-  const dim3 gm((unsigned)bx, (unsigned)nn_grid_y(bx, tg->mf_npad / tt, slots, M3D_NN_CULL != 0));
-  const SeedArgs sa{s->corr, s->tgt->xyz32, s->tgt->n, self_seed ? 1 : 0};
-  nn_mfma_kernel<<<gm, kMBlock, 0, st>>>(s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox, tg->mf_npad, off,
-                                         s->state, s->keys, s->near2, sa, q0);
-  return hipGetLastError();
+  return slots;
 }
 
+// M3D_NN_PLAN=0 in the environment: every launch as the uniform 2-D one
+bool nn_plan_on() {
+  static const bool on = [] {
+    const char* e = getenv("M3D_NN_PLAN");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+
+// The plan shape of a brute-force loop over ns sources: its query blocks and the block budget (the
+// resident slots); 0 / 0 where no plan applies — slots unknown, at least as many query blocks as
+// slots (the 1M source: 1954 query blocks, uniform S = 1 stays), or more than the planner holds.
+void nn_plan_shape(int64_t ns, int32_t* qblocks, int32_t* budget) {
+  const int64_t slots = nn_resident_slots(), bx = (ns + kMQueries - 1) / kMQueries;
+  const bool ok = M3D_NN_CULL != 0 && slots > 0 && bx >= 1 && bx < slots && bx <= kPlanMaxQ && slots <= 0xFFFF;
+  *qblocks = ok ? (int32_t)bx : 0;
+  *budget = ok ? (int32_t)slots : 0;
+}
+
+PlanArgs nn_plan_args(const m3d_icp* s) {
+  PlanArgs pa;
+  if (!nn_plan_on() || s->nn_qblocks <= 0 || s->tgrid == nullptr) return pa;
+  pa.cnt = s->nn_cnt;
+  pa.seen = s->nn_seen;
+  pa.table = s->nn_table;
+  pa.n = s->nn_qblocks;
+  pa.budget = s->nn_budget;
+  pa.cap = (int32_t)plan_cap(kPlanSmax, s->tgrid->mf_npad / ((int64_t)kTH * kMTile));
+  return pa;
+}
+
+#endif  // M3D_NN_TU_MAIN
+
 }  // namespace m3d
+#endif  // this translation unit holds something

@@ -182,6 +182,9 @@ SIGNATURES = {
     "m3d_debug_acos_device": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int, vp]),
     "m3d_debug_block_cache_fill": (C.c_int, [C.c_int]),
     "m3d_debug_icp_defer_count": (C.c_int, [vp, C.c_uint32, vp]),
+    "m3d_debug_nn_plan_host": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]),
+    "m3d_debug_icp_nn_plan": (C.c_int, [vp, vp, C.c_int64, vp]),
+    "m3d_debug_icp_nn_plan_read": (C.c_int, [vp, vp, vp, vp, vp]),
     "m3d_parse_ascii_rows": (C.c_int, [C.c_char_p, C.c_size_t, i64, i32, C.POINTER(dbl),
                                        C.POINTER(C.c_size_t)]),
     "m3d_format_ascii_rows": (C.c_int, [C.POINTER(dbl), i64, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -225,7 +228,11 @@ def load() -> C.CDLL:
     if lib.m3d_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI {lib.m3d_abi_version()} != {ABI_VERSION}; rebuild it")
     for name, (res, args) in SIGNATURES.items():
-        f = getattr(lib, name)
+        f = getattr(lib, name, None)
+        if f is None and name.startswith("m3d_debug_") and os.environ.get("AB_LIB"):
+            continue  # A/B runs (AB_LIB: another build of this ABI) may lack a later diagnostic entry
+        if f is None:
+            raise ImportError(f"{LIB_PATH}: no symbol {name}; rebuild it")
         f.restype = res
         f.argtypes = args
     _lib = lib

@@ -667,6 +667,22 @@ int m3d_debug_block_cache_fill(int byte);
  * list makes the next scan drop its writes and m3d_icp_result_get fail with M3D_ERR_HIP until the
  * next m3d_icp_reset.  M3D_ERR_INVALID when the loop defers nothing.  ABI 13. */
 int m3d_debug_icp_defer_count(m3d_icp* s, uint32_t count, void* stream);
+/* The brute-force NN's slice plan, the rule on the host: counts [host] n tile
+ * counts, one per query block of 512 sources -> out [host] `budget` entries x | y << 16 | S << 24
+ * (slice y of the S slices of query block x; 0xFFFFFFFF = empty), S = clamp(ceil(t / tau), 1,
+ * min(smax, ntiles)) for the smallest tau with sum S <= budget.  Returns tau (>= 1), or
+ * M3D_ERR_INVALID (n < 1, n > budget).  Added within ABI 13, the version number is unchanged. */
+int m3d_debug_nn_plan_host(const uint32_t* counts, int64_t n, int64_t budget, int64_t smax, int64_t ntiles,
+                           uint32_t* out);
+/* Force S[x] [host, n = the loop's query blocks] slices per query block for the following
+ * evaluations of a brute-force loop, until the next m3d_icp_reset (synchronous on stream); the
+ * loop's own planner leaves a forced plan alone.  M3D_ERR_INVALID for S < 1, S > the target's
+ * tiles, sum S > the resident block slots, or a loop whose launch takes no plan.  Within ABI 13. */
+int m3d_debug_icp_nn_plan(m3d_icp* s, const int32_t* S, int64_t n, void* stream);
+/* Read a loop's plan back (synchronous): shape3 [host] = {query blocks (0: no plan), budget, flag
+ * (0 none, 1 planned, 2 forced)}; counts [host, query blocks] the tile counts the planner last
+ * read, table [host, budget] the entries; either may be NULL.  Within ABI 13. */
+int m3d_debug_icp_nn_plan_read(m3d_icp* s, uint32_t* counts, uint32_t* table, int32_t* shape3, void* stream);
 
 /* ------------------------------------------------------------------ host text I/O (§8(f) rank 4) */
 

@@ -4,7 +4,10 @@ cfg1 pair, brute force; the launch looked at is the last of `evals` evaluations 
 block the build records s_memrealtime (100 MHz, 10 ns) at entry, after the setup (queries, seeds,
 boxes, first cull round, first tile staged), after the tile loop and at the exit of its last wave,
 and when its last wave out finished the deferred exact passes, with the tiles the block kept and the
-half tiles its slowest wave swept."""
+half tiles its slowest wave swept, and its slice: query block x, slice y and — since the
+slice plan (nn_plan.h, EXPERIMENTS §R19) — the query block's slice count S (x | y << 32 | S << 48;
+a build from before the plan leaves S at 0: grid.y).  With the plan it prints the S histogram and
+the block durations against S.  M3D_NN_PLAN=0 in the environment: the uniform launch."""
 import ctypes as C
 import os
 import sys
@@ -44,8 +47,9 @@ def main():
     assert rc == 0, "m3d_debug_nn_clock failed"
     a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, CLK_WORDS).astype(np.int64)
     a = a[a[:, 3] > 0]
-    bx, by = a[:, 6] & 0xFFFFFFFF, a[:, 6] >> 32
+    bx, by, bs = a[:, 6] & 0xFFFFFFFF, (a[:, 6] >> 32) & 0xFFFF, a[:, 6] >> 48
     gx, gy = int(bx.max()) + 1, int(by.max()) + 1
+    bs = np.where(bs > 0, bs, gy)
     us = 10e-3
     t0 = a[:, 0].min()
     st, en = (a[:, 0] - t0) * us, (a[:, 3] - t0) * us
@@ -68,6 +72,13 @@ def main():
     print("durations per bin:", " ".join(f"{e:.1f}:{h}" for e, h in zip(edges[:-1], hist)))
     print(f"tiles kept per block: {stats(tiles.astype(np.float64))}")
     print(f"half tiles swept by the slowest wave: {stats(slow.astype(np.float64))}")
+    per_x = np.zeros(gx, np.int64)
+    per_x[bx] = bs
+    print("slices per query block (S: query blocks):", " ".join(f"{k}:{v}" for k, v in zip(*np.unique(per_x, return_counts=True))))
+    print("duration against S (S: blocks, mean tiles, mean duration, p99, max):")
+    for k in np.unique(bs):
+        m = bs == k
+        print(f"  {k:3d}: {m.sum():4d}  {tiles[m].mean():5.2f}  {du[m].mean():6.2f}  {np.percentile(du[m], 99):6.2f}  {du[m].max():6.2f}")
     print("duration against tiles kept (tiles: blocks, mean duration, mean tile loop, max duration):")
     for k in np.unique(tiles):
         m = tiles == k
@@ -84,7 +95,7 @@ def main():
     if len(late):
         print(f"later blocks ({len(late)}): starts {stats(st[late])}; ends {stats(en[late])}")
     k = int(np.argmax(en))
-    print(f"the launch ends with block ({bx[k]}, {by[k]}): start {st[k]:.2f}, duration {du[k]:.2f} "
+    print(f"the launch ends with block ({bx[k]}, {by[k]}) of S = {bs[k]}: start {st[k]:.2f}, duration {du[k]:.2f} "
           f"(setup {setup[k]:.2f}, loop {loop[k]:.2f}, rest {rest[k]:.2f}), tiles {tiles[k]}, slowest wave {slow[k]} halves")
     hist, edges = np.histogram(en, bins=12)
     print("ends per bin:  ", " ".join(f"{e:.1f}:{h}" for e, h in zip(edges[:-1], hist)))
