@@ -2440,6 +2440,35 @@ int m3d_segment_plane(m3d_ctx* ctx, const m3d_cloud* cloud, const m3d_plane_para
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- DBSCAN
+// cluster.hip; the grid of cell eps cached on the cloud, scratch from the preprocessing buffer
+int m3d_cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* cloud, double eps, int32_t min_points,
+                       int32_t* labels_out, m3d_dbscan_result* out, int32_t* sizes_out, int32_t* count_out,
+                       void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && out && (labels_out || cloud->n == 0), "invalid arguments");
+  CHECK_ARG(ctx, std::isfinite(eps) && eps > 0.0 && min_points >= 1,
+            "cluster_dbscan: eps must be finite and > 0, min_points >= 1");
+  *out = m3d_dbscan_result{0, 0, 0, -1, 0};
+  if (cloud->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const Grid* g = nullptr;
+  int rc = ensure_grid(ctx, cloud, eps, st, &g);
+  if (rc) return rc;
+  char* scratch = nullptr;
+  rc = prep_buffer(ctx, cluster_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  hipError_t e = cluster_dbscan(ctx, cloud, g, eps, min_points, labels_out, out, sizes_out, count_out, scratch, st, &why);
+  if (e != hipSuccess) {
+    *out = m3d_dbscan_result{0, 0, 0, -1, 0};
+    return clean_fail(ctx, "cluster_dbscan", e, why);
+  }
+  return M3D_OK;
+}
+
 // ------------------------------------------------------------------------------- feature matching
 int m3d_feature_correspondences(m3d_ctx* ctx, const double* f_src, int64_t ns, const double* f_tgt,
                                 int64_t nt, int32_t dim, int32_t mutual_filter,

@@ -610,13 +610,9 @@ hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double 
   return select_kept(keep, n, index_out, n_out, S, L, st);  // syncs: stats_out is complete too
 }
 
-hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius,
-                           int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
-                           hipStream_t st) {
+hipError_t radius_flags(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius, int32_t* count_out,
+                        uint8_t* keep, hipStream_t st) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const CleanScratch L = clean_layout(n);
-  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
   const float Rf = box_half_width(c, radius);
   const double r2 = radius * radius;
   const float bf = prefilter_bound(r2, pair_eabs(c));  // the threshold is r² throughout: one bound
@@ -627,7 +623,17 @@ hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points,
   else
     radius_count_kernel<false><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf,
                                                               nb_points, nullptr, keep);
-  hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius,
+                           int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
+                           hipStream_t st) {
+  const int64_t n = c->n;
+  char* S = static_cast<char*>(scratch);
+  const CleanScratch L = clean_layout(n);
+  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
+  hipError_t e = radius_flags(c, g, nb_points, radius, count_out, keep, st);
   if (e != hipSuccess) return e;
   return select_kept(keep, n, index_out, n_out, S, L, st);
 }

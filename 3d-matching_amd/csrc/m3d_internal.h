@@ -627,6 +627,17 @@ hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double 
 hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius,
                            int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
                            hipStream_t st);
+// the radius filter's count pass alone (enqueue only): keep[i] = #{j : d²(i, j) < radius²} > nb_points,
+// one wave per point; count_out [device] n int32 (the full counts) or null (a count stops there)
+hipError_t radius_flags(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius, int32_t* count_out,
+                        uint8_t* keep, hipStream_t st);
+// DBSCAN (cluster.hip).  g: the cloud's grid of cell `eps`; n ≥ 1; scratch: cluster_scratch_bytes(n)
+// bytes; sizes_out / count_out [device] or null.  Returns after a stream sync.  why: the message of a
+// failure that is not a HIP error (hipErrorUnknown).
+size_t cluster_scratch_bytes(int64_t n);
+hipError_t cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* c, const Grid* g, double eps, int32_t min_points,
+                          int32_t* labels_out, m3d_dbscan_result* out, int32_t* sizes_out, int32_t* count_out,
+                          void* scratch, hipStream_t st, std::string* why);
 // plane segmentation (plane.hip).  kPlaneChunk points per chunk of the score kernel (a constant of
 // the library: a plane's err bits depend on n alone); a launch scores at most plane_batch_cap(n)
 // planes (its per-chunk partials stay within a fixed budget).

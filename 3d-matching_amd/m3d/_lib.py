@@ -97,6 +97,11 @@ class PlaneResult(C.Structure):
                 ("best_count", i64), ("evaluated", i64), ("iterations", i64), ("best_rmse", dbl)]
 
 
+class DbscanResult(C.Structure):
+    _fields_ = [("num_clusters", i64), ("num_core", i64), ("num_noise", i64), ("largest_label", i64),
+                ("largest_size", i64)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "m3d_abi_version": (C.c_int, []),
@@ -164,6 +169,7 @@ SIGNATURES = {
     "m3d_segment_plane": (C.c_int, [vp, vp, C.POINTER(PlaneParams), vp, C.POINTER(PlaneResult), vp, vp, vp, vp]),
     "m3d_plane_score": (C.c_int, [vp, vp, vp, i64, dbl, vp, vp, vp]),
     "m3d_plane_chunk": (i32, []),
+    "m3d_cluster_dbscan": (C.c_int, [vp, vp, dbl, i32, vp, C.POINTER(DbscanResult), vp, vp, vp]),
     "m3d_feature_correspondences": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, dbl, vp,
                                               C.POINTER(i64), vp]),
     "m3d_ransac_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FeatureRansacParams),

@@ -14,6 +14,7 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``pcd.remove_statistical_outlier(nb, ratio)`` (users)    | ``remove_statistical_outlier``    |
 | ``pcd.remove_radius_outlier(nb, r)`` (users)             | ``remove_radius_outlier``         |
 | ``pcd.segment_plane(thr, ransac_n, iterations)`` (users) | ``segment_plane``, ``plane_score`` |
+| ``pcd.cluster_dbscan(eps, min_points)`` (users)          | ``cluster_dbscan``                |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -227,6 +228,45 @@ def plane_score(points, planes, distance_threshold: float):
     ctx.check(ctx.lib.m3d_plane_score(ctx.h, c.h, ptr(pl), H, float(distance_threshold), ptr(cnt), ptr(err),
                                       stream_handle()), "plane_score")
     return cnt[:H].cpu().numpy(), err[:H].cpu().numpy()
+
+
+@dataclass
+class DbscanOutcome:
+    """What ``cluster_dbscan`` found besides the labels."""
+    num_clusters: int
+    num_core: int
+    num_noise: int
+    largest_label: int   # the biggest cluster, the lowest label on ties; −1 without a cluster
+    largest_size: int
+    sizes: np.ndarray    # int32 (num_clusters,): members per label
+    counts: np.ndarray   # int32 (n,): every point's full neighbour count, itself included
+
+
+def cluster_dbscan(points, eps: float, min_points: int, *, with_details: bool = False):
+    """PointCloud::ClusterDBSCAN on the device (m3d_cluster_dbscan; the contract is in include/m3d.h)
+    → labels int32 (n,), −1 = noise; ``with_details=True`` → (labels, ``DbscanOutcome``)."""
+    if not (np.isfinite(float(eps)) and float(eps) > 0.0):
+        raise ValueError("cluster_dbscan: eps must be finite and > 0")
+    if int(min_points) < 1:
+        raise ValueError("cluster_dbscan: min_points >= 1")
+    if _empty(points):  # an empty cloud gives an empty result, no device involved
+        labels = np.zeros(0, np.int32)
+        return (labels, DbscanOutcome(0, 0, 0, -1, 0, np.zeros(0, np.int32), np.zeros(0, np.int32))) \
+            if with_details else labels
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    lab = device_empty((c.n,), torch.int32)
+    sizes = device_empty((c.n,), torch.int32) if with_details else None
+    cnt = device_empty((c.n,), torch.int32) if with_details else None
+    r = _lib.DbscanResult()
+    ctx.check(ctx.lib.m3d_cluster_dbscan(ctx.h, c.h, float(eps), int(min_points), ptr(lab), C.byref(r), ptr(sizes),
+                                         ptr(cnt), stream_handle()), "cluster_dbscan")
+    labels = lab.cpu().numpy()
+    if not with_details:
+        return labels
+    return labels, DbscanOutcome(int(r.num_clusters), int(r.num_core), int(r.num_noise), int(r.largest_label),
+                                 int(r.largest_size), sizes[: int(r.num_clusters)].cpu().numpy(), cnt.cpu().numpy())
 
 
 def estimate_normals(points, radius: float, max_nn: int = 30, normals=None):

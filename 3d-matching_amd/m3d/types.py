@@ -98,6 +98,13 @@ class PointCloud:
 
         return segment_plane(self.points, distance_threshold, ransac_n, num_iterations, probability)
 
+    def cluster_dbscan(self, eps: float, min_points: int, print_progress: bool = False):
+        """Open3D ``PointCloud.cluster_dbscan`` on the device (m3d.prep) → labels int32 (n,), −1 =
+        noise (``print_progress`` is accepted and ignored)."""
+        from .prep import cluster_dbscan
+
+        return cluster_dbscan(self.points, eps, min_points)
+
     def transform(self, T):
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]

@@ -12,6 +12,10 @@ by the device path of ``m3d.prep``:
    ``ransac_n``, ``num_iterations``, ``probability``, ``seed`` drops the inliers of Open3D's
    ``segment_plane`` (the table or floor a scanned part stands on) from ``pcd`` after 1a;
    ``plane_model`` and ``plane_removed`` keep the plane and the number of points dropped
+1c. optional, not in the reference: ``keep_cluster`` = ``{"eps", "min_points"}`` keeps the largest
+   cluster of Open3D's ``cluster_dbscan`` (the object, without the clamp, the hand and the plane's
+   leftover rim) after 1b; ``cluster_label``, ``cluster_size`` and ``num_clusters`` keep what was
+   found; no cluster at all is a ``ValueError``
 2. ``pcd_down`` = voxel down-sample (voxel_size); file normals, when present, are averaged
    per voxel like Open3D's VoxelDownSample                                           ply.py:106
 3. ``pcd_down`` normals: hybrid search (2·v, 30), oriented by those averaged normals ply.py:110-112
@@ -37,7 +41,7 @@ from m3d.types import Feature, PointCloud
 
 class Ply:
     def __init__(self, path, voxel_size: float = 0.3, remove_outliers: dict | None = None,
-                 remove_plane: dict | None = None) -> None:
+                 remove_plane: dict | None = None, keep_cluster: dict | None = None) -> None:
         self.path = Path(path)
         self.voxel_size = voxel_size
         if not self.path.exists():
@@ -52,7 +56,7 @@ class Ply:
         if len(pts) == 0:
             raise ValueError(f"Point cloud is empty: {self.path}")          # ply.py:81-84
         self.pcd = PointCloud(pts, nrm)
-        self._preprocess(voxel_size, remove_outliers, remove_plane)
+        self._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster)
 
     def _remove_outliers(self, params: dict) -> None:
         """``pcd`` ← the points (and file normals) one of Open3D's two outlier filters keeps."""
@@ -83,8 +87,22 @@ class Ply:
         self.plane_removed = len(inliers)
         self.pcd = self.pcd.select_by_index(inliers, invert=True)
 
+    def _keep_cluster(self, params: dict) -> None:
+        """``pcd`` ← the points (and file normals) of the largest DBSCAN cluster."""
+        from m3d import prep
+
+        if set(params) != {"eps", "min_points"}:
+            raise ValueError("keep_cluster: {'eps', 'min_points'}")
+        labels, out = prep.cluster_dbscan(self.pcd.points, params["eps"], params["min_points"], with_details=True)
+        if out.num_clusters == 0:
+            raise ValueError("keep_cluster: no cluster found (every point is noise)")
+        self.cluster_label = out.largest_label
+        self.cluster_size = out.largest_size
+        self.num_clusters = out.num_clusters
+        self.pcd = self.pcd.select_by_index(np.flatnonzero(labels == out.largest_label))
+
     def _preprocess(self, voxel_size: float, remove_outliers: dict | None = None,
-                    remove_plane: dict | None = None) -> None:
+                    remove_plane: dict | None = None, keep_cluster: dict | None = None) -> None:
         """ply.py:53-66.  Wall time of each stage lands in ``stage_ms`` (every stage returns host
         arrays, so the device work is complete when its timer stops)."""
         from m3d import prep
@@ -108,6 +126,9 @@ class Ply:
         if remove_plane is not None:
             self._remove_plane(remove_plane)
             lap("remove_plane")
+        if keep_cluster is not None:
+            self._keep_cluster(keep_cluster)
+            lap("keep_cluster")
         # the full cloud goes to the device once (down-sampling, then its normals), the
         # down-sampled one once (its normals, then FPFH: the noise is added after, ply.py:61-62)
         p_dev = to_device(self.pcd.points)
@@ -132,13 +153,13 @@ class Ply:
     @classmethod
     def from_arrays(cls, points, normals=None, points_down=None, fpfh=None, voxel_size: float = 0.3,
                     preprocess: bool = False, remove_outliers: dict | None = None,
-                    remove_plane: dict | None = None):
+                    remove_plane: dict | None = None, keep_cluster: dict | None = None):
         obj = cls.__new__(cls)
         obj.path = None
         obj.voxel_size = voxel_size
         obj.pcd = PointCloud(points, normals)
         if preprocess:
-            obj._preprocess(voxel_size, remove_outliers, remove_plane)
+            obj._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster)
             return obj
         obj.pcd_down = PointCloud(points if points_down is None else points_down)
         obj.pcd_fpfh = None if fpfh is None else Feature(np.asarray(fpfh, np.float64))

@@ -595,6 +595,36 @@ int m3d_plane_score(m3d_ctx* ctx, const m3d_cloud* cloud, const double* planes, 
  * sequential sum inside a chunk, the chunk sums are added in a fixed order) */
 int32_t m3d_plane_chunk(void);
 
+/* ------------------------------------------------------------------ DBSCAN clustering (cluster.hip)
+ * PointCloud::ClusterDBSCAN(eps, min_points) (Open3D 0.19) — what is left of a scan once its support
+ * plane is gone, split into the object and the rest.
+ *   nbs[i] = {j : d²(i, j) < eps²}: strict, the point itself included,
+ *            d² = (dx·dx + dy·dy) + dz·dz in fp64 on the cloud's original coordinates
+ *   core[i] = |nbs[i]| >= min_points
+ * Open3D labels the points in index order, growing a cluster from every still unlabelled core
+ * point through the neighbourhoods of the core points it reaches; whatever order its set pops in,
+ * the labels are
+ *   core point:   the rank of its connected component in the graph on the core points whose edges
+ *                 join core pairs with d² < eps², components ranked by their smallest member index
+ *   border point: (not core, at least one core point in nbs) the smallest label among its core
+ *                 neighbours
+ *   other points: −1 (noise)
+ * and these are what the device computes (three box scans on the grid of cell eps and a lock-free
+ * union–find with integer atomics only: repeated calls return the same bits).  The grid is cached
+ * on the cloud like the radius filter's. */
+typedef struct {
+  int64_t num_clusters, num_core, num_noise;
+  int64_t largest_label;  /* biggest cluster, lowest label on ties; -1 without a cluster */
+  int64_t largest_size;
+} m3d_dbscan_result;
+/* labels_out [device] n int32 (-1 = noise); sizes_out [device] room for n int32 or NULL
+ * (entries [0, num_clusters) are written); count_out [device] n int32 or NULL: every point's full
+ * neighbour count (NULL: a count stops at min_points).  n == 0: zeros, no device work.
+ * M3D_ERR_INVALID: eps not finite or <= 0, min_points < 1.  Synchronous. */
+int m3d_cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* cloud, double eps, int32_t min_points,
+                       int32_t* labels_out, m3d_dbscan_result* out, int32_t* sizes_out,
+                       int32_t* count_out, void* stream);
+
 /* ------------------------------------------------------------------ feature matching (a5, a6) */
 
 /* CorrespondencesFromFeatures (src/matcher/ransac.py:85): exact fp64 1-NN in feature space
