@@ -2469,6 +2469,80 @@ int m3d_cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* cloud, double eps, int32_t
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- ISS keypoints
+// iss.hip (clean.hip for the resolution); the grids of cell salient_radius / non_max_radius cached
+// on the cloud, scratch from the preprocessing buffer
+int m3d_model_resolution(m3d_ctx* ctx, const m3d_cloud* cloud, double* res_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && res_out, "invalid arguments");
+  *res_out = 0.0;
+  if (cloud->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  char* scratch = nullptr;
+  int rc = prep_buffer(ctx, clean_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  hipError_t e = model_resolution(ctx, cloud, res_out, scratch, st, &why);
+  if (e != hipSuccess) {
+    *res_out = 0.0;
+    return clean_fail(ctx, "model_resolution", e, why);
+  }
+  return M3D_OK;
+}
+
+int m3d_compute_iss_keypoints(m3d_ctx* ctx, const m3d_cloud* cloud, const m3d_iss_params* params,
+                              m3d_iss_result* out, int32_t* index_out, double* third_out, int32_t* count_out,
+                              void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && params && out && (index_out || cloud->n == 0), "invalid arguments");
+  double rs = params->salient_radius, rn = params->non_max_radius;
+  CHECK_ARG(ctx, std::isfinite(rs) && rs >= 0.0 && std::isfinite(rn) && rn >= 0.0,
+            "compute_iss_keypoints: the radii must be finite and >= 0");
+  CHECK_ARG(ctx, std::isfinite(params->gamma_21) && std::isfinite(params->gamma_32) && params->min_neighbors >= 0,
+            "compute_iss_keypoints: the gammas must be finite, min_neighbors >= 0");
+  *out = m3d_iss_result{0, 0, 0, rs, rn, 0.0};
+  const int64_t n = cloud->n;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const size_t clean_bytes = clean_scratch_bytes(n);
+  char* scratch = nullptr;
+  int rc = prep_buffer(ctx, clean_bytes + iss_scratch_bytes(n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  if (rs == 0.0 || rn == 0.0) {
+    double res = 0.0;
+    hipError_t e = model_resolution(ctx, cloud, &res, scratch, st, &why);
+    if (e != hipSuccess) return clean_fail(ctx, "compute_iss_keypoints (model resolution)", e, why);
+    rs = 6.0 * res;
+    rn = 4.0 * res;
+    out->resolution = res;
+    out->salient_radius = rs;
+    out->non_max_radius = rn;
+  }
+  if (!(rs > 0.0 && rn > 0.0) || !std::isfinite(rs)) {  // coincident points (or one): nothing is salient
+    if (third_out) HIPX(ctx, hipMemsetAsync(third_out, 0, sizeof(double) * (size_t)n, st));
+    if (count_out) HIPX(ctx, hipMemsetAsync(count_out, 0, sizeof(int32_t) * (size_t)n, st));
+    HIPX(ctx, hipStreamSynchronize(st));
+    return M3D_OK;
+  }
+  const Grid *gs = nullptr, *gn = nullptr;
+  if ((rc = ensure_grid(ctx, cloud, rs, st, &gs)) != 0) return rc;
+  if ((rc = ensure_grid(ctx, cloud, rn, st, &gn)) != 0) return rc;
+  int64_t tally[3] = {0, 0, 0};
+  hipError_t e = iss_keypoints(ctx, cloud, gs, gn, rs, rn, params->gamma_21, params->gamma_32,
+                               params->min_neighbors, index_out, third_out, count_out, tally, scratch + clean_bytes,
+                               scratch, st);
+  if (e != hipSuccess) return clean_fail(ctx, "compute_iss_keypoints", e, why);
+  out->num_keypoints = tally[0];
+  out->num_salient = tally[1];
+  out->num_counted = tally[2];
+  return M3D_OK;
+}
+
 // ------------------------------------------------------------------------------- feature matching
 int m3d_feature_correspondences(m3d_ctx* ctx, const double* f_src, int64_t ns, const double* f_tgt,
                                 int64_t nt, int32_t dim, int32_t mutual_filter,
@@ -2635,6 +2709,12 @@ int m3d_debug_kabsch3_host(const double* src9, const double* tgt9, double* T16) 
 int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6) {
   if (!A36 || !b6 || !x6) return M3D_ERR_INVALID;
   if (!ldlt6_solve_spd(A36, b6, x6)) ldlt6_solve(A36, b6, x6);  // the device solve's rule (icp.hip)
+  return M3D_OK;
+}
+
+int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3) {
+  if (!sym6 || !lam3) return M3D_ERR_INVALID;
+  sym3_eigenvalues(sym6[0], sym6[1], sym6[2], sym6[3], sym6[4], sym6[5], lam3);
   return M3D_OK;
 }
 

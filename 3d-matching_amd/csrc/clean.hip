@@ -274,6 +274,37 @@ __global__ __launch_bounds__(kCleanBlock) void stat_flag_kernel(const double* __
   keep[i] = (a > 0.0 && a < stats[3]) ? 1 : 0;
 }
 
+// Σ 2·avg over ALL n points (model_resolution: avg at k = 2 is half the distance to the nearest other
+// point, doubling it is exact; a duplicate's 0 is a term like any other), the blocks of
+// stat_partial_kernel; then res = the partials' fixed-order sum / n → stats[0]
+__global__ __launch_bounds__(kCleanBlock) void res_partial_kernel(const double* __restrict__ avg, int64_t n,
+                                                                  double* __restrict__ partials) {
+  __shared__ double red[kCleanBlock / kWave];
+  const int64_t i = (int64_t)blockIdx.x * kCleanBlock + threadIdx.x;
+  const double t = cl_wave_sum(i < n ? 2.0 * avg[i] : 0.0);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < kCleanBlock / kWave; ++k) s += red[k];
+    partials[blockIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(kCleanBlock) void res_final_kernel(const double* __restrict__ partials, int64_t nb,
+                                                                int64_t n, double* __restrict__ stats) {
+  __shared__ double red[kCleanBlock];
+  double v = 0.0;
+  for (int64_t b = threadIdx.x; b < nb; b += kCleanBlock) v += partials[b];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = kCleanBlock / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) stats[0] = red[0] / (double)n;
+}
+
 // ------------------------------------------------------------------------------- host side
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -608,6 +639,29 @@ hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double 
   if ((e = hipMemcpyAsync(stats_out, stats, sizeof(double) * kStatWords, hipMemcpyDeviceToHost, st)) != hipSuccess)
     return e;
   return select_kept(keep, n, index_out, n_out, S, L, st);  // syncs: stats_out is complete too
+}
+
+hipError_t model_resolution(m3d_ctx* ctx, const m3d_cloud* c, double* res_out, void* scratch, hipStream_t st,
+                            std::string* why) {
+  const int64_t n = c->n;
+  char* S = static_cast<char*>(scratch);
+  const CleanScratch L = clean_layout(n);
+  double* avg = reinterpret_cast<double*>(S + L.avg);
+  hipError_t e = knn_ladder(ctx, c, 2, nullptr, nullptr, nullptr, avg, S, L, st, why);
+  if (e != hipSuccess) return e;
+  double* partials = reinterpret_cast<double*>(S + L.partials);
+  double* stats = reinterpret_cast<double*>(S + L.stats);
+  const unsigned nb = (unsigned)((n + kCleanBlock - 1) / kCleanBlock);
+  res_partial_kernel<<<nb, kCleanBlock, 0, st>>>(avg, n, partials);
+  res_final_kernel<<<1, kCleanBlock, 0, st>>>(partials, (int64_t)nb, n, stats);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(res_out, stats, sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  return hipStreamSynchronize(st);
+}
+
+hipError_t select_flagged(const uint8_t* keep, int64_t n, int32_t* index_out, int64_t* n_out, void* scratch,
+                          hipStream_t st) {
+  return select_kept(keep, n, index_out, n_out, static_cast<char*>(scratch), clean_layout(n), st);
 }
 
 hipError_t radius_flags(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius, int32_t* count_out,

@@ -60,7 +60,7 @@ __host__ __device__ __forceinline__ float prefilter_bound(double thr, double e) 
   float f = (float)b2;  // to nearest, then up if that fell below
   if ((double)f < b2) f = std::nextafter(f, INFINITY);
 #endif
-  return isfinite(f) ? f : FLT_MAX;
+  return std::isfinite(f) ? f : FLT_MAX;
 }
 
 // lane l ← lane l − 1 across the whole wave (gfx9 DPP wave_shr:1; lane 0 keeps `old`): a VALU

@@ -11,6 +11,8 @@
 //  * ldlt6_solve: Eigen::LDLT (diagonal pivoting; zero pivots give zero components) as used by
 //      Open3D SolveLinearSystemPSD(JTJ, -JTr); ldlt6_solve_spd: the same system unpivoted,
 //      for full-rank JTJ (the device solve's fast path, falling back to ldlt6_solve).
+//  * sym3_eigenvalues: the three eigenvalues of a symmetric 3×3 by cyclic Jacobi (the covariance
+//      of an ISS neighbourhood, iss.hip): a few ulps of the norm, exact zeros for a zero block.
 //  * vec6_to_matrix: Open3D TransformVector6dToMatrix4d, R = Rz(x2)·Ry(x1)·Rx(x0).
 #pragma once
 
@@ -177,6 +179,56 @@ M3D_HD void swapd(double& a, double& b) {
   const double t = a;
   a = b;
   b = t;
+}
+
+// One Jacobi rotation of a symmetric 3×3 held in six scalars: zeroes a_pq; (arp, arq) are the two
+// other off-diagonal entries a_rp, a_rq.  An a_pq that no longer changes either diagonal entry is
+// dropped (Rutishauser's test); an exact zero costs nothing and touches nothing.
+M3D_HD void jacobi3_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+  if (apq == 0.0) return;
+  const double g = 100.0 * fabs(apq);
+  if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
+    apq = 0.0;
+    return;
+  }
+  const double h = aqq - app;
+  double t;
+  if (fabs(h) + g == fabs(h)) {
+    t = apq / h;
+  } else {
+    const double theta = 0.5 * h / apq;
+    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+    if (theta < 0.0) t = -t;
+  }
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double rp = arp, rq = arq;
+  arp = c * rp - s * rq;
+  arq = s * rp + c * rq;
+}
+
+// The three eigenvalues of the symmetric 3×3 (a00 a01 a02; · a11 a12; · · a22), ascending, by cyclic
+// Jacobi: every rotation is an orthogonal similarity, so the error is a few ulps of the norm
+// whatever the ratio of the eigenvalues (the trigonometric closed form loses λ0 ≪ λ2).  A
+// block-diagonal matrix stays block-diagonal — an exact zero row / column gives an exact zero
+// eigenvalue.  Scalars only: nothing here is indexed at run time.  The sweeps are bounded; the
+// convergence is quadratic (three to five sweeps in practice).
+M3D_HD void sym3_eigenvalues(double a00, double a01, double a02, double a11, double a12, double a22,
+                             double lam[3]) {
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
+    jacobi3_rotate(a00, a11, a01, a02, a12);
+    jacobi3_rotate(a00, a22, a02, a01, a12);
+    jacobi3_rotate(a11, a22, a12, a01, a02);
+  }
+  if (a11 < a00) swapd(a00, a11);
+  if (a22 < a11) swapd(a11, a22);
+  if (a11 < a00) swapd(a00, a11);
+  lam[0] = a00;
+  lam[1] = a11;
+  lam[2] = a22;
 }
 
 // Eigen::LDLT-style solve of a symmetric 6×6 system A x = b (A row-major, full).

@@ -631,6 +631,23 @@ hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points,
 // one wave per point; count_out [device] n int32 (the full counts) or null (a count stops there)
 hipError_t radius_flags(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius, int32_t* count_out,
                         uint8_t* keep, hipStream_t st);
+// Open3D ComputeModelResolution: the mean over all n points of the distance to the nearest other
+// point (the ladder at k = 2, a fixed-order sum); n ≥ 1, scratch: clean_scratch_bytes(n).  Synchronous.
+hipError_t model_resolution(m3d_ctx* ctx, const m3d_cloud* c, double* res_out, void* scratch, hipStream_t st,
+                            std::string* why);
+// keep flags → the ascending kept indices and their number (the filters' stable compaction);
+// scratch: clean_scratch_bytes(n).  Synchronous.
+hipError_t select_flagged(const uint8_t* keep, int64_t n, int32_t* index_out, int64_t* n_out, void* scratch,
+                          hipStream_t st);
+// ISS keypoints (iss.hip).  gs / gn: the cloud's grids of cell rs / rn (both radii > 0, n ≥ 1);
+// scratch: iss_scratch_bytes(n), clean_scratch: clean_scratch_bytes(n); third_out / count_out
+// [device] or null; tally[3] = keypoints, points with third > 0, points with count ≥ min_neighbors.
+// Returns after a stream sync.
+size_t iss_scratch_bytes(int64_t n);
+hipError_t iss_keypoints(m3d_ctx* ctx, const m3d_cloud* c, const Grid* gs, const Grid* gn, double rs, double rn,
+                         double gamma_21, double gamma_32, int32_t min_neighbors, int32_t* index_out,
+                         double* third_out, int32_t* count_out, int64_t tally[3], void* scratch,
+                         void* clean_scratch, hipStream_t st);
 // DBSCAN (cluster.hip).  g: the cloud's grid of cell `eps`; n ≥ 1; scratch: cluster_scratch_bytes(n)
 // bytes; sizes_out / count_out [device] or null.  Returns after a stream sync.  why: the message of a
 // failure that is not a HIP error (hipErrorUnknown).

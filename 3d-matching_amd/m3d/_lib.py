@@ -102,6 +102,16 @@ class DbscanResult(C.Structure):
                 ("largest_size", i64)]
 
 
+class IssParams(C.Structure):
+    _fields_ = [("salient_radius", dbl), ("non_max_radius", dbl), ("gamma_21", dbl), ("gamma_32", dbl),
+                ("min_neighbors", i32)]
+
+
+class IssResult(C.Structure):
+    _fields_ = [("num_keypoints", i64), ("num_salient", i64), ("num_counted", i64), ("salient_radius", dbl),
+                ("non_max_radius", dbl), ("resolution", dbl)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "m3d_abi_version": (C.c_int, []),
@@ -170,6 +180,8 @@ SIGNATURES = {
     "m3d_plane_score": (C.c_int, [vp, vp, vp, i64, dbl, vp, vp, vp]),
     "m3d_plane_chunk": (i32, []),
     "m3d_cluster_dbscan": (C.c_int, [vp, vp, dbl, i32, vp, C.POINTER(DbscanResult), vp, vp, vp]),
+    "m3d_model_resolution": (C.c_int, [vp, vp, C.POINTER(dbl), vp]),
+    "m3d_compute_iss_keypoints": (C.c_int, [vp, vp, C.POINTER(IssParams), C.POINTER(IssResult), vp, vp, vp, vp]),
     "m3d_feature_correspondences": (C.c_int, [vp, vp, i64, vp, i64, i32, i32, dbl, vp,
                                               C.POINTER(i64), vp]),
     "m3d_ransac_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FeatureRansacParams),
@@ -200,6 +212,7 @@ SIGNATURES = {
     "m3d_debug_xxh3_128": (C.c_int, [vp, C.c_size_t, C.POINTER(u64)]),
     "m3d_debug_kabsch3_host":(C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_ldlt6_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
+    "m3d_debug_sym3_eigenvalues_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl)]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``pcd.remove_radius_outlier(nb, r)`` (users)             | ``remove_radius_outlier``         |
 | ``pcd.segment_plane(thr, ransac_n, iterations)`` (users) | ``segment_plane``, ``plane_score`` |
 | ``pcd.cluster_dbscan(eps, min_points)`` (users)          | ``cluster_dbscan``                |
+| ``keypoint.compute_iss_keypoints(pcd, ...)`` (users)     | ``compute_iss_keypoints``, ``model_resolution`` |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -267,6 +268,66 @@ def cluster_dbscan(points, eps: float, min_points: int, *, with_details: bool = 
         return labels
     return labels, DbscanOutcome(int(r.num_clusters), int(r.num_core), int(r.num_noise), int(r.largest_label),
                                  int(r.largest_size), sizes[: int(r.num_clusters)].cpu().numpy(), cnt.cpu().numpy())
+
+
+def model_resolution(points) -> float:
+    """Open3D ``ComputeModelResolution`` on the device (m3d_model_resolution): the mean distance to
+    the nearest other point; 0.0 for an empty cloud or a single point."""
+    if not isinstance(points, Cloud):
+        shape = tuple(points.shape) if hasattr(points, "shape") else np.shape(points)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("model_resolution: points must be (n, 3)")
+    if _empty(points):
+        return 0.0
+    c = _cloud(points)
+    ctx = c.ctx
+    res = C.c_double(0.0)
+    ctx.check(ctx.lib.m3d_model_resolution(ctx.h, c.h, C.byref(res), stream_handle()), "model_resolution")
+    return float(res.value)
+
+
+@dataclass
+class IssOutcome:
+    """What ``compute_iss_keypoints`` found besides the keypoint indices."""
+    num_keypoints: int
+    num_salient: int       # points with third_eigen_values > 0: the candidates of the non-maximum pass
+    num_counted: int       # points with count >= min_neighbors
+    salient_radius: float  # as used
+    non_max_radius: float
+    resolution: float      # 0.0 when both radii were given
+    third_eigen_values: np.ndarray  # float64 (n,): the smallest eigenvalue of a salient point, else 0
+    counts: np.ndarray     # int32 (n,): points strictly within salient_radius, the point itself included
+
+
+def compute_iss_keypoints(points, salient_radius: float = 0.0, non_max_radius: float = 0.0, gamma_21: float = 0.975,
+                          gamma_32: float = 0.975, min_neighbors: int = 5, *, with_details: bool = False):
+    """keypoint::ComputeISSKeypoints on the device (m3d_compute_iss_keypoints; the contract is in
+    include/m3d.h) → keypoint indices int64, ascending; ``with_details=True`` → (indices, ``IssOutcome``)."""
+    rs, rn, g21, g32 = float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32)
+    if not (np.isfinite(rs) and rs >= 0.0 and np.isfinite(rn) and rn >= 0.0):
+        raise ValueError("compute_iss_keypoints: the radii must be finite and >= 0")
+    if not (np.isfinite(g21) and np.isfinite(g32)):
+        raise ValueError("compute_iss_keypoints: the gammas must be finite")
+    if int(min_neighbors) < 0:
+        raise ValueError("compute_iss_keypoints: min_neighbors >= 0")
+    if _empty(points):  # an empty cloud gives an empty result, no device involved
+        idx = np.zeros(0, np.int64)
+        return (idx, IssOutcome(0, 0, 0, rs, rn, 0.0, np.zeros(0), np.zeros(0, np.int32))) if with_details else idx
+    torch = _torch()
+    c = _cloud(points)
+    ctx = c.ctx
+    ind = device_empty((c.n,), torch.int32)
+    third = device_empty((c.n,), torch.float64) if with_details else None
+    cnt = device_empty((c.n,), torch.int32) if with_details else None
+    p = _lib.IssParams(rs, rn, g21, g32, int(min_neighbors))
+    r = _lib.IssResult()
+    ctx.check(ctx.lib.m3d_compute_iss_keypoints(ctx.h, c.h, C.byref(p), C.byref(r), ptr(ind), ptr(third), ptr(cnt),
+                                                stream_handle()), "compute_iss_keypoints")
+    idx = ind[: int(r.num_keypoints)].cpu().numpy().astype(np.int64)
+    if not with_details:
+        return idx
+    return idx, IssOutcome(int(r.num_keypoints), int(r.num_salient), int(r.num_counted), float(r.salient_radius),
+                           float(r.non_max_radius), float(r.resolution), third.cpu().numpy(), cnt.cpu().numpy())
 
 
 def estimate_normals(points, radius: float, max_nn: int = 30, normals=None):

@@ -21,6 +21,12 @@ by the device path of ``m3d.prep``:
 3. ``pcd_down`` normals: hybrid search (2·v, 30), oriented by those averaged normals ply.py:110-112
 4. ``pcd_fpfh`` = FPFH on ``pcd_down`` (hybrid 5·v, 100) — an Open3D-style ``Feature``
    (``.data`` 33×N)                                                                  ply.py:117-120
+4a. optional, not in the reference: ``keypoints`` = any subset of ``{"salient_radius",
+   "non_max_radius", "gamma_21", "gamma_32", "min_neighbors"}`` (``{}``: Open3D's defaults) keeps
+   only the ISS keypoints of ``pcd_down`` (Open3D's ``compute_iss_keypoints``) in ``pcd_down`` and
+   ``pcd_fpfh``; the FPFH rows are still computed on the whole down-sampled cloud, as users do.
+   ``keypoint_indices`` (into the down-sampled cloud) and ``keypoint_radii`` (salient, non-max, as
+   used) record what was kept
 5. Gaussian noise N(0, 0.05²) on ``pcd_down`` points from the GLOBAL numpy RNG, after the
    features (the reference's robustness test)                                        ply.py:61-62
 6. ``pcd`` normals: hybrid search (2·v, 30), oriented by normals read from the file  ply.py:65,133
@@ -41,7 +47,8 @@ from m3d.types import Feature, PointCloud
 
 class Ply:
     def __init__(self, path, voxel_size: float = 0.3, remove_outliers: dict | None = None,
-                 remove_plane: dict | None = None, keep_cluster: dict | None = None) -> None:
+                 remove_plane: dict | None = None, keep_cluster: dict | None = None,
+                 keypoints: dict | None = None) -> None:
         self.path = Path(path)
         self.voxel_size = voxel_size
         if not self.path.exists():
@@ -56,7 +63,7 @@ class Ply:
         if len(pts) == 0:
             raise ValueError(f"Point cloud is empty: {self.path}")          # ply.py:81-84
         self.pcd = PointCloud(pts, nrm)
-        self._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster)
+        self._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster, keypoints)
 
     def _remove_outliers(self, params: dict) -> None:
         """``pcd`` ← the points (and file normals) one of Open3D's two outlier filters keeps."""
@@ -101,13 +108,29 @@ class Ply:
         self.num_clusters = out.num_clusters
         self.pcd = self.pcd.select_by_index(np.flatnonzero(labels == out.largest_label))
 
+    _ISS_KEYS = {"salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors"}
+
+    def _keep_keypoints(self, params: dict, cloud) -> None:
+        """``pcd_down`` and ``pcd_fpfh`` ← their rows at the ISS keypoints of ``pcd_down``."""
+        from m3d import prep
+
+        idx, out = prep.compute_iss_keypoints(cloud, **params, with_details=True)
+        self.keypoint_indices = idx
+        self.keypoint_radii = (out.salient_radius, out.non_max_radius)
+        self.pcd_down = self.pcd_down.select_by_index(idx)
+        self.pcd_fpfh = Feature(np.ascontiguousarray(self.pcd_fpfh.data[:, idx]))
+
     def _preprocess(self, voxel_size: float, remove_outliers: dict | None = None,
-                    remove_plane: dict | None = None, keep_cluster: dict | None = None) -> None:
+                    remove_plane: dict | None = None, keep_cluster: dict | None = None,
+                    keypoints: dict | None = None) -> None:
         """ply.py:53-66.  Wall time of each stage lands in ``stage_ms`` (every stage returns host
         arrays, so the device work is complete when its timer stops)."""
         from m3d import prep
         from m3d.core import Cloud, to_device
 
+        if keypoints is not None and not set(keypoints) <= self._ISS_KEYS:
+            raise ValueError("keypoints: any of 'salient_radius', 'non_max_radius', 'gamma_21', 'gamma_32', "
+                             "'min_neighbors'")
         v = voxel_size
         ms = getattr(self, "stage_ms", None)
         if ms is None:
@@ -143,6 +166,9 @@ class Ply:
         self.pcd_down = PointCloud(down, down_n)
         self.pcd_fpfh = Feature(prep.compute_fpfh(c_down, down_n, 5 * v, 100).T)
         lap("fpfh")
+        if keypoints is not None:
+            self._keep_keypoints(keypoints, c_down)
+            lap("keypoints")
         noise = 0.05 * np.random.randn(*self.pcd_down.points.shape)      # ply.py:61-62
         self.pcd_down.points = self.pcd_down.points + noise
         lap("noise")
@@ -153,13 +179,14 @@ class Ply:
     @classmethod
     def from_arrays(cls, points, normals=None, points_down=None, fpfh=None, voxel_size: float = 0.3,
                     preprocess: bool = False, remove_outliers: dict | None = None,
-                    remove_plane: dict | None = None, keep_cluster: dict | None = None):
+                    remove_plane: dict | None = None, keep_cluster: dict | None = None,
+                    keypoints: dict | None = None):
         obj = cls.__new__(cls)
         obj.path = None
         obj.voxel_size = voxel_size
         obj.pcd = PointCloud(points, normals)
         if preprocess:
-            obj._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster)
+            obj._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster, keypoints)
             return obj
         obj.pcd_down = PointCloud(points if points_down is None else points_down)
         obj.pcd_fpfh = None if fpfh is None else Feature(np.asarray(fpfh, np.float64))

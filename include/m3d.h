@@ -625,6 +625,64 @@ int m3d_cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* cloud, double eps, int32_t
                        int32_t* labels_out, m3d_dbscan_result* out, int32_t* sizes_out,
                        int32_t* count_out, void* stream);
 
+/* ------------------------------------------------------------------ ISS keypoints (iss.hip)
+ * keypoint::ComputeISSKeypoints(input, salient_radius = 0, non_max_radius = 0, gamma_21 = 0.975,
+ * gamma_32 = 0.975, min_neighbors = 5) (Open3D 0.19) — the few hundred repeatable points of a scan
+ * whose FPFH rows go to the global registration.
+ *   d²(i, j) = (dx·dx + dy·dy) + dz·dz in fp64 on the cloud's original coordinates, no contraction
+ * Radii.  salient_radius == 0 or non_max_radius == 0 replaces BOTH: salient_radius = 6·res,
+ *   non_max_radius = 4·res, res = (Σ_i sqrt(d² to the nearest other point)) / n — Open3D's
+ *   ComputeModelResolution (SearchKNN(2), entry 1).  The per-point values are exact (the k-NN ladder
+ *   at k = 2); the sum is the fixed-order fp64 reduction of the outlier statistics (256-point
+ *   blocks, then one block; no floating-point atomics: repeated calls return the same bits).
+ *   n = 1: res = 0.  A resolved radius of 0: no keypoints, no scan.
+ * Saliency, for every i with S(i) = {j : d²(i, j) < salient_radius²} (strict, i itself included):
+ *   count[i] = |S(i)|; fewer than min_neighbors: third[i] = 0
+ *   the covariance of S(i), centred on the query: d = p_j − p_i in fp64, S1 = Σd, S2 = Σd dᵀ,
+ *     m = S1 / count, C = S2 / count − m mᵀ;  all |C_ab| <= 1e-12 (Eigen's isZero): third[i] = 0
+ *   λ0 <= λ1 <= λ2 the eigenvalues of C;  salient iff λ1 / λ2 < gamma_21 && λ0 / λ1 < gamma_32
+ *     (the divisions as written: a NaN compares false);  third[i] = λ0 if salient, else 0
+ * Non-maximum, for every i with third[i] > 0 and N(i) = {j : d²(i, j) < non_max_radius²}: i is a
+ *   keypoint iff |N(i)| >= min_neighbors and no j in N(i) has S(j) != S(i) and third[j] > third[i].
+ * Output: the keypoint indices, ascending (Open3D's order is that of its OpenMP critical section).
+ *
+ * Two deliberate differences from Open3D's arithmetic:
+ * 1. Centred moments.  Open3D's ComputeCovariance sums raw coordinates and subtracts; against an
+ *    80-bit reference its eigenvalues are off by 1.2e-11·λ2 on a unit shell near (10, −4, 2.5) and by
+ *    9.8e-8·λ2 on a cloud offset by 500.  The centred fp64 sums stay within 2.1e-15·λ2 whatever the
+ *    order of summation: the same quantity without the cancellation.
+ * 2. The same-set rule (S(j) != S(i) above).  Two nearby points very often have the identical
+ *    neighbour set; the covariance is translation invariant, so in exact arithmetic their third
+ *    values are equal, neither is < the other and both can be keypoints.  Open3D decides such pairs
+ *    by the rounding of two differently ordered sums of the same numbers (2.5–6 % of the points of
+ *    the test clouds sit within 1e-12·λ2 of such a tie).  The device never compares third across
+ *    equal sets.  It tells sets apart by a per-point integer signature (count, Σ_{j in S} mix64(j)
+ *    mod 2⁶⁴, mix64 = splitmix64's finaliser): order independent, integer adds only.  Equal
+ *    signatures are treated as equal sets; two different sets of equal size collide with
+ *    probability 2⁻⁶⁴ per compared pair. */
+typedef struct {
+  double salient_radius, non_max_radius; /* 0: from the model resolution (see above) */
+  double gamma_21, gamma_32;
+  int32_t min_neighbors;
+} m3d_iss_params;
+typedef struct {
+  int64_t num_keypoints;
+  int64_t num_salient;  /* points with third > 0: the candidates of the non-maximum pass */
+  int64_t num_counted;  /* points with count >= min_neighbors */
+  double salient_radius, non_max_radius; /* as used */
+  double resolution;    /* 0 when not computed */
+} m3d_iss_result;
+/* res_out [host].  n == 0: 0, no device work.  Synchronous. */
+int m3d_model_resolution(m3d_ctx* ctx, const m3d_cloud* cloud, double* res_out, void* stream);
+/* index_out [device] room for n int32 (entries [0, num_keypoints) are written); third_out [device] n
+ * doubles or NULL; count_out [device] n int32 or NULL (zeros when a resolved radius is 0).
+ * n == 0: zeros, no device work.  M3D_ERR_INVALID: a radius negative or not finite, a gamma not
+ * finite, min_neighbors < 0.  Synchronous; the grids of cell salient_radius and non_max_radius are
+ * cached on the cloud like the radius filter's. */
+int m3d_compute_iss_keypoints(m3d_ctx* ctx, const m3d_cloud* cloud, const m3d_iss_params* params,
+                              m3d_iss_result* out, int32_t* index_out, double* third_out,
+                              int32_t* count_out, void* stream);
+
 /* ------------------------------------------------------------------ feature matching (a5, a6) */
 
 /* CorrespondencesFromFeatures (src/matcher/ransac.py:85): exact fp64 1-NN in feature space
@@ -676,6 +734,8 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
 int m3d_debug_kabsch3_host(const double* src9, const double* tgt9, double* T16);
 int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6);  // the device solve's
                                                                        // rule: unpivoted, pivoted fallback
+/* linalg.h sym3_eigenvalues, compiled for the host: sym6 = (a00, a01, a02, a11, a12, a22) → lam3 ascending */
+int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3);
 /* XXH64 of [p, p + len) (the chunk hash of m3d_content_keys; known-answer tests). */
 uint64_t m3d_debug_xxh64(const void* p, size_t len, uint64_t seed);
 /* XXH3-128 (default secret, seed 0) of [p, p + len), len >= 241 (the long-input path the content
