@@ -1421,6 +1421,7 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
       cv.add(&s->ld64, n1);
       cv.add(&s->lidx, n1);
       cv.add(&s->corr, n1);
+      if (params->nn_method == M3D_NN_BRUTE) cv.add(&s->seed, n1);
       cv.add(&s->partials, (size_t)(terms_blocks(src->n) * kTermSlots + kTermSlots));  // + the sums
       if (cand_cap > 0) {  // the deferral list and its header (count, ticket, fault)
         cv.add(&s->hlist, n1);
@@ -2799,6 +2800,24 @@ int m3d_debug_icp_nn_plan_read(m3d_icp* s, uint32_t* counts, uint32_t* table, in
   if (table)
     HIPX(s->ctx, hipMemcpyAsync(table, s->nn_table, sizeof(uint32_t) * (size_t)s->nn_budget, hipMemcpyDeviceToHost, S(stream)));
   HIPX(s->ctx, hipMemcpyAsync(&shape3[2], &s->state->plan_ok, sizeof(int32_t), hipMemcpyDeviceToHost, S(stream)));
+  HIPX(s->ctx, hipStreamSynchronize(S(stream)));
+  return M3D_OK;
+}
+
+int m3d_debug_icp_seed_read(m3d_icp* s, float* seed, int32_t* corr, float* tgt32, int32_t* info2, void* stream) {
+  if (!s || !info2) return M3D_ERR_INVALID;
+  CHECK_ARG(s->ctx, s->seed != nullptr && s->tgt->rec64 != nullptr,
+            "this loop keeps no seed records (brute-force NN on a non-empty target only)");
+  info2[0] = s->keys_clean ? 1 : 0;
+  Touch tch{s->ctx, S(stream)};
+  HIPX(s->ctx, hipMemcpyAsync(&info2[1], &s->state->mfma_ok, sizeof(int32_t), hipMemcpyDeviceToHost, S(stream)));
+  const size_t ns = (size_t)s->src->n, nt = (size_t)s->tgt->n;
+  if (seed && ns > 0)
+    HIPX(s->ctx, hipMemcpyAsync(seed, s->seed, sizeof(float4) * ns, hipMemcpyDeviceToHost, S(stream)));
+  if (corr && ns > 0)
+    HIPX(s->ctx, hipMemcpyAsync(corr, s->corr, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, S(stream)));
+  if (tgt32)
+    HIPX(s->ctx, hipMemcpyAsync(tgt32, s->tgt->xyz32, sizeof(float4) * nt, hipMemcpyDeviceToHost, S(stream)));
   HIPX(s->ctx, hipStreamSynchronize(S(stream)));
   return M3D_OK;
 }

@@ -328,6 +328,7 @@ struct TermsArgs {
   int est;
   double c[3];
   int64_t* reset_keys;   // fused single-device loop: hand the keys back as kKeyNone
+  float4* seed;          // with reset_keys and rec64: the next scan's seed records (below), else null
 };
 
 // est: M3D_EST_POINT_TO_PLANE → slots 0..20 JTJ (upper, row-major), 21..26 JTr, 27 Σr²
@@ -453,8 +454,10 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
   }
   M3D_TPH(2);
   double tq[kP][3], tn[kP][3];
+  double pad[kP][2];  // the record's last 16 bytes: the target's centred fp32 point (pack_rec_kernel)
 #pragma unroll
   for (int u = 0; u < kP; ++u) {
+    pad[u][0] = pad[u][1] = 0.0;
     const bool own = valid[u] && gj[u] >= a.off && gj[u] < a.off + a.nt_shard;
     // branch-free: a source whose winner is not on this shard loads target 0 and drops it — but
     // an EMPTY target shard has no target 0 (no arrays at all): nothing is loaded there
@@ -470,6 +473,8 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
       tn[u][0] = r0.w;
       tn[u][1] = r1.x;
       tn[u][2] = r1.y;
+      pad[u][0] = r1.z;
+      pad[u][1] = r1.w;
     } else {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -492,6 +497,14 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
     }
     const int64_t i = ii[u];
     if (a.corr != nullptr) a.corr[i] = (int32_t)gj[u];
+    // Seed record of the next self-seeded scan (nnkey.h seed_key_rec): the final winner's fp32
+    // point — the record gathered above is gj's, resolved winners included — and its index, −1
+    // none (then the point is never read).  Only the fused tail that hands the keys back has the
+    // pointer: keys_clean ⇒ seed[i] describes corr[i].
+    if (kWT && a.seed != nullptr) {
+      a.seed[i] = make_float4(__int_as_float(__double2loint(pad[u][0])), __int_as_float(__double2hiint(pad[u][0])),
+                              __int_as_float(__double2loint(pad[u][1])), __int_as_float((int32_t)gj[u]));
+    }
     if (gj[u] < a.off || gj[u] >= a.off + a.nt_shard) continue;  // none, or another shard's target
     terms_add<kEst>(acc, vs[u], tq[u], tn[u], d2[u], a.c);
   }
@@ -1298,8 +1311,12 @@ hipError_t launch_icp_keyinit(const m3d_icp* s, int64_t off, hipStream_t st, int
 }
 
 
+// 64-B target record: fp64 point, fp64 normal, and in the last 16 bytes the centred fp32 point
+// (xyz32's bits: what the scan's seed gather read), which the fused tail copies into the seed
+// records; every other reader takes the first 48 bytes only
 __global__ __launch_bounds__(256) void pack_rec_kernel(const double* __restrict__ xyz,
-                                                       const double* __restrict__ nrm, int64_t n,
+                                                       const double* __restrict__ nrm,
+                                                       const float4* __restrict__ xyz32, int64_t n,
                                                        double* __restrict__ rec) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -1308,7 +1325,9 @@ __global__ __launch_bounds__(256) void pack_rec_kernel(const double* __restrict_
     r[k] = xyz[3 * i + k];
     r[3 + k] = nrm != nullptr ? nrm[3 * i + k] : 0.0;
   }
-  r[6] = r[7] = 0.0;
+  const float4 p = xyz32[i];
+  r[6] = __hiloint2double(__float_as_int(p.y), __float_as_int(p.x));
+  r[7] = __hiloint2double(__float_as_int(p.w), __float_as_int(p.z));
   for (int k = 0; k < 8; ++k) rec[8 * i + k] = r[k];
 }
 
@@ -1317,7 +1336,7 @@ hipError_t ensure_target_rec(const m3d_cloud* c, hipStream_t st) {
   double* rec = nullptr;
   hipError_t e = block_alloc(reinterpret_cast<void**>(&rec), sizeof(double) * 8 * c->n, st);
   if (e != hipSuccess) return e;
-  pack_rec_kernel<<<(unsigned)((c->n + 255) / 256), 256, 0, st>>>(c->xyz64, c->nrm64, c->n, rec);
+  pack_rec_kernel<<<(unsigned)((c->n + 255) / 256), 256, 0, st>>>(c->xyz64, c->nrm64, c->xyz32, c->n, rec);
   e = hipGetLastError();  // asynchronous (stream order); m3d_icp_create synchronises once
   if (e != hipSuccess) {
     block_release(rec);
@@ -1377,6 +1396,8 @@ static TermsArgs terms_args(const m3d_icp* s, int64_t off, const int32_t* claim,
   a.est = s->params.estimation;
   for (int k = 0; k < 3; ++k) a.c[k] = s->src->center[k];
   a.reset_keys = reset_keys ? s->keys : nullptr;
+  // (launch_icp_nn takes the records under the same condition)
+  a.seed = reset_keys && claim == nullptr && off == 0 && a.rec64 != nullptr ? s->seed : nullptr;
   return a;
 }
 

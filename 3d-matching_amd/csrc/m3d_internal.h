@@ -375,6 +375,9 @@ struct m3d_icp {
   int32_t nn_qblocks = 0;
   int32_t nn_budget = 0;
   int32_t* corr = nullptr;         // ns current correspondence (-1 none)
+  float4* seed = nullptr;          // ns seed records of the self-seeded brute-force scan: corr[i]'s centred
+                                   // fp32 point and index (w; -1 none), written by the fused tail that
+                                   // hands the keys back: keys_clean ⇒ seed[i] describes corr[i]
   double* pcd64 = nullptr;         // ns×3: the source as Open3D's RegistrationICP holds it — the
                                    // points after every update but the last (dT, IcpState)
   double* partials = nullptr;      // nblocks × kTermSlots

@@ -211,17 +211,29 @@ hipError_t build_mfma_tiles(const m3d_cloud* c, Grid* g, TmpArena* ta, hipStream
 // its queries' starting key itself (nnkey.h seed_key: the previous correspondence, exact — one
 // target load per query) and the blocks of grid.y == 0 also publish it; the MIN over the
 // blocks' atomics is the keyinit → scan result bit for bit.
+// With seed records (on == 2: the fused tail left, per query, its correspondence's fp32 point and
+// index, icp.hip terms_block) the key comes from the query's record, read beside src32[i] — the
+// same fp32 operations on the same bits (nnkey.h seed_key_rec) without the dependent, random
+// gather of tgt[prev[i]].  The records' pointer travels in `tgt`: a fifth member made the kernels
+// spill (docs/EXPERIMENTS.md §R22).
 struct SeedArgs {
   const int32_t* prev;  // corr of the previous evaluation
-  const float4* tgt;    // the target cloud's centred fp32 points, original order
+  const float4* tgt;    // the target cloud's centred fp32 points, original order; on == 2: the
+                        // seed records in slot order instead (prev and nt unused)
   int64_t nt;           // its size
-  int on;
+  int on;               // 0: keys[] holds the starting keys; 1: prev / tgt; 2: seed records
 };
 
-__device__ __forceinline__ int64_t start_key(const SeedArgs& sa, const IcpState* __restrict__ s,
-                                             int64_t i, float4 p, float qx, float qy, float qz,
-                                             int64_t off, const int64_t* __restrict__ keys) {
-  return sa.on ? seed_key(s, i, p, qx, qy, qz, sa.tgt, sa.nt, off, sa.prev, nullptr) : keys[i];
+// Query i's seed record where the tail left none (sa.on == 1): the same record formed from prev /
+// tgt (a previous correspondence outside the shard seeds nothing here: seed_key without dprev)
+__device__ __forceinline__ float4 seed_rec_prev(const SeedArgs& sa, int64_t i, int64_t off) {
+  const int64_t j = sa.prev[i];
+  float4 r = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+  if (j >= off && j < off + sa.nt) {
+    r = sa.tgt[j - off];
+    r.w = __int_as_float((int32_t)j);
+  }
+  return r;
 }
 
 // A block's place in the launch: slice y of the S slices of query block x (NnSlice, below)
@@ -259,7 +271,8 @@ __device__ void nn_slice_scan(const float4* __restrict__ src32, int64_t ns, cons
     float qx, qy, qz;
     const float4 p = src32[i];
     xform32(Rt, p, qx, qy, qz);
-    const int64_t key = start_key(sa, s, i, p, qx, qy, qz, off, keys);  // keyinit's starting key
+    const int64_t key = sa.on == 0 ? keys[i]  // keyinit's starting key
+                                   : seed_key_rec(s, sa.on == 2 ? sa.tgt[i] : seed_rec_prev(sa, i, off), qx, qy, qz);
     uint64_t k1 = key == kKeyNone ? make_key(r2_hi, 0xFFFFFFFFu) : (uint64_t)key;
     float k1d = key_real_d2(k1), n2 = kInf;
     const uint64_t k10 = k1;
@@ -370,6 +383,15 @@ __device__ __forceinline__ float wave_minmax(float v) {
 #endif
 // the deferred exact passes in batches through LDS (nn_mfma_kernel, after the sweep); 0 (A/B
 // builds): one sub-tile per global round trip, as before
+// the entry's state words and plan table entry in one scalar round trip (nn_mfma_body); 0 (A/B
+// builds): behind one another's branches, as before
+#ifndef M3D_NN_ENTRY
+#define M3D_NN_ENTRY 1
+#endif
+// the self-seeded scan reads the tail's seed records (launch_icp_nn); 0 (A/B builds): prev / tgt
+#ifndef M3D_NN_SEED_REC
+#define M3D_NN_SEED_REC 1
+#endif
 #ifndef M3D_NN_DEFER_BATCH
 #define M3D_NN_DEFER_BATCH 1
 #endif
@@ -437,10 +459,11 @@ __device__ __forceinline__ uint64_t group_mask(uint32_t bits) {
 // The query at position `slot` of the visit order ([q0, ns): order, or the slots themselves;
 // beyond ns: inactive): transform, starting key, B operand without its threshold; an active
 // query widens lq, the lane's share of its wave's query box (box_out_of_reach).  Returns the
-// search bound X, −1 for an inactive query.
-__device__ __forceinline__ float load_query(QState& q, QBox& lq, int64_t slot, int h,
-                                            const float4* __restrict__ src32, int64_t ns,
-                                            const IcpState* __restrict__ s, const SeedArgs& sa, int64_t off,
+// search bound X, −1 for an inactive query.  p = the query's source point and, self-seeding,
+// rec = its seed record: the caller loads them for all of the lane's queries before the first
+// use (an inactive query's are slot 0's, unused).
+__device__ __forceinline__ float load_query(QState& q, QBox& lq, int64_t slot, int h, float4 p, float4 rec,
+                                            int64_t ns, const IcpState* __restrict__ s, const SeedArgs& sa,
                                             const int64_t* __restrict__ keys) {
   const float* Rt = s->Rt32;
   const float r2_hi = s->r2_hi, S = s->mfma_scale;
@@ -449,9 +472,8 @@ __device__ __forceinline__ float load_query(QState& q, QBox& lq, int64_t slot, i
   q.n2 = kInf;
   float X = -1.0f;
   if (i >= 0) {
-    const float4 p = src32[i];
     xform32(Rt, p, q.qx, q.qy, q.qz);
-    const int64_t key = start_key(sa, s, i, p, q.qx, q.qy, q.qz, off, keys);
+    const int64_t key = sa.on ? seed_key_rec(s, rec, q.qx, q.qy, q.qz) : keys[i];
     q.k1 = key == kKeyNone ? make_key(r2_hi, 0xFFFFFFFFu) : (uint64_t)key;
     X = search_bound(key_d2(q.k1), s->band_e, r2_hi);
     lq.lo[0] = fminf(lq.lo[0], q.qx);
@@ -775,7 +797,20 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
                                              const IcpState* __restrict__ s, int64_t* __restrict__ keys,
                                              uint32_t* __restrict__ near2, const SeedArgs& sa, int64_t q0,
                                              const NnPlan& pl) {
+#if M3D_NN_ENTRY
+  // One scalar round trip at entry: the block's table entry (the launch has exactly the table's
+  // pl.budget blocks: blockIdx.x is in range whatever the state says) and the state words that
+  // decide the block's path are loaded together and selected afterwards, instead of each behind
+  // the previous one's branch.
+  uint32_t e_tab = kPlanEmpty;
+  if (kPlan && pl.table != nullptr) e_tab = pl.table[blockIdx.x];
+  int32_t st_done = s->done, st_plan = s->plan_ok, st_mfma = s->mfma_ok;
+  // (through an empty asm: or the compiler sinks each load back behind the branch that uses it)
+  asm volatile("" : "+s"(st_done), "+s"(st_plan), "+s"(st_mfma), "+s"(e_tab));
+  if (st_done) return;
+#else
   if (s->done) return;
+#endif
 #if M3D_NN_CLOCK
   const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -785,8 +820,13 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
   // launch has — y = b / nq, x = b % nq, S = pl.S; an empty entry, or y ≥ S, has nothing to do.
   NnSlice bs{0u, 0u, 0u};  // (2-D launch: unused — the hardware's values at every use, as before the plan)
   if (kPlan && pl.table != nullptr) {
+#if M3D_NN_ENTRY
+    if (st_plan) {
+      const uint32_t e = e_tab;
+#else
     if (s->plan_ok) {
       const uint32_t e = pl.table[blockIdx.x];
+#endif
       if (e == kPlanEmpty) return;
       bs = NnSlice{plan_x(e), plan_y(e), plan_S(e)};
     } else {
@@ -797,7 +837,11 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
   }
   // slice y takes every S-th target tile (strided: a query block's few candidate tiles, adjacent
   // in row order, spread over its S blocks instead of landing in one)
+#if M3D_NN_ENTRY
+  if (!st_mfma) {  // the same tiles by a plain scan, unculled
+#else
   if (!s->mfma_ok) {  // the same tiles by a plain scan, unculled
+#endif
     const int64_t tstep = (int64_t)(kPlan ? bs.S : gridDim.y) * kTT;
     for (int64_t t0 = (int64_t)(kPlan ? bs.y : blockIdx.y) * kTT; t0 < nt_pad; t0 += tstep)
       nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTT), off, s, keys, near2, sa, q0,
@@ -835,10 +879,33 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
   uint32_t force = 0;  // groups whose threshold exceeds the fp16 range: exact path everywhere
   uint32_t chg = 0;    // groups whose k1 left its starting key (k1 only ever decreases)
   QBox lq{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}, -1.0f};
+  const int64_t slot0 = q0 + (kPlan ? (int64_t)bs.x : (int64_t)blockIdx.x) * kMQueries + wave * kMG * 32 + c;
+  // source points and seed records of all the lane's queries in flight before the first use: one
+  // round trip, not one per group (an inactive query loads slot 0's, unused)
+  float4 qp[kMG], qr[kMG];
 #pragma unroll
   for (int g = 0; g < kMG; ++g) {
-    const int64_t slot = q0 + (kPlan ? (int64_t)bs.x : (int64_t)blockIdx.x) * kMQueries + (wave * kMG + g) * 32 + c;
-    const float X = load_query(q[g], lq, slot, h, src32, ns, s, sa, off, keys);
+    const int64_t slot = slot0 + g * 32;
+    qp[g] = src32[slot < ns ? slot : 0];
+    qr[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  if (sa.on == 2) {
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) {
+      const int64_t slot = slot0 + g * 32;
+      qr[g] = sa.tgt[slot < ns ? slot : 0];
+    }
+  } else if (sa.on) {
+#pragma unroll
+    for (int g = 0; g < kMG; ++g) {
+      const int64_t slot = slot0 + g * 32;
+      qr[g] = seed_rec_prev(sa, slot < ns ? slot : 0, off);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < kMG; ++g) {
+    const int64_t slot = slot0 + g * 32;
+    const float X = load_query(q[g], lq, slot, h, qp[g], qr[g], ns, s, sa, keys);
     if (q[g].qi >= 0) act |= 1u << g;
     if (__any(refresh_threshold(q[g], h, X, eps, S2))) force |= 1u << g;
   }
@@ -1205,7 +1272,9 @@ hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStrea
   const int64_t slots = nn_resident_slots();
   const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
   const int64_t gy = nn_grid_y(bx, tg->mf_npad / tt, slots, M3D_NN_CULL != 0);
-  const SeedArgs sa{s->corr, s->tgt->xyz32, s->tgt->n, self_seed ? 1 : 0};
+  // (the records exist where the fused tail wrote them: icp.hip terms_args, the same condition)
+  const bool by_rec = M3D_NN_SEED_REC != 0 && self_seed && off == 0 && s->tgt->rec64 != nullptr && s->seed != nullptr;
+  const SeedArgs sa{s->corr, by_rec ? s->seed : s->tgt->xyz32, s->tgt->n, by_rec ? 2 : self_seed ? 1 : 0};
   // The planned launch whenever the loop's plan can apply: the whole source, M3D_NN_PLAN on, and
   // (nn_plan_shape, at create) resident slots known and more of them than query blocks.
   const bool planned = nn_plan_on() && s->nn_qblocks > 0 && q0 == 0 && ns == s->src->n && bx == s->nn_qblocks &&

@@ -503,4 +503,16 @@ __device__ __forceinline__ int64_t seed_key(const IcpState* __restrict__ s, int6
   return seed_key_j(s, (int64_t)prev[i], i, p, qx, qy, qz, tgt32, nt_shard, off, dprev);
 }
 
+// seed_key from a seed record (icp.hip terms_block: the previous correspondence's centred fp32
+// point — the bits of tgt32[j] — and j's bits in w, −1 none) instead of prev[i] and the gather of
+// tgt32[prev[i]]: seed_key_j's in-shard branch on the same bits, so the same key.  Whole-target
+// loops only (off = 0: every j is in the shard).
+__device__ __forceinline__ int64_t seed_key_rec(const IcpState* __restrict__ s, float4 rec, float qx, float qy,
+                                                float qz) {
+  const int32_t j = __float_as_int(rec.w);
+  if (j < 0) return kKeyNone;
+  const float d2 = d2f(qx, qy, qz, rec.x, rec.y, rec.z);
+  return d2 <= s->r2_hi ? (int64_t)make_key(d2, (uint32_t)j) : kKeyNone;
+}
+
 }  // namespace m3d

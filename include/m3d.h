@@ -773,6 +773,15 @@ int m3d_debug_icp_nn_plan(m3d_icp* s, const int32_t* S, int64_t n, void* stream)
  * (0 none, 1 planned, 2 forced)}; counts [host, query blocks] the tile counts the planner last
  * read, table [host, budget] the entries; either may be NULL.  Within ABI 13. */
 int m3d_debug_icp_nn_plan_read(m3d_icp* s, uint32_t* counts, uint32_t* table, int32_t* shape3, void* stream);
+/* The seed records of a brute-force loop (synchronous): seed [host, ns x 4 f32] the
+ * records in the loop's slot order (x, y, z, index bits; index -1: none), corr [host, ns i32] the
+ * loop's correspondences in the same order, tgt32 [host, nt x 4 f32] the target's centred fp32
+ * points on the device, whose row corr[i] record i must equal bit for bit; any of the three may be
+ * NULL.  info2 [host] = {1 when the next m3d_icp_step will seed its scan from the records (the last
+ * fused tail wrote them), else 0; the loop state's mfma_ok (0: the scans of the current transform
+ * take the plain fallback)}.  M3D_ERR_INVALID for a loop without records (grid NN, empty target).
+ * Within ABI 13. */
+int m3d_debug_icp_seed_read(m3d_icp* s, float* seed, int32_t* corr, float* tgt32, int32_t* info2, void* stream);
 
 /* ------------------------------------------------------------------ host text I/O (§8(f) rank 4) */
 

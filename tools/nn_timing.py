@@ -2,7 +2,7 @@
 """Brute-force NN timing at cfg1 (100k x 100k): per-launch average of nn_mfma_kernel and of the
 fused terms tail over `iters` seeded evaluations (library HIP events), for A/B runs of library
 builds (AB_LIB, tools/ab_build.sh; build flags M3D_NN_CULL, M3D_NN_REACH, M3D_NN_DEFER_BATCH,
-M3D_NN_DEFER_FILTER, M3D_NN_TILE_MORTON).
+M3D_NN_DEFER_FILTER, M3D_NN_TILE_MORTON, M3D_NN_SEED_REC, M3D_NN_ENTRY).
 Usage: python tools/nn_timing.py [iters]"""
 import sys
 from pathlib import Path
