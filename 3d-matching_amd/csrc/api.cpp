@@ -2695,6 +2695,129 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- Fast Global Registration
+// fgr.hip; scratch is an allocation of the call's own (the evaluation at the end uses the arena)
+int32_t m3d_fgr_trial_batch(void) { return kFgrTrialBatch; }
+int32_t m3d_fgr_one_wg_rows(void) { return kFgrOneWgRows; }
+
+extern "C++" {
+namespace {
+int fgr_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, int64_t nc, const m3d_fgr_params* p) {
+  CHECK_ARG(ctx, src && tgt && p, "invalid arguments");
+  CHECK_ARG(ctx, nc >= 0 && nc < ((int64_t)1 << 31) / 300, "fgr: 0 <= rows < 2^31 / 300");
+  CHECK_ARG(ctx, p->tuple_scale > 0.0 && p->tuple_scale <= 1.0, "fgr: tuple_scale must be in (0, 1]");
+  CHECK_ARG(ctx, p->division_factor > 0.0, "fgr: division_factor must be > 0");
+  CHECK_ARG(ctx, p->iteration_number >= 0 && p->maximum_tuple_count >= 0,
+            "fgr: iteration_number and maximum_tuple_count must be >= 0");
+  CHECK_ARG(ctx, p->path >= 0 && p->path <= 2, "fgr: path is 0, 1 or 2");
+  return M3D_OK;
+}
+
+// steps 2-3 into a scratch block of the call's own
+int fgr_rows_call(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const int32_t* corr, int64_t nc,
+                  const m3d_fgr_params* p, m3d_fgr_result* out, int32_t* rows_out, DevTmp<char>* scratch,
+                  hipStream_t st) {
+  CHECK_ARG(ctx, nc == 0 || corr != nullptr, "null correspondence pointer");
+  int rc = dev_alloc(ctx, &scratch->p, (int64_t)fgr_scratch_bytes(src->n, tgt->n, nc, fgr_tuple_cap(p, nc)));
+  if (rc) return rc;
+  int bad = 0;
+  HIPX(ctx, fgr_rows(ctx, src->xyz64, src->n, tgt->xyz64, tgt->n, corr, nc, p, out, rows_out, scratch->p, st, &bad));
+  if (bad) return m3d_fail(ctx, M3D_ERR_INVALID, "fgr: a correspondence index is outside its cloud");
+  return M3D_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int m3d_fgr_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const int32_t* corr,
+                               int64_t nc, const m3d_fgr_params* p, m3d_fgr_result* out, int32_t* rows_out,
+                               int32_t* corr_set_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  int rc = fgr_check(ctx, src, tgt, nc, p);
+  if (rc) return rc;
+  CHECK_ARG(ctx, out != nullptr, "invalid arguments");
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 16; ++k) out->T[k] = out->T_norm[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  const int64_t ns = src->n, nt = tgt->n;
+  if (ns == 0 || nt == 0) {
+    Touch tch{ctx, st};
+    if (corr_set_out && ns > 0) HIPX(ctx, hipMemsetAsync(corr_set_out, 0xFF, 4 * ns, st));
+    HIPX(ctx, hipStreamSynchronize(st));
+    return M3D_OK;
+  }
+  {
+    Touch tch{ctx, st};
+    DevTmp<char> scratch;
+    rc = fgr_rows_call(ctx, src, tgt, corr, nc, p, out, rows_out, &scratch, st);
+    if (rc) return rc;
+    CHECK_ARG(ctx, p->path != 1 || out->n_rows <= kFgrOneWgRows, "fgr: path 1 holds at most m3d_fgr_one_wg_rows rows");
+    HIPX(ctx, fgr_optimise(ctx, ns, nt, nc, p, out, scratch.p, st));
+  }
+  // O = (R, ((−R·m1) + g·t) + m0), returned: O⁻¹ = (Rᵀ, −Rᵀ·o)
+  const double* Tn = out->T_norm;
+  const double g = out->scale_global;
+  double o[3];
+  for (int i = 0; i < 3; ++i) {
+    const double rm = (Tn[4 * i] * out->mean_tgt[0] + Tn[4 * i + 1] * out->mean_tgt[1]) + Tn[4 * i + 2] * out->mean_tgt[2];
+    o[i] = ((0.0 - rm) + g * Tn[4 * i + 3]) + out->mean_src[i];
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) out->T[4 * i + j] = Tn[4 * j + i];
+    out->T[4 * i + 3] = 0.0 - ((Tn[i] * o[0] + Tn[4 + i] * o[1]) + Tn[8 + i] * o[2]);
+  }
+  if (p->maximum_correspondence_distance > 0.0) {
+    m3d_eval_result ev;
+    rc = m3d_evaluate_registration(ctx, src, tgt, out->T, p->maximum_correspondence_distance, M3D_NN_GRID, 0, &ev,
+                                   corr_set_out, nullptr, stream);
+    if (rc) return rc;
+    out->fitness = ev.fitness;
+    out->inlier_rmse = ev.inlier_rmse;
+  } else if (corr_set_out) {
+    HIPX(ctx, hipMemsetAsync(corr_set_out, 0xFF, 4 * ns, st));
+    HIPX(ctx, hipStreamSynchronize(st));
+  }
+  return M3D_OK;
+}
+
+int m3d_fgr_tuple_test(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const int32_t* corr, int64_t nc,
+                       const m3d_fgr_params* p, int32_t* rows_out, int64_t* n_rows_out, int64_t* trials_out,
+                       void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  int rc = fgr_check(ctx, src, tgt, nc, p);
+  if (rc) return rc;
+  CHECK_ARG(ctx, n_rows_out && trials_out && (rows_out || nc == 0), "invalid arguments");
+  *n_rows_out = *trials_out = 0;
+  if (src->n == 0 || tgt->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  DevTmp<char> scratch;
+  m3d_fgr_result r;
+  memset(&r, 0, sizeof(r));
+  rc = fgr_rows_call(ctx, src, tgt, corr, nc, p, &r, rows_out, &scratch, st);
+  if (rc) return rc;
+  *n_rows_out = r.n_rows;
+  *trials_out = r.trials;
+  return M3D_OK;
+}
+
+int m3d_fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, double* sums27_out,
+                  void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, sums27_out && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (p && q)), "invalid arguments");
+  for (int k = 0; k < 27; ++k) sums27_out[k] = 0.0;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  DevTmp<char> scratch;
+  int rc = dev_alloc(ctx, &scratch.p, (int64_t)fgr_terms_scratch_bytes(n));
+  if (rc) return rc;
+  HIPX(ctx, fgr_terms(ctx, p, q, n, par, 0, sums27_out, scratch.p, st));
+  return M3D_OK;
+}
+
 // ------------------------------------------------------------------------------- test hooks
 int m3d_debug_kabsch3_host(const double* src9, const double* tgt9, double* T16) {
   if (!src9 || !tgt9 || !T16) return M3D_ERR_INVALID;

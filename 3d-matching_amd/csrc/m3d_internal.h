@@ -673,4 +673,25 @@ size_t segment_plane_scratch_bytes(int64_t n, int batch);
 hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batch, const int32_t* samples,
                          m3d_plane_result* out, int32_t* inliers_out, int32_t* counts_out, double* err_out,
                          void* scratch, hipStream_t st, int* bad_sample);
+// Fast Global Registration (fgr.hip).  Constants of the library: the sum order's segment (every
+// sum's bits depend on the element count alone), the rows the one-workgroup loop holds, the trials
+// of a tuple-test batch.
+constexpr int kFgrSegRows = 384;
+constexpr int kFgrOneWgRows = 3072;
+constexpr int kFgrTrialBatch = 16384;
+int64_t fgr_tuple_cap(const m3d_fgr_params* p, int64_t nc);  // tuples the test can keep (0: no test)
+size_t fgr_scratch_bytes(int64_t ns, int64_t nt, int64_t nc, int64_t cap);
+// normalise + tuple test (ns, nt ≥ 1): the row set stays in scratch, out gets n_input, n_rows,
+// tuples, trials, scale_global, par_final = par₀ and the means; rows_out [device] or null.
+// Synchronous.  *bad_row: a row index was outside its cloud (out untouched).
+hipError_t fgr_rows(m3d_ctx* ctx, const double* src, int64_t ns, const double* tgt, int64_t nt,
+                    const int32_t* corr, int64_t nc, const m3d_fgr_params* p, m3d_fgr_result* out,
+                    int32_t* rows_out, void* scratch, hipStream_t st, int* bad_row);
+// the loop over the row set fgr_rows left in the same scratch: out->T_norm, out->par_final.  Synchronous.
+hipError_t fgr_optimise(m3d_ctx* ctx, int64_t ns, int64_t nt, int64_t nc, const m3d_fgr_params* p,
+                        m3d_fgr_result* out, void* scratch, hipStream_t st);
+size_t fgr_terms_scratch_bytes(int64_t n);
+// one iteration's sums over n ≥ 1 given rows (path as m3d_fgr_params.path) → sums27 [host].  Synchronous.
+hipError_t fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, int path,
+                     double sums27[27], void* scratch, hipStream_t st);
 }  // namespace m3d

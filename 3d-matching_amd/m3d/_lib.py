@@ -33,6 +33,8 @@ OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
 NN_METHODS = {"brute": NN_BRUTE, "grid": NN_GRID}
 ABI_VERSION = 13
 PLANE_CHUNK = 512  # plane.hip kPlaneChunk (m3d_plane_chunk): points per chunk of the score kernel's partial sums
+FGR_TRIAL_BATCH = 16384  # fgr.hip kFgrTrialBatch (m3d_fgr_trial_batch): trials per batch of the tuple test
+FGR_ONE_WG_ROWS = 3072   # fgr.hip kFgrOneWgRows (m3d_fgr_one_wg_rows): rows the one-workgroup loop holds
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -95,6 +97,18 @@ class PlaneParams(C.Structure):
 class PlaneResult(C.Structure):
     _fields_ = [("plane", dbl * 4), ("ransac_plane", dbl * 4), ("num_inliers", i64), ("best_index", i64),
                 ("best_count", i64), ("evaluated", i64), ("iterations", i64), ("best_rmse", dbl)]
+
+
+class FgrParams(C.Structure):
+    _fields_ = [("division_factor", dbl), ("maximum_correspondence_distance", dbl), ("tuple_scale", dbl),
+                ("seed", u64), ("iteration_number", i32), ("maximum_tuple_count", i32),
+                ("use_absolute_scale", i32), ("decrease_mu", i32), ("tuple_test", i32), ("path", i32)]
+
+
+class FgrResult(C.Structure):
+    _fields_ = [("T", dbl * 16), ("fitness", dbl), ("inlier_rmse", dbl), ("n_input", i64), ("n_rows", i64),
+                ("tuples", i64), ("trials", i64), ("par_final", dbl), ("scale_global", dbl),
+                ("mean_src", dbl * 3), ("mean_tgt", dbl * 3), ("T_norm", dbl * 16)]
 
 
 class DbscanResult(C.Structure):
@@ -186,6 +200,13 @@ SIGNATURES = {
                                               C.POINTER(i64), vp]),
     "m3d_ransac_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FeatureRansacParams),
                                                 C.POINTER(FeatureRansacResult), vp, vp]),
+    "m3d_fgr_on_correspondences": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FgrParams), C.POINTER(FgrResult),
+                                             vp, vp, vp]),
+    "m3d_fgr_tuple_test": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(FgrParams), vp, C.POINTER(i64),
+                                     C.POINTER(i64), vp]),
+    "m3d_fgr_terms": (C.c_int, [vp, vp, vp, i64, dbl, C.POINTER(dbl), vp]),
+    "m3d_fgr_trial_batch": (i32, []),
+    "m3d_fgr_one_wg_rows": (i32, []),
     "m3d_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "m3d_comm_init": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(vp)]),
     "m3d_comm_destroy": (None, [vp]),

@@ -16,6 +16,7 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``pcd.segment_plane(thr, ransac_n, iterations)`` (users) | ``segment_plane``, ``plane_score`` |
 | ``pcd.cluster_dbscan(eps, min_points)`` (users)          | ``cluster_dbscan``                |
 | ``keypoint.compute_iss_keypoints(pcd, ...)`` (users)     | ``compute_iss_keypoints``, ``model_resolution`` |
+| ``registration_fgr_based_on_correspondence`` (users)     | ``fgr_on_correspondences``, ``fgr_tuple_test``, ``fgr_terms`` |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -448,3 +449,113 @@ def ransac_on_correspondences(src, tgt, corres, max_correspondence_distance: flo
     return FeatureRansacOutcome(np.array(r.T[:]).reshape(4, 4), r.fitness, r.inlier_rmse,
                                 int(r.best_index), int(r.validations), corr_pairs(ctx, cs, sc.n),
                                 float(r.corres_ratio))
+
+
+FGR_TRIAL_BATCH = _lib.FGR_TRIAL_BATCH  # trials per batch of the tuple test
+FGR_ONE_WG_ROWS = _lib.FGR_ONE_WG_ROWS  # rows the one-workgroup loop holds
+
+
+@dataclass
+class FgrOutcome:
+    transformation: np.ndarray   # source → target, original scale
+    fitness: float
+    inlier_rmse: float
+    correspondence_set: np.ndarray
+    rows: np.ndarray             # (n_rows, 2) the row set the loop optimised over
+    n_input: int
+    tuples: int                  # accepted trials kept by the tuple test (0 without it)
+    trials: int                  # trials the sequential tuple loop ran
+    par_final: float
+    scale_global: float
+    mean_src: np.ndarray
+    mean_tgt: np.ndarray
+    T_norm: np.ndarray           # the loop's T: normalised target → normalised source
+
+
+def _check_fgr_option(o):
+    if not (0.0 < float(o.tuple_scale) <= 1.0):
+        raise ValueError("fgr: tuple_scale must be in (0, 1]")
+    if not float(o.division_factor) > 0.0:
+        raise ValueError("fgr: division_factor must be > 0")
+    if int(o.iteration_number) < 0 or int(o.maximum_tuple_count) < 0:
+        raise ValueError("fgr: iteration_number and maximum_tuple_count must be >= 0")
+    if not np.isfinite(float(o.maximum_correspondence_distance)):
+        raise ValueError("fgr: maximum_correspondence_distance must be finite")
+
+
+def _fgr_params(option, path: int = 0):
+    from .types import FastGlobalRegistrationOption
+
+    o = option if option is not None else FastGlobalRegistrationOption()
+    _check_fgr_option(o)
+    if path not in (0, 1, 2):
+        raise ValueError("fgr: path is 0, 1 or 2")
+    seed = 0 if o.seed is None else int(o.seed)
+    return _lib.FgrParams(float(o.division_factor), float(o.maximum_correspondence_distance), float(o.tuple_scale),
+                          seed & ((1 << 64) - 1), int(o.iteration_number), int(o.maximum_tuple_count),
+                          int(bool(o.use_absolute_scale)), int(bool(o.decrease_mu)), int(bool(o.tuple_test)), int(path))
+
+
+def _fgr_rows(corres, ns: int, nt: int):
+    c = np.asarray(corres)
+    c = np.zeros((0, 2), np.int64) if c.size == 0 else c.reshape(-1, 2).astype(np.int64)
+    if len(c) and (c.min() < 0 or c[:, 0].max() >= ns or c[:, 1].max() >= nt):
+        raise ValueError("fgr: a correspondence index is outside its cloud")
+    return c.astype(np.int32)
+
+
+def _fgr_rows_room(p, nc: int) -> int:
+    cap = min(max(int(p.maximum_tuple_count), 1), max(100 * nc, 1))
+    return max(3 * cap if p.tuple_test else nc, 1)
+
+
+def fgr_on_correspondences(src_points, tgt_points, corres, option=None, with_details: bool = False, *, path: int = 0):
+    """Fast Global Registration over given (source, target) rows on the device
+    (m3d_fgr_on_correspondences; the contract is in include/m3d.h) → ``FgrOutcome``
+    (``with_details``: with the row set; otherwise ``rows`` is empty).  ``path`` forces the loop's
+    launch shape (1 one workgroup, 2 one launch per iteration) and changes no bit of the result."""
+    p = _fgr_params(option, path)
+    torch = _torch()
+    sc, tc = _cloud(src_points), _cloud(tgt_points)
+    ctx = sc.ctx
+    rows = _fgr_rows(corres, sc.n, tc.n)
+    nc = len(rows)
+    corr = to_device(rows, dtype="int32", shape_tail=(2,)) if nc else None
+    r = _lib.FgrResult()
+    rows_out = device_empty((_fgr_rows_room(p, nc), 2), torch.int32) if with_details else None
+    cs = device_empty((max(sc.n, 1),), torch.int32)
+    ctx.check(ctx.lib.m3d_fgr_on_correspondences(ctx.h, sc.h, tc.h, ptr(corr), nc, C.byref(p), C.byref(r),
+                                                 ptr(rows_out), ptr(cs), stream_handle()), "fgr_on_correspondences")
+    have = sc.n > 0 and tc.n > 0
+    kept = rows_out[: int(r.n_rows)].cpu().numpy() if with_details and have else np.zeros((0, 2), np.int32)
+    return FgrOutcome(np.array(r.T[:]).reshape(4, 4), r.fitness, r.inlier_rmse, corr_pairs(ctx, cs, sc.n), kept,
+                      int(r.n_input), int(r.tuples), int(r.trials), float(r.par_final), float(r.scale_global),
+                      np.array(r.mean_src[:]), np.array(r.mean_tgt[:]), np.array(r.T_norm[:]).reshape(4, 4))
+
+
+def fgr_tuple_test(src_points, tgt_points, corres, option=None):
+    """Normalisation and tuple test alone (m3d_fgr_tuple_test) → (rows (n_rows, 2) int32, trials)."""
+    p = _fgr_params(option)
+    torch = _torch()
+    sc, tc = _cloud(src_points), _cloud(tgt_points)
+    ctx = sc.ctx
+    rows = _fgr_rows(corres, sc.n, tc.n)
+    nc = len(rows)
+    corr = to_device(rows, dtype="int32", shape_tail=(2,)) if nc else None
+    out = device_empty((_fgr_rows_room(p, nc), 2), torch.int32)
+    n_rows, trials = C.c_int64(), C.c_int64()
+    ctx.check(ctx.lib.m3d_fgr_tuple_test(ctx.h, sc.h, tc.h, ptr(corr), nc, C.byref(p), ptr(out), C.byref(n_rows),
+                                         C.byref(trials), stream_handle()), "fgr_tuple_test")
+    return out[: n_rows.value].cpu().numpy(), int(trials.value)
+
+
+def fgr_terms(p_rows, q_rows, par: float) -> np.ndarray:
+    """One iteration's sums over given rows (m3d_fgr_terms): the 21 upper-triangle entries of JᵀJ
+    and the 6 of Jᵀr, (27,) float64."""
+    ctx = context()
+    p, q = to_device(p_rows), to_device(q_rows)
+    if p.shape != q.shape:
+        raise ValueError("fgr_terms: p and q must have the same shape")
+    out = (C.c_double * 27)()
+    ctx.check(ctx.lib.m3d_fgr_terms(ctx.h, ptr(p), ptr(q), p.shape[0], float(par), out, stream_handle()), "fgr_terms")
+    return np.array(out[:], np.float64)

@@ -3,6 +3,8 @@
 * ``RegistrationResult`` — Open3D ``pipelines.registration.RegistrationResult`` as the reference
   uses it (`ransac.py:134-136`, `icp.py:42`): ``transformation`` (4×4 f64), ``fitness``,
   ``inlier_rmse``, ``correspondence_set`` (M×2 int32).
+* ``FastGlobalRegistrationOption`` — Open3D ``pipelines.registration.FastGlobalRegistrationOption``:
+  the same names and defaults.
 * ``PointCloud`` — the two attributes the path reads from ``o3d.geometry.PointCloud``:
   ``points`` (N×3 f64) and ``normals`` (N×3 f64 or empty), and ``covariances`` (N×3×3 f64 or
   empty) for Generalized ICP.
@@ -24,6 +26,27 @@ class RegistrationResult:
     def __repr__(self):
         return (f"RegistrationResult with fitness={self.fitness:e}, inlier_rmse={self.inlier_rmse:e}, "
                 f"and correspondence_set size of {len(self.correspondence_set)}")
+
+
+class FastGlobalRegistrationOption:
+    """Open3D ``FastGlobalRegistrationOption`` (0.19): names and defaults as upstream.  ``seed``
+    keys the counter sampler of the tuple test (``None``: 0)."""
+
+    def __init__(self, division_factor: float = 1.4, use_absolute_scale: bool = False, decrease_mu: bool = False,
+                 maximum_correspondence_distance: float = 0.025, iteration_number: int = 64,
+                 tuple_scale: float = 0.95, maximum_tuple_count: int = 1000, tuple_test: bool = True, seed=None):
+        self.division_factor = float(division_factor)
+        self.use_absolute_scale = bool(use_absolute_scale)
+        self.decrease_mu = bool(decrease_mu)
+        self.maximum_correspondence_distance = float(maximum_correspondence_distance)
+        self.iteration_number = int(iteration_number)
+        self.tuple_scale = float(tuple_scale)
+        self.maximum_tuple_count = int(maximum_tuple_count)
+        self.tuple_test = bool(tuple_test)
+        self.seed = seed
+
+    def __repr__(self):
+        return ("FastGlobalRegistrationOption(" + ", ".join(f"{k}={v!r}" for k, v in vars(self).items()) + ")")
 
 
 class Feature:

@@ -14,6 +14,11 @@ from .evaluate import (
     evaluate_registration,
     get_information_matrix_from_point_clouds,
 )
+from .fgr import (
+    global_registration_fgr,
+    registration_fgr_based_on_correspondence,
+    registration_fgr_based_on_feature_matching,
+)
 from .gicp import registration_generalized_icp
 from .icp import refine_registration, registration_icp
 from .ransac import (
@@ -35,6 +40,9 @@ __all__ = [
     "evaluate_registration",
     "get_information_matrix_from_point_clouds",
     "global_registration",
+    "global_registration_fgr",
+    "registration_fgr_based_on_correspondence",
+    "registration_fgr_based_on_feature_matching",
     "run_ransac",
     "refine_registration",
     "registration_generalized_icp",

@@ -6,24 +6,44 @@ written).  This façade supplies it (``Ply.voxel_size``, default 
 the same two stages on the device:
 
 1. coarse: ``global_registration`` when both inputs carry FPFH features (``pcd_fpfh``), else the
-   step-RANSAC loop (``run_ransac``) over the given ``correspondences``;
+   step-RANSAC loop (``run_ransac``) over the given ``correspondences``; ``coarse="fgr"`` runs Fast
+   Global Registration instead (``matcher.fgr``: no sample budget, no dependence on a seed's luck);
 2. fine: ``refine_registration`` (point-to-plane ICP, radius 0.4·voxel) from the coarse result.
 """
 
 from __future__ import annotations
 
+from .fgr import global_registration_fgr, registration_fgr_based_on_correspondence
 from .icp import refine_registration
 from .ransac import global_registration, run_ransac
 
 
 def register(source, target, voxel_size=None, correspondences=None, ransac_iterations: int = 10000,
-             refine: bool = True, iteration: int = 30, **ransac_kwargs):
+             refine: bool = True, iteration: int = 30, coarse: str = "ransac", fgr_option=None, **ransac_kwargs):
     """Return the refined ``RegistrationResult`` mapping ``source`` onto ``target``.
 
     ``iteration``: RANSACConvergenceCriteria max_iteration of the feature path
     (global_registration's own default, 30); ``ransac_iterations``: hypotheses of the
-    correspondence path."""
+    correspondence path.  ``coarse``: "ransac" (the default) or "fgr" (``fgr_option``: a
+    ``FastGlobalRegistrationOption``; default maximum_correspondence_distance = 0.5·voxel)."""
     v = voxel_size if voxel_size is not None else getattr(source, "voxel_size", 0.3)
+    if coarse not in ("ransac", "fgr"):
+        raise ValueError("coarse must be 'ransac' or 'fgr'")
+    if coarse == "fgr":
+        if ransac_kwargs:
+            raise TypeError(f"unexpected arguments with coarse='fgr': {sorted(ransac_kwargs)}")
+        if correspondences is None and getattr(source, "pcd_fpfh", None) is not None \
+                and getattr(target, "pcd_fpfh", None) is not None:
+            first = global_registration_fgr(source, target, v, fgr_option)
+        elif correspondences is not None:
+            if fgr_option is None:
+                from m3d.types import FastGlobalRegistrationOption
+
+                fgr_option = FastGlobalRegistrationOption(maximum_correspondence_distance=0.5 * float(v))
+            first = registration_fgr_based_on_correspondence(source, target, correspondences, fgr_option)
+        else:
+            raise ValueError("register needs FPFH features on both inputs (pcd_fpfh) or correspondences")
+        return first if not refine else refine_registration(source, target, first.transformation, v)
     if correspondences is None and getattr(source, "pcd_fpfh", None) is not None \
             and getattr(target, "pcd_fpfh", None) is not None:
         coarse = global_registration(source, target, v, iteration=iteration)

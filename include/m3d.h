@@ -728,6 +728,77 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
                                   m3d_feature_ransac_result* out, int32_t* corr_set_out,
                                   void* stream);
 
+/* ------------------------------------------------------------------ Fast Global Registration (fgr.hip)
+ * Open3D 0.19 FastGlobalRegistration.cpp (Zhou, Park, Koltun) restated; tests/fgr_restatement.py is
+ * the same text in numpy.  fp64 throughout, every operation rounded on its own in the order written.
+ *   normalise   m0 = mean(S), m1 = mean(G); scale = max over both centred clouds of √((x² + y²) + z²);
+ *               use_absolute_scale ? (g = 1, par₀ = scale) : (g = scale, par₀ = 1);
+ *               P = (S − m0) / g, Q = (G − m1) / g
+ *   tuple test  (tuple_test) with n rows, trials h = 0 … 100·n − 1 in order, each drawing three rows
+ *               with replacement from the counter sampler of m3d_ransac_on_correspondences
+ *               (base = splitmix64(seed ^ h·0x9E3779B97F4A7C15), row_k = ((splitmix64(base + k) >> 32)·n) >> 32);
+ *               edges li = |P[i0] − P[i1]|, |P[i1] − P[i2]|, |P[i2] − P[i0]| (√((dx² + dy²) + dz²)), lj the
+ *               same over Q; accepted iff li_k·tuple_scale < lj_k && lj_k < li_k / tuple_scale for all k;
+ *               an accepted trial appends its three rows; the loop stops after the trial that brings
+ *               the accepted count to >= maximum_tuple_count (0: after the first accepted trial).  The
+ *               appended rows replace the row set, duplicates stay.
+ *   optimise    fewer than 10 rows: T = I.  Else par = par₀, p_c = P[i_c], q_c = Q[j_c] (a copy that
+ *               moves), and iteration_number times: r = p − q, s = (par / (((r_x² + r_y²) + r_z²) + par))²,
+ *               JᵀJ = Σ s·J Jᵀ, Jᵀr = Σ s·J r over the rows Jx = (0, −q_z, q_y, −1, 0, 0),
+ *               Jy = (q_z, 0, −q_x, 0, −1, 0), Jz = (−q_y, q_x, 0, 0, 0, −1); JᵀJ x = −Jᵀr by the ICP
+ *               solve (unpivoted LDLᵀ while safe, else Eigen's pivot order; a non-finite δ is I),
+ *               δ = TransformVector6dToMatrix4d(x), T ← δ·T, q_c ← δ·q_c; then, if decrease_mu and
+ *               itr % 4 == 0 and par > maximum_correspondence_distance: par /= division_factor.
+ *   result      T = (R, t) maps the normalised target onto the normalised source;
+ *               O = (R, ((−R·m1) + g·t) + m0); the transformation returned is O⁻¹ = (Rᵀ, −Rᵀ·o);
+ *               fitness, inlier_rmse and the correspondence set are m3d_evaluate_registration's at
+ *               maximum_correspondence_distance under O⁻¹ (radius <= 0: zeros, no pairs).
+ * Every sum (the means, the loop's sums) is taken in one order that depends on the element count
+ * alone: repeated calls, and both loop paths, return the same bits. */
+typedef struct {
+  double division_factor;                 /* 1.4 */
+  double maximum_correspondence_distance; /* 0.025 */
+  double tuple_scale;                     /* 0.95 */
+  uint64_t seed;                          /* counter sampler seed (Open3D's seed=None: 0) */
+  int32_t iteration_number;               /* 64 */
+  int32_t maximum_tuple_count;            /* 1000 */
+  int32_t use_absolute_scale;             /* 0 */
+  int32_t decrease_mu;                    /* 0 */
+  int32_t tuple_test;                     /* 1 */
+  int32_t path;                           /* loop: 0 automatic, 1 one workgroup, 2 one launch per iteration */
+} m3d_fgr_params;
+typedef struct {
+  double T[16];                /* source → target, original scale */
+  double fitness, inlier_rmse;
+  int64_t n_input, n_rows;     /* rows given; rows optimised over */
+  int64_t tuples, trials;      /* accepted trials kept; trials the sequential loop ran */
+  double par_final, scale_global;
+  double mean_src[3], mean_tgt[3];
+  double T_norm[16];           /* the loop's T (normalised target → normalised source) */
+} m3d_fgr_result;
+/* Steps normalise … result.  corr [device] nc×2 int32 (source, target) rows; rows_out [device] room
+ * for 3·max(maximum_tuple_count, 1)×2 int32 (tuple test; never more than 300·nc×2) or nc×2, or NULL:
+ * the row set optimised over; corr_set_out [device] ns int32 or NULL (−1 none).  An empty cloud gives
+ * T = I and zeros.  M3D_ERR_INVALID: a row index outside its cloud (found on the device before a
+ * point is read through it), path 1 with more rows than the one-workgroup loop holds, a
+ * tuple_scale outside (0, 1], division_factor <= 0, negative counts.  Synchronous. */
+int m3d_fgr_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const int32_t* corr,
+                               int64_t nc, const m3d_fgr_params* params, m3d_fgr_result* out,
+                               int32_t* rows_out, int32_t* corr_set_out, void* stream);
+/* Steps normalise and tuple test alone: rows_out as above (required), *n_rows_out and *trials_out
+ * [host].  Synchronous. */
+int m3d_fgr_tuple_test(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const int32_t* corr,
+                       int64_t nc, const m3d_fgr_params* params, int32_t* rows_out, int64_t* n_rows_out,
+                       int64_t* trials_out, void* stream);
+/* One iteration's sums over n given rows: p, q [device] n×3 f64 → sums27_out [host]: the 21 entries
+ * of JᵀJ's upper triangle (row-major) and the 6 of Jᵀr.  n == 0: zeros.  Synchronous. */
+int m3d_fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, double* sums27_out,
+                  void* stream);
+/* constants of the library: trials per batch of the tuple test; the most rows the one-workgroup
+ * loop holds (the sum order's segment is a fixed fraction of it) */
+int32_t m3d_fgr_trial_batch(void);
+int32_t m3d_fgr_one_wg_rows(void);
+
 /* ------------------------------------------------------------------ test hooks
  * Host-compiled copy of the device 3×3 linear algebra (same source), for CPU-side unit tests
  * of the math.  Never used by the product path. */
