@@ -2062,16 +2062,27 @@ int gicp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double
 }
 }  // namespace
 
-int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
-                   const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
-                   double epsilon, double* sums_out, int32_t* corr_idx, void* stream) {
-  if (!ctx) return M3D_ERR_INVALID;
-  Touch tch{ctx, S(stream)};
+extern "C++" {
+namespace {
+// a caller's robust kernel: a known kind, and a finite k > 0 for the kinds that read it
+int robust_check(m3d_ctx* ctx, const m3d_robust_kernel* kernel) {
+  CHECK_ARG(ctx, kernel != nullptr, "null robust kernel");
+  CHECK_ARG(ctx, kernel->kind >= M3D_KERNEL_L2 && kernel->kind <= M3D_KERNEL_TUKEY, "unknown robust kernel");
+  CHECK_ARG(ctx, kernel->kind == M3D_KERNEL_L2 || kernel->kind == M3D_KERNEL_L1 ||
+                     (std::isfinite(kernel->k) && kernel->k > 0.0),
+            "robust kernel: k must be finite and > 0");
+  return M3D_OK;
+}
+
+// One Generalized-ICP evaluation; kernel null: the plane-to-plane terms of gicp.hip, else
+// robust.hip's with that (checked) kernel
+int gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+               const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method, double epsilon,
+               const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx, hipStream_t st) {
   CHECK_ARG(ctx, sums_out != nullptr, "null output");
   int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, nn_method, epsilon);
   if (rc) return rc;
   for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
-  hipStream_t st = S(stream);
   const int64_t ns = src->n, nt = tgt->n;
   if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
     hipSetDevice(ctx->device);
@@ -2090,18 +2101,44 @@ int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, con
   // pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and covariances
   rc = one_evaluation(s, T_host, true, [&](double* pin) {
     KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-    return launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin, true, st);
+    return kernel == nullptr
+               ? launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin, true, st)
+               : launch_robust_gicp_terms(s, kernel->kind, kernel->k, ga.cov_s, ga.cov_t, ga.partials, pin, true, st);
   }, corr_idx, kTermSlots, sums, st);
   if (rc) return rc;
   for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
   return M3D_OK;
 }
 
-int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
-                 const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
-                 m3d_icp_result* out, int32_t* corr_idx, void* stream) {
-  if (!ctx) return M3D_ERR_INVALID;
-  Touch tch{ctx, S(stream)};
+// The evaluations of a one-shot loop whose terms pass is not the fused tail's: max_iteration + 1
+// times NN scan, terms(sums) (the pass and its reduce) and the point-to-plane solve, enqueued in
+// growing chunks with a look at `done` in between, as m3d_icp_run; evaluations after convergence
+// are device no-ops.  Then the result.  The loop has been reset.
+template <class Terms>
+int run_terms_loop(m3d_icp* s, int32_t max_iteration, Terms terms, m3d_icp_result* out, int32_t* corr_idx,
+                   hipStream_t st) {
+  m3d_ctx* ctx = s->ctx;
+  const bool search = s->src->n > 0 && s->tgt->n > 0;  // else: no scan, zero sums, every source unmatched
+  auto step = [&](int32_t k) {
+    hipError_t e = hipSuccess;
+    for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
+      if (search) e = enqueue_nn(s, 0, st);
+      if (e == hipSuccess) {
+        KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+        e = terms(s->sums);
+      }
+      if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
+    }
+    return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("terms loop step: ") + hipGetErrorString(e));
+  };
+  int rc = run_chunked(s, max_iteration + 1, step, st);
+  if (!rc) rc = finish_run(s, out, corr_idx, st);
+  return rc;
+}
+
+int gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+             const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
+             const m3d_robust_kernel* kernel, m3d_icp_result* out, int32_t* corr_idx, void* stream) {
   CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
   int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, params->nn_method, params->epsilon);
   if (rc) return rc;
@@ -2110,28 +2147,147 @@ int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const
                    params->max_iteration, params->nn_method, &s.s);
   if (rc) return rc;
   hipStream_t st = S(stream);
-  const bool search = src->n > 0 && tgt->n > 0;  // else: no scan, zero sums, every source unmatched
   GicpArrays ga;
   rc = gicp_setup(s, src_cov, tgt_cov, params->epsilon, st, &ga);
   if (!rc) rc = m3d_icp_reset(s, init, stream);
-  // max_iteration + 1 evaluations (NN scan, plane-to-plane terms + reduce, point-to-plane solve),
-  // enqueued in growing chunks with a look at `done` in between, as m3d_icp_run; evaluations
-  // after convergence are device no-ops
-  auto step = [&](int32_t k) {
-    hipError_t e = hipSuccess;
-    for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
-      if (search) e = enqueue_nn(s, 0, st);
-      if (e == hipSuccess) {
-        KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-        e = launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, s->sums, false, st);
-      }
-      if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
-    }
-    return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("gicp step: ") + hipGetErrorString(e));
-  };
-  if (!rc) rc = run_chunked(s, params->max_iteration + 1, step, st);
-  if (!rc) rc = finish_run(s, out, corr_idx, st);
+  if (!rc)
+    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
+      return kernel == nullptr
+                 ? launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, sums, false, st)
+                 : launch_robust_gicp_terms(s, kernel->kind, kernel->k, ga.cov_s, ga.cov_t, ga.partials, sums, false, st);
+    }, out, corr_idx, st);
   if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
+  return rc;
+}
+
+// the block partials of a robust point-to-plane pass (GicpArrays without covariances)
+int robust_plane_setup(m3d_icp* s, hipStream_t st, GicpArrays* ga) {
+  ga->ctx = s->ctx;
+  ga->st = st;
+  Carve cc;
+  cc.add(&ga->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(robust_blocks(s->src->n), 1));
+  size_t bytes = 0;
+  if (cc.alloc(&ga->block, &bytes, st) != hipSuccess)
+    return m3d_fail(s->ctx, M3D_ERR_OOM, "device allocation failed (robust point-to-plane partials)");
+  return M3D_OK;
+}
+
+// a kernel that changes nothing (null or L2): the call is the one without a kernel
+const m3d_robust_kernel* non_l2(const m3d_robust_kernel* kernel) {
+  return kernel != nullptr && kernel->kind != M3D_KERNEL_L2 ? kernel : nullptr;
+}
+}  // namespace
+}  // extern "C++"
+
+int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                   const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
+                   double epsilon, double* sums_out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  return gicp_terms(ctx, src, tgt, src_cov, tgt_cov, T_host, max_dist, nn_method, epsilon, nullptr, sums_out,
+                    corr_idx, S(stream));
+}
+
+int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                 const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
+                 m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  return gicp_run(ctx, src, tgt, src_cov, tgt_cov, init, max_dist, params, nullptr, out, corr_idx, stream);
+}
+
+// ------------------------------------------------------------------------------- robust kernels
+// robust.hip.  Generalized ICP with a kernel is the calls above with another terms pass;
+// point-to-plane with a kernel is the same loop shape around the point-to-plane loop object.
+int m3d_gicp_terms_robust(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                          const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
+                          double epsilon, const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx,
+                          void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  if (kernel != nullptr) {
+    const int rc = robust_check(ctx, kernel);
+    if (rc) return rc;
+  }
+  return gicp_terms(ctx, src, tgt, src_cov, tgt_cov, T_host, max_dist, nn_method, epsilon, non_l2(kernel), sums_out,
+                    corr_idx, S(stream));
+}
+
+int m3d_gicp_run_robust(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                        const double* tgt_cov, const double* init, double max_dist,
+                        const m3d_gicp_params* params, const m3d_robust_kernel* kernel, m3d_icp_result* out,
+                        int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  if (kernel != nullptr) {
+    const int rc = robust_check(ctx, kernel);
+    if (rc) return rc;
+  }
+  return gicp_run(ctx, src, tgt, src_cov, tgt_cov, init, max_dist, params, non_l2(kernel), out, corr_idx, stream);
+}
+
+int m3d_robust_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* T_host,
+                     double max_dist, int32_t nn_method, const m3d_robust_kernel* kernel, double* sums_out,
+                     int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  CHECK_ARG(ctx, src && tgt && sums_out, "invalid arguments");
+  int rc = robust_check(ctx, kernel);
+  if (rc) return rc;
+  CHECK_ARG(ctx, max_dist > 0.0, "Invalid max_correspondence_distance.");
+  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
+  CHECK_ARG(ctx, tgt->nrm64 != nullptr || tgt->n == 0,
+            "TransformationEstimationPointToPlane requires pre-computed normal vectors for target "
+            "PointCloud.");
+  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
+  hipStream_t st = S(stream);
+  const int64_t ns = src->n, nt = tgt->n;
+  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
+    hipSetDevice(ctx->device);
+    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    return M3D_OK;
+  }
+  m3d_icp_params p{1e-6, 1e-6, 0, M3D_EST_POINT_TO_PLANE, nn_method, 0};
+  ScopedLoop s;
+  rc = icp_create(ctx, src, tgt, max_dist, &p, &s.s, true);
+  if (rc) return rc;
+  GicpArrays ga;
+  rc = robust_plane_setup(s, st, &ga);
+  if (rc) return rc;
+  double sums[kTermSlots] = {};
+  rc = one_evaluation(s, T_host, true, [&](double* pin) {
+    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+    return launch_robust_plane_terms(s, kernel->kind, kernel->k, ga.partials, pin, true, st);
+  }, corr_idx, kTermSlots, sums, st);
+  if (rc) return rc;
+  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
+  return M3D_OK;
+}
+
+int m3d_robust_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* init,
+                       double max_dist, const m3d_icp_params* params, const m3d_robust_kernel* kernel,
+                       m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  Touch tch{ctx, S(stream)};
+  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
+  int rc = robust_check(ctx, kernel);
+  if (rc) return rc;
+  CHECK_ARG(ctx, params->estimation == M3D_EST_POINT_TO_PLANE,
+            "a robust kernel needs the point-to-plane estimation (TransformationEstimationPointToPoint takes none)");
+  ScopedLoop s;
+  rc = icp_create(ctx, src, tgt, max_dist, params, &s.s, true);
+  if (rc) return rc;
+  hipStream_t st = S(stream);
+  GicpArrays ga;
+  rc = robust_plane_setup(s, st, &ga);
+  if (!rc) rc = m3d_icp_reset(s, init, stream);
+  if (!rc)
+    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
+      return launch_robust_plane_terms(s, kernel->kind, kernel->k, ga.partials, sums, false, st);
+    }, out, corr_idx, st);
+  if (rc) (void)hipStreamSynchronize(st);  // the partials go back to the block cache idle
   return rc;
 }
 
@@ -2839,6 +2995,12 @@ int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6) {
 int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3) {
   if (!sym6 || !lam3) return M3D_ERR_INVALID;
   sym3_eigenvalues(sym6[0], sym6[1], sym6[2], sym6[3], sym6[4], sym6[5], lam3);
+  return M3D_OK;
+}
+
+int m3d_debug_sym3_eigen_host(const double* sym6, double* lam3, double* V9) {
+  if (!sym6 || !lam3 || !V9) return M3D_ERR_INVALID;
+  sym3_eigen(sym6[0], sym6[1], sym6[2], sym6[3], sym6[4], sym6[5], lam3, V9);
   return M3D_OK;
 }
 

@@ -13,6 +13,7 @@
 //      for full-rank JTJ (the device solve's fast path, falling back to ldlt6_solve).
 //  * sym3_eigenvalues: the three eigenvalues of a symmetric 3×3 by cyclic Jacobi (the covariance
 //      of an ISS neighbourhood, iss.hip): a few ulps of the norm, exact zeros for a zero block.
+//      sym3_eigen: the same with the eigenvectors; sym3_inv_sqrt: M^(−1/2) from them (robust.hip).
 //  * vec6_to_matrix: Open3D TransformVector6dToMatrix4d, R = Rz(x2)·Ry(x1)·Rx(x0).
 #pragma once
 
@@ -183,13 +184,15 @@ M3D_HD void swapd(double& a, double& b) {
 
 // One Jacobi rotation of a symmetric 3×3 held in six scalars: zeroes a_pq; (arp, arq) are the two
 // other off-diagonal entries a_rp, a_rq.  An a_pq that no longer changes either diagonal entry is
-// dropped (Rutishauser's test); an exact zero costs nothing and touches nothing.
-M3D_HD void jacobi3_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
-  if (apq == 0.0) return;
+// dropped (Rutishauser's test); an exact zero costs nothing and touches nothing.  Returns whether
+// a rotation was applied, and then its cosine and sine: column p ← c·p − s·q, column q ← s·p + c·q.
+M3D_HD bool jacobi3_rotation(double& app, double& aqq, double& apq, double& arp, double& arq, double& c,
+                             double& s) {
+  if (apq == 0.0) return false;
   const double g = 100.0 * fabs(apq);
   if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
     apq = 0.0;
-    return;
+    return false;
   }
   const double h = aqq - app;
   double t;
@@ -200,13 +203,34 @@ M3D_HD void jacobi3_rotate(double& app, double& aqq, double& apq, double& arp, d
     t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
     if (theta < 0.0) t = -t;
   }
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  c = 1.0 / sqrt(t * t + 1.0);
+  s = t * c;
   app -= t * apq;
   aqq += t * apq;
   apq = 0.0;
   const double rp = arp, rq = arq;
   arp = c * rp - s * rq;
   arq = s * rp + c * rq;
+  return true;
+}
+
+M3D_HD void jacobi3_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+  double c, s;
+  (void)jacobi3_rotation(app, aqq, apq, arp, arq, c, s);
+}
+
+// The same rotation, accumulated into the columns p and q of the eigenvector matrix (three rows)
+M3D_HD void jacobi3_rotate_v(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
+                             double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
+  double c, s;
+  if (!jacobi3_rotation(app, aqq, apq, arp, arq, c, s)) return;
+  const double p0 = v0p, q0 = v0q, p1 = v1p, q1 = v1q, p2 = v2p, q2 = v2q;
+  v0p = c * p0 - s * q0;
+  v0q = s * p0 + c * q0;
+  v1p = c * p1 - s * q1;
+  v1q = s * p1 + c * q1;
+  v2p = c * p2 - s * q2;
+  v2q = s * p2 + c * q2;
 }
 
 // The three eigenvalues of the symmetric 3×3 (a00 a01 a02; · a11 a12; · · a22), ascending, by cyclic
@@ -229,6 +253,66 @@ M3D_HD void sym3_eigenvalues(double a00, double a01, double a02, double a11, dou
   lam[0] = a00;
   lam[1] = a11;
   lam[2] = a22;
+}
+
+// sym3_eigenvalues with its rotations accumulated: lam ascending — the same rotations on the same
+// six scalars, hence sym3_eigenvalues' bits — and V (row-major) whose column k is a unit eigenvector
+// of lam[k]: V is a product of at most 36 plane rotations, so VᵀV = I and V·diag(lam)·Vᵀ = A to a
+// few ulps (of the norm).  Scalars only, bounded sweeps, as above.
+M3D_HD void sym3_eigen(double a00, double a01, double a02, double a11, double a12, double a22, double lam[3],
+                       double V[9]) {
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
+    jacobi3_rotate_v(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+    jacobi3_rotate_v(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+    jacobi3_rotate_v(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+  }
+  if (a11 < a00) {
+    swapd(a00, a11);
+    swapd(v00, v01);
+    swapd(v10, v11);
+    swapd(v20, v21);
+  }
+  if (a22 < a11) {
+    swapd(a11, a22);
+    swapd(v01, v02);
+    swapd(v11, v12);
+    swapd(v21, v22);
+  }
+  if (a11 < a00) {
+    swapd(a00, a11);
+    swapd(v00, v01);
+    swapd(v10, v11);
+    swapd(v20, v21);
+  }
+  lam[0] = a00;
+  lam[1] = a11;
+  lam[2] = a22;
+  V[0] = v00;
+  V[1] = v01;
+  V[2] = v02;
+  V[3] = v10;
+  V[4] = v11;
+  V[5] = v12;
+  V[6] = v20;
+  V[7] = v21;
+  V[8] = v22;
+}
+
+// W = M^(−1/2) = V·diag(1/√λ)·Vᵀ of a symmetric positive definite 3×3, the symmetric square root
+// of the inverse (unique: any orthonormal basis of a repeated eigenvalue's space gives the same
+// W).  M and W as upper triangles (xx, xy, xz, yy, yz, zz): W is symmetric in every bit.
+M3D_HD void sym3_inv_sqrt(const double M[6], double W[6]) {
+  double lam[3], V[9];
+  sym3_eigen(M[0], M[1], M[2], M[3], M[4], M[5], lam, V);
+  const double s0 = 1.0 / sqrt(lam[0]), s1 = 1.0 / sqrt(lam[1]), s2 = 1.0 / sqrt(lam[2]);
+  W[0] = ((V[0] * s0) * V[0] + (V[1] * s1) * V[1]) + (V[2] * s2) * V[2];
+  W[1] = ((V[0] * s0) * V[3] + (V[1] * s1) * V[4]) + (V[2] * s2) * V[5];
+  W[2] = ((V[0] * s0) * V[6] + (V[1] * s1) * V[7]) + (V[2] * s2) * V[8];
+  W[3] = ((V[3] * s0) * V[3] + (V[4] * s1) * V[4]) + (V[5] * s2) * V[5];
+  W[4] = ((V[3] * s0) * V[6] + (V[4] * s1) * V[7]) + (V[5] * s2) * V[8];
+  W[5] = ((V[6] * s0) * V[6] + (V[7] * s1) * V[7]) + (V[8] * s2) * V[8];
 }
 
 // Eigen::LDLT-style solve of a symmetric 6×6 system A x = b (A row-major, full).

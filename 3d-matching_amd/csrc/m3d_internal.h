@@ -537,6 +537,13 @@ hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, dou
 hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, double* out6, hipStream_t st);
 hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
                              double* sums, bool with_defer, hipStream_t st);
+// robust.hip: the same two passes with a robust kernel (kind: a checked M3D_KERNEL_*, k its scale);
+// partials: robust_blocks(ns) × kTermSlots doubles
+int64_t robust_blocks(int64_t ns);
+hipError_t launch_robust_plane_terms(const m3d_icp* s, int32_t kind, double k, double* partials, double* sums,
+                                     bool with_defer, hipStream_t st);
+hipError_t launch_robust_gicp_terms(const m3d_icp* s, int32_t kind, double k, double* cov_s, const double* cov_t,
+                                    double* partials, double* sums, bool with_defer, hipStream_t st);
 // claim/dmin: target-shard exchange results (m3d_icp_shard_claim), or null
 hipError_t launch_icp_terms_mode(const m3d_icp* s, int64_t off, const int32_t* claim,
                                  const int64_t* dmin, hipStream_t st);

@@ -27,6 +27,7 @@ KERNEL_NN, KERNEL_SCORE, KERNEL_KABSCH, KERNEL_TERMS, KERNEL_LOOP, KERNEL_COMM =
 ICP_NO_SPLIT = 2
 NN_BRUTE, NN_GRID = 0, 1
 EVAL_INFORMATION = 1
+ROBUST_L2, ROBUST_L1, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_GM, ROBUST_TUKEY = 0, 1, 2, 3, 4, 5  # M3D_KERNEL_L2 ..
 COMM_ID_BYTES = 128
 DT_I32, DT_I64, DT_F64 = 0, 1, 2
 OP_SUM, OP_MIN, OP_MAX = 0, 1, 2
@@ -83,6 +84,10 @@ class EvalResult(C.Structure):
 class GicpParams(C.Structure):
     _fields_ = [("relative_fitness", dbl), ("relative_rmse", dbl), ("max_iteration", i32),
                 ("nn_method", i32), ("epsilon", dbl)]
+
+
+class RobustKernel(C.Structure):
+    _fields_ = [("kind", i32), ("k", dbl)]
 
 
 class OutlierStats(C.Structure):
@@ -161,6 +166,14 @@ SIGNATURES = {
     "m3d_gicp_terms": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, i32, dbl, C.POINTER(dbl), vp, vp]),
     "m3d_gicp_run": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(GicpParams),
                                C.POINTER(IcpResult), vp, vp]),
+    "m3d_robust_terms": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, i32, C.POINTER(RobustKernel), C.POINTER(dbl),
+                                   vp, vp]),
+    "m3d_robust_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams),
+                                     C.POINTER(RobustKernel), C.POINTER(IcpResult), vp, vp]),
+    "m3d_gicp_terms_robust": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, i32, dbl, C.POINTER(RobustKernel),
+                                        C.POINTER(dbl), vp, vp]),
+    "m3d_gicp_run_robust": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(GicpParams),
+                                      C.POINTER(RobustKernel), C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams),
                               C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_create": (C.c_int, [vp, vp, vp, dbl, C.POINTER(IcpParams), C.POINTER(vp)]),
@@ -235,6 +248,7 @@ SIGNATURES = {
     "m3d_debug_kabsch3_host":(C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_ldlt6_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_sym3_eigenvalues_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl)]),
+    "m3d_debug_sym3_eigen_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
 }
 
 _lib = None

@@ -489,22 +489,56 @@ def corr_pairs(ctx: Context, corr, n: int) -> np.ndarray:
     return out[: m.value]
 
 
+def _robust_kernel(kernel):
+    """A robust kernel (matcher.robust: an object with ``kind`` = _lib.ROBUST_* and, where the
+    kernel has a scale, ``k``) as the library's struct; None for no kernel or L2 — the call is then
+    the one without a kernel."""
+    if kernel is None or int(kernel.kind) == _lib.ROBUST_L2:
+        return None
+    return _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
+
+
 def icp(src: Cloud, tgt: Cloud, max_dist: float, init=None, estimation=_lib.EST_POINT_TO_PLANE,
         relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30, with_correspondences=True,
-        nn: str = "grid"):
-    """registration_icp on the device (m3d_icp_run)."""
+        nn: str = "grid", kernel=None):
+    """registration_icp on the device (m3d_icp_run; with a robust kernel other than L2,
+    m3d_robust_icp_run: point-to-plane only)."""
     torch = _torch()
     p = _lib.IcpParams(float(relative_fitness), float(relative_rmse), int(max_iteration), int(estimation),
                        _nn_method(nn), 0)
+    rk = _robust_kernel(kernel)
     res = _lib.IcpResult()
     corr = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
     init16 = _T16(np.eye(4) if init is None else init)
-    src.ctx.check(src.ctx.lib.m3d_icp_run(src.ctx.h, src.h, tgt.h, init16, float(max_dist), C.byref(p),
-                                          C.byref(res), ptr(corr), stream_handle()), "icp_run")
+    if rk is None:
+        src.ctx.check(src.ctx.lib.m3d_icp_run(src.ctx.h, src.h, tgt.h, init16, float(max_dist), C.byref(p),
+                                              C.byref(res), ptr(corr), stream_handle()), "icp_run")
+    else:
+        src.ctx.check(src.ctx.lib.m3d_robust_icp_run(src.ctx.h, src.h, tgt.h, init16, float(max_dist), C.byref(p),
+                                                     C.byref(rk), C.byref(res), ptr(corr), stream_handle()),
+                      "robust_icp_run")
     cs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
     return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
                       res.num_correspondences, res.iterations, bool(res.converged), cs,
                       np.array(res.update[:]).reshape(4, 4))
+
+
+def robust_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, kernel=None, nn: str = "grid",
+                 with_correspondences=True):
+    """One point-to-plane evaluation with a robust kernel at the transform T (m3d_robust_terms) →
+    (sums (30,) f64 in gicp_terms' layout, corr_idx (ns,) int32 torch cuda or None).  Every kind,
+    L2 too, runs through the robust pass here."""
+    method = _nn_method(nn)
+    torch = _torch()
+    if kernel is None:
+        raise ValueError("robust_terms needs a kernel")
+    rk = _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
+    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    sums = (C.c_double * 32)()
+    src.ctx.check(src.ctx.lib.m3d_robust_terms(
+        src.ctx.h, src.h, tgt.h, _T16(np.eye(4) if T is None else T), float(max_dist), method, C.byref(rk), sums,
+        ptr(idx), stream_handle()), "robust_terms")
+    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
 
 
 def _cov_device(cov, n: int, what: str):
@@ -518,11 +552,13 @@ def _cov_device(cov, n: int, what: str):
 
 
 def gicp_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, src_cov=None, tgt_cov=None,
-               epsilon: float = 1e-3, nn: str = "grid", with_correspondences=True):
+               epsilon: float = 1e-3, nn: str = "grid", with_correspondences=True, kernel=None):
     """One Generalized-ICP evaluation at the transform T (m3d_gicp_terms): the exact radius 1-NN,
     then the plane-to-plane sums over the matched pairs → (sums (30,) f64: JᵀJ upper triangle
     row-major, Jᵀr, Σr², count, Σd²; corr_idx (ns,) int32 torch cuda or None).  src_cov / tgt_cov:
-    n×3×3 covariances in the cloud's point order, or None = from the cloud's normals with epsilon."""
+    n×3×3 covariances in the cloud's point order, or None = from the cloud's normals with epsilon.
+    kernel: a robust kernel (m3d_gicp_terms_robust: each whitened row weighted on its own); None or
+    L2 is the call without one."""
     method = _nn_method(nn)
     if not max_dist > 0.0:
         raise ValueError("max_dist must be > 0")
@@ -532,18 +568,26 @@ def gicp_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, src_cov=No
     cs, ct = _cov_device(src_cov, src.n, "source"), _cov_device(tgt_cov, tgt.n, "target")
     idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
     sums = (C.c_double * 32)()
-    src.ctx.check(src.ctx.lib.m3d_gicp_terms(
-        src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), _T16(np.eye(4) if T is None else T), float(max_dist),
-        method, float(epsilon), sums, ptr(idx), stream_handle()), "gicp_terms")
+    rk = _robust_kernel(kernel)
+    T16 = _T16(np.eye(4) if T is None else T)
+    if rk is None:
+        src.ctx.check(src.ctx.lib.m3d_gicp_terms(
+            src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), T16, float(max_dist),
+            method, float(epsilon), sums, ptr(idx), stream_handle()), "gicp_terms")
+    else:
+        src.ctx.check(src.ctx.lib.m3d_gicp_terms_robust(
+            src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), T16, float(max_dist),
+            method, float(epsilon), C.byref(rk), sums, ptr(idx), stream_handle()), "gicp_terms_robust")
     return np.array(sums[:30]), (None if idx is None else idx[: src.n])
 
 
 def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_cov=None,
          epsilon: float = 1e-3, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
-         with_correspondences=True, nn: str = "grid"):
+         with_correspondences=True, nn: str = "grid", kernel=None):
     """registration_generalized_icp on the device (m3d_gicp_run) → IcpOutcome.  src_cov / tgt_cov:
     n×3×3 covariances in the cloud's point order, or None = from the cloud's normals with
-    epsilon (a cloud with neither raises ValueError)."""
+    epsilon (a cloud with neither raises ValueError).  kernel: a robust kernel
+    (m3d_gicp_run_robust); None or L2 is the call without one."""
     method = _nn_method(nn)
     if not max_dist > 0.0:
         raise ValueError("Invalid max_correspondence_distance.")
@@ -555,9 +599,15 @@ def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_c
                         float(epsilon))
     res = _lib.IcpResult()
     corr = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
-    src.ctx.check(src.ctx.lib.m3d_gicp_run(src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct),
-                                           _T16(np.eye(4) if init is None else init), float(max_dist),
-                                           C.byref(p), C.byref(res), ptr(corr), stream_handle()), "gicp_run")
+    rk = _robust_kernel(kernel)
+    init16 = _T16(np.eye(4) if init is None else init)
+    if rk is None:
+        src.ctx.check(src.ctx.lib.m3d_gicp_run(src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), init16, float(max_dist),
+                                               C.byref(p), C.byref(res), ptr(corr), stream_handle()), "gicp_run")
+    else:
+        src.ctx.check(src.ctx.lib.m3d_gicp_run_robust(src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), init16,
+                                                      float(max_dist), C.byref(p), C.byref(rk), C.byref(res),
+                                                      ptr(corr), stream_handle()), "gicp_run_robust")
     pairs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
     return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
                       res.num_correspondences, res.iterations, bool(res.converged), pairs,

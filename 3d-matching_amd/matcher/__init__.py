@@ -30,8 +30,15 @@ from .ransac import (
     run_ransac,
 )
 from .register import register
+from .robust import CauchyLoss, GMLoss, HuberLoss, L1Loss, L2Loss, TukeyLoss
 
 __all__ = [
+    "CauchyLoss",
+    "GMLoss",
+    "HuberLoss",
+    "L1Loss",
+    "L2Loss",
+    "TukeyLoss",
     "compute_feature_correspondences",
     "compute_point_cloud_distance",
     "compute_step_transformation",

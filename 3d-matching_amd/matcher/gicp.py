@@ -43,10 +43,12 @@ def _gicp_cloud(x):
 
 def registration_generalized_icp(source, target, max_correspondence_distance, init=None, epsilon=1e-3,
                                  relative_fitness=1e-6, relative_rmse=1e-6,
-                                 max_iteration=30) -> RegistrationResult:
+                                 max_iteration=30, kernel=None) -> RegistrationResult:
     """Open3D ``registration_generalized_icp(source, target, max_correspondence_distance, init,
-    TransformationEstimationForGeneralizedICP(epsilon), ICPConvergenceCriteria(relative_fitness,
-    relative_rmse, max_iteration))`` on the device."""
+    TransformationEstimationForGeneralizedICP(epsilon, kernel), ICPConvergenceCriteria(
+    relative_fitness, relative_rmse, max_iteration))`` on the device.  ``kernel``: a robust kernel
+    of ``matcher.robust``, applied to each whitened residual row; None or ``L2Loss()`` is the
+    unweighted estimator."""
     if max_correspondence_distance <= 0.0:
         raise ValueError("Invalid max_correspondence_distance.")
     if not epsilon > 0.0:
@@ -56,5 +58,5 @@ def registration_generalized_icp(source, target, max_correspondence_distance, in
     src, tgt = _cache.clouds([(sp, sn), (tp, tn)])
     out = _gicp(src, tgt, max_correspondence_distance, init=np.eye(4) if init is None else init,
                 src_cov=sc, tgt_cov=tc, epsilon=epsilon, relative_fitness=relative_fitness,
-                relative_rmse=relative_rmse, max_iteration=max_iteration)
+                relative_rmse=relative_rmse, max_iteration=max_iteration, kernel=kernel)
     return RegistrationResult(out.transformation, out.fitness, out.inlier_rmse, out.correspondence_set)

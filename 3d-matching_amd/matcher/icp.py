@@ -32,10 +32,15 @@ def _full_cloud(x):
 
 def registration_icp(source, target, max_correspondence_distance, init=None,
                      estimation="point_to_plane", relative_fitness=1e-6, relative_rmse=1e-6,
-                     max_iteration=30) -> RegistrationResult:
-    """Open3D ``pipelines.registration.registration_icp`` semantics on the device."""
+                     max_iteration=30, kernel=None) -> RegistrationResult:
+    """Open3D ``pipelines.registration.registration_icp`` semantics on the device.  ``kernel``: a
+    robust kernel of ``matcher.robust`` for ``TransformationEstimationPointToPlane(kernel)``; None
+    or ``L2Loss()`` is the unweighted estimator.  ``TransformationEstimationPointToPoint`` takes no
+    kernel: one with ``estimation="point_to_point"`` raises ValueError."""
     if max_correspondence_distance <= 0.0:
         raise ValueError("Invalid max_correspondence_distance.")
+    if kernel is not None and estimation == "point_to_point":
+        raise ValueError("TransformationEstimationPointToPoint takes no robust kernel")
     sp, _ = _full_cloud(source)
     tp, tn = _full_cloud(target)
     est = {"point_to_plane": _lib.EST_POINT_TO_PLANE, "point_to_point": _lib.EST_POINT_TO_POINT}[estimation]
@@ -45,11 +50,12 @@ def registration_icp(source, target, max_correspondence_distance, init=None,
     src, tgt = _cache.clouds([(sp, None), (tp, tn if est == _lib.EST_POINT_TO_PLANE else None)])
     out = _icp(src, tgt, max_correspondence_distance, init=np.eye(4) if init is None else init,
                estimation=est, relative_fitness=relative_fitness, relative_rmse=relative_rmse,
-               max_iteration=max_iteration)
+               max_iteration=max_iteration, kernel=kernel)
     return RegistrationResult(out.transformation, out.fitness, out.inlier_rmse, out.correspondence_set)
 
 
-def refine_registration(src, tgt, init_trans, voxel_size) -> RegistrationResult:
-    """icp.py:17-48 — point-to-plane ICP on the full-resolution clouds, radius 0.4·voxel_size."""
+def refine_registration(src, tgt, init_trans, voxel_size, kernel=None) -> RegistrationResult:
+    """icp.py:17-48 — point-to-plane ICP on the full-resolution clouds, radius 0.4·voxel_size
+    (``kernel``: a robust kernel for the estimator, ``registration_icp``'s)."""
     dist_thresh = voxel_size * 0.4
-    return registration_icp(src, tgt, dist_thresh, init_trans, "point_to_plane")
+    return registration_icp(src, tgt, dist_thresh, init_trans, "point_to_plane", kernel=kernel)

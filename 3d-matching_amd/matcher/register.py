@@ -8,7 +8,8 @@ the same two stages on the device:
 1. coarse: ``global_registration`` when both inputs carry FPFH features (``pcd_fpfh``), else the
    step-RANSAC loop (``run_ransac``) over the given ``correspondences``; ``coarse="fgr"`` runs Fast
    Global Registration instead (``matcher.fgr``: no sample budget, no dependence on a seed's luck);
-2. fine: ``refine_registration`` (point-to-plane ICP, radius 0.4·voxel) from the coarse result.
+2. fine: ``refine_registration`` (point-to-plane ICP, radius 0.4·voxel) from the coarse result;
+   ``kernel``: a robust kernel of ``matcher.robust`` for that stage.
 """
 
 from __future__ import annotations
@@ -19,13 +20,15 @@ from .ransac import global_registration, run_ransac
 
 
 def register(source, target, voxel_size=None, correspondences=None, ransac_iterations: int = 10000,
-             refine: bool = True, iteration: int = 30, coarse: str = "ransac", fgr_option=None, **ransac_kwargs):
+             refine: bool = True, iteration: int = 30, coarse: str = "ransac", fgr_option=None, kernel=None,
+             **ransac_kwargs):
     """Return the refined ``RegistrationResult`` mapping ``source`` onto ``target``.
 
     ``iteration``: RANSACConvergenceCriteria max_iteration of the feature path
     (global_registration's own default, 30); ``ransac_iterations``: hypotheses of the
     correspondence path.  ``coarse``: "ransac" (the default) or "fgr" (``fgr_option``: a
-    ``FastGlobalRegistrationOption``; default maximum_correspondence_distance = 0.5·voxel)."""
+    ``FastGlobalRegistrationOption``; default maximum_correspondence_distance = 0.5·voxel).
+    ``kernel``: the ICP stage's robust kernel (``refine_registration``'s)."""
     v = voxel_size if voxel_size is not None else getattr(source, "voxel_size", 0.3)
     if coarse not in ("ransac", "fgr"):
         raise ValueError("coarse must be 'ransac' or 'fgr'")
@@ -43,7 +46,7 @@ def register(source, target, voxel_size=None, correspondences=None, ransac_itera
             first = registration_fgr_based_on_correspondence(source, target, correspondences, fgr_option)
         else:
             raise ValueError("register needs FPFH features on both inputs (pcd_fpfh) or correspondences")
-        return first if not refine else refine_registration(source, target, first.transformation, v)
+        return first if not refine else refine_registration(source, target, first.transformation, v, kernel)
     if correspondences is None and getattr(source, "pcd_fpfh", None) is not None \
             and getattr(target, "pcd_fpfh", None) is not None:
         coarse = global_registration(source, target, v, iteration=iteration)
@@ -54,4 +57,4 @@ def register(source, target, voxel_size=None, correspondences=None, ransac_itera
         raise ValueError("register needs FPFH features on both inputs (pcd_fpfh) or correspondences")
     if not refine:
         return coarse
-    return refine_registration(source, target, coarse.transformation, v)
+    return refine_registration(source, target, coarse.transformation, v, kernel)

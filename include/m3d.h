@@ -468,6 +468,59 @@ int m3d_gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const
                  const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
                  m3d_icp_result* out, int32_t* corr_idx, void* stream);
 
+/* ------------------------------------------------------------------ robust kernels (robust.hip)
+ * Open3D 0.19 RobustKernel.cpp inside TransformationEstimationPointToPlane(kernel) and
+ * TransformationEstimationForGeneralizedICP(epsilon, kernel), restated in
+ * tests/robust_restatement.py; added within ABI 13, the version number is unchanged.  A residual r
+ * gets the weight w(r), k the kernel's scale:
+ *   L2 1 | L1 1/|r| | Huber k/max(|r|, k) | Cauchy 1/(1 + (r/k)^2) | GM k/(k + r^2)^2 |
+ *   Tukey (1 - min(1, |r/k|)^2)^2
+ * and a row (J, r) adds w J J^T to JtJ, w J r to Jtr and r^2 (unweighted) to sum r^2.
+ * Point-to-plane has one row per matched pair: r = (vs - vt) . nt, J = [vs x nt | nt].
+ * Generalized ICP has three, each weighted on its own: W = (Ct + Cs)^(-1/2), the symmetric root,
+ * r_j = W.row(j) d, J_j = (W J0).row(j).  L1 at r = 0 gives an infinite weight, literally: the
+ * update is then non-finite and the loop replaces it by the identity, as for any non-finite
+ * update.  Everything else (NN search, transformed copy, fitness / inlier_rmse from the NN
+ * distances, convergence rule, LDLT solve, slot layout, fixed summation order) is m3d_icp_run's. */
+#define M3D_KERNEL_L2 0
+#define M3D_KERNEL_L1 1
+#define M3D_KERNEL_HUBER 2
+#define M3D_KERNEL_CAUCHY 3
+#define M3D_KERNEL_GM 4
+#define M3D_KERNEL_TUKEY 5
+
+typedef struct {
+  int32_t kind; /* M3D_KERNEL_L2 .. M3D_KERNEL_TUKEY */
+  double k;     /* the scale; read by Huber, Cauchy, GM and Tukey: finite and > 0 */
+} m3d_robust_kernel;
+
+/* One point-to-plane evaluation with `kernel`, as m3d_gicp_terms: T_host applied unless
+ * isIdentity(), the exact radius 1-NN, then sums_out [host] 32 f64 in the same layout.  Here, and
+ * only here, kind L2 also runs through robust.hip's pass (its check against the point-to-plane
+ * oracle).  M3D_ERR_INVALID for an unknown kind, a k <= 0 or non-finite for a kind that reads k, a
+ * target without normals, max_dist <= 0 or an unknown nn_method.  Synchronous. */
+int m3d_robust_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* T_host,
+                     double max_dist, int32_t nn_method, const m3d_robust_kernel* kernel, double* sums_out,
+                     int32_t* corr_idx, void* stream);
+
+/* registration_icp with TransformationEstimationPointToPlane(kernel): m3d_icp_run's loop with the
+ * robust point-to-plane terms, three launches per iteration.  params->estimation must be
+ * M3D_EST_POINT_TO_PLANE (TransformationEstimationPointToPoint takes no kernel); other errors as
+ * m3d_robust_terms and m3d_icp_run.  Synchronous. */
+int m3d_robust_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* init,
+                       double max_dist, const m3d_icp_params* params, const m3d_robust_kernel* kernel,
+                       m3d_icp_result* out, int32_t* corr_idx, void* stream);
+
+/* m3d_gicp_terms / m3d_gicp_run with a kernel (NULL or kind L2: exactly those calls). */
+int m3d_gicp_terms_robust(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                          const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
+                          double epsilon, const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx,
+                          void* stream);
+int m3d_gicp_run_robust(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+                        const double* tgt_cov, const double* init, double max_dist,
+                        const m3d_gicp_params* params, const m3d_robust_kernel* kernel, m3d_icp_result* out,
+                        int32_t* corr_idx, void* stream);
+
 /* ------------------------------------------------------------------ preprocessing
  * Open3D 0.19 semantics restated (oracle/prep_oracle.py); all fp64. */
 
@@ -807,6 +860,8 @@ int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6);  // t
                                                                        // rule: unpivoted, pivoted fallback
 /* linalg.h sym3_eigenvalues, compiled for the host: sym6 = (a00, a01, a02, a11, a12, a22) → lam3 ascending */
 int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3);
+/* linalg.h sym3_eigen, compiled for the host: lam3 as above, V9 row-major, column k a unit eigenvector of lam3[k] */
+int m3d_debug_sym3_eigen_host(const double* sym6, double* lam3, double* V9);
 /* XXH64 of [p, p + len) (the chunk hash of m3d_content_keys; known-answer tests). */
 uint64_t m3d_debug_xxh64(const void* p, size_t len, uint64_t seed);
 /* XXH3-128 (default secret, seed 0) of [p, p + len), len >= 241 (the long-input path the content
