@@ -2,12 +2,11 @@
 // every point of a cloud), PointCloud::RemoveStatisticalOutliers and RemoveRadiusOutliers
 // (Open3D 0.19 semantics), the kept indices compacted on the device in ascending order.
 //
-// All arithmetic is fp64 in the project's operation order (-ffp-contract=off):
-// d² = (dx·dx + dy·dy) + dz·dz on the cloud's original coordinates, lists in ascending (d², index)
-// order.  The centred fp32 grid points only screen candidates (prefilter_bound) and size the cell
-// box (box_half_width): a candidate the screen passes is decided by its exact d², one it drops is
-// provably outside the current threshold.  The wave-held sorted list, the box scan that fills it
-// and their exactness argument live in knn_wave.h, shared with prep.hip's hybrid search.
+// All arithmetic is fp64 in the project's operation order (-ffp-contract=off), lists in ascending
+// (d², index) order.  The scans — the cell-box walk, the fixed-radius scan, the wave-held sorted list
+// of the k-NN ladder — and their exactness argument (the fp32 screen, the exact d²) live in
+// knn_wave.h, shared with prep.hip, cluster.hip and iss.hip; radius_count_kernel is that header's
+// fixed-radius scan written out.
 //
 // Unbounded k-NN = a radius ladder over uniform grids (knn_ladder).  Level ℓ searches the still
 // pending queries on a grid of cell r_ℓ (r₀, then at least doubling) with the hybrid search's rule
@@ -147,6 +146,8 @@ __global__ __launch_bounds__(kCleanBlock) void radius_count_kernel(
   const int64_t i = (int64_t)__float_as_int(g.pts[wq].w);
   const double q[3] = {xyz64[3 * i], xyz64[3 * i + 1], xyz64[3 * i + 2]};
   const float4 qf = xyz32[i];
+  // knn_wave.h wave_scan_box's walk, screen and test written out: through the shared scan this
+  // kernel's full count measured 0.2 % above the parent's range at large radii (EXPERIMENTS §R24)
   const int x0 = grid_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
   const int x1 = grid_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
   const int y0 = grid_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
@@ -206,17 +207,40 @@ __global__ __launch_bounds__(kCleanBlock) void axis_hist_kernel(const float4* __
 // stats (device, kStatWords doubles): [0] valid, [1] mean, [2] std_dev, [3] threshold
 constexpr int kStatWords = 4;
 
-__device__ __forceinline__ double cl_wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+// level 1 of a fixed-order sum: the block's 256 values v → partials[blockIdx.x] (each wave an xor
+// butterfly, the four wave sums in wave order)
+__device__ __forceinline__ void block_sum_partial(double v, double* __restrict__ partials) {
+  __shared__ double red[kCleanBlock / kWave];
+  const double t = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < kCleanBlock / kWave; ++k) s += red[k];
+    partials[blockIdx.x] = s;
+  }
+}
+
+// level 2, one block: thread t adds partials t, t + 256, … in increasing order, then a fixed LDS
+// tree over the 256 sums; thread 0 hands the total to done(sum)
+template <class Done>
+__device__ __forceinline__ void block_sum_final(const double* __restrict__ partials, int64_t nb, Done&& done) {
+  __shared__ double red[kCleanBlock];
+  double v = 0.0;
+  for (int64_t b = threadIdx.x; b < nb; b += kCleanBlock) v += partials[b];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = kCleanBlock / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) done(red[0]);
 }
 
 // pass 0: Σ avg over avg > 0; pass 1: Σ (avg − mean)² over avg > 0 (mean = stats[1])
 __global__ __launch_bounds__(kCleanBlock) void stat_partial_kernel(const double* __restrict__ avg, int64_t n,
                                                                    int pass, const double* __restrict__ stats,
                                                                    double* __restrict__ partials) {
-  __shared__ double red[kCleanBlock / kWave];
   const int64_t i = (int64_t)blockIdx.x * kCleanBlock + threadIdx.x;
   double v = 0.0;
   if (i < n) {
@@ -230,39 +254,23 @@ __global__ __launch_bounds__(kCleanBlock) void stat_partial_kernel(const double*
       }
     }
   }
-  const double t = cl_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < kCleanBlock / kWave; ++k) s += red[k];
-    partials[blockIdx.x] = s;
-  }
+  block_sum_partial(v, partials);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void stat_final_kernel(const double* __restrict__ partials, int64_t nb,
                                                                  int64_t n, int pass, double std_ratio,
                                                                  double* __restrict__ stats) {
-  __shared__ double red[kCleanBlock];
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += kCleanBlock) v += partials[b];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = kCleanBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
+  block_sum_final(partials, nb, [&](const double& sum) {
     const double valid = (double)n;  // every point's list holds at least the point itself
     if (pass == 0) {
       stats[0] = valid;
-      stats[1] = red[0] / valid;
+      stats[1] = sum / valid;
     } else {
-      const double sd = sqrt(red[0] / (valid - 1.0));  // n = 1: 0 / 0 = NaN, nothing is kept
+      const double sd = sqrt(sum / (valid - 1.0));  // n = 1: 0 / 0 = NaN, nothing is kept
       stats[2] = sd;
       stats[3] = stats[1] + std_ratio * sd;
     }
-  }
+  });
 }
 
 __global__ __launch_bounds__(kCleanBlock) void stat_flag_kernel(const double* __restrict__ avg, int64_t n,
@@ -279,58 +287,45 @@ __global__ __launch_bounds__(kCleanBlock) void stat_flag_kernel(const double* __
 // stat_partial_kernel; then res = the partials' fixed-order sum / n → stats[0]
 __global__ __launch_bounds__(kCleanBlock) void res_partial_kernel(const double* __restrict__ avg, int64_t n,
                                                                   double* __restrict__ partials) {
-  __shared__ double red[kCleanBlock / kWave];
   const int64_t i = (int64_t)blockIdx.x * kCleanBlock + threadIdx.x;
-  const double t = cl_wave_sum(i < n ? 2.0 * avg[i] : 0.0);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < kCleanBlock / kWave; ++k) s += red[k];
-    partials[blockIdx.x] = s;
-  }
+  block_sum_partial(i < n ? 2.0 * avg[i] : 0.0, partials);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void res_final_kernel(const double* __restrict__ partials, int64_t nb,
                                                                 int64_t n, double* __restrict__ stats) {
-  __shared__ double red[kCleanBlock];
-  double v = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += kCleanBlock) v += partials[b];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = kCleanBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) stats[0] = red[0] / (double)n;
+  block_sum_final(partials, nb, [&](const double& sum) { stats[0] = sum / (double)n; });
 }
 
 // ------------------------------------------------------------------------------- host side
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// the pieces of a call's scratch for n points, placed onto `scratch` (null: the layout's size alone)
 struct CleanScratch {
-  size_t pend_a, pend_b, cnt, avg, keep, partials, stats, nsel, tmp, tmp_bytes, total;
+  int32_t *pend_a = nullptr, *pend_b = nullptr;
+  uint32_t* cnt = nullptr;
+  double* avg = nullptr;
+  uint8_t* keep = nullptr;
+  double *partials = nullptr, *stats = nullptr;
+  int32_t* nsel = nullptr;
+  char* tmp = nullptr;
+  size_t tmp_bytes = 0, bytes = 0;
+  CleanScratch(int64_t n, void* scratch) {
+    size_t tb = 0;
+    hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int32_t>(0), (uint8_t*)nullptr,
+                                  (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
+    tmp_bytes = std::max<size_t>(tb, 1);
+    Carve cv;
+    cv.add(&pend_a, (size_t)n);
+    cv.add(&pend_b, (size_t)n);
+    cv.add(&cnt, kMaxLevels);
+    cv.add(&avg, (size_t)n);
+    cv.add(&keep, (size_t)n);
+    cv.add(&partials, (size_t)((n + kCleanBlock - 1) / kCleanBlock));
+    cv.add(&stats, kStatWords);
+    cv.add(&nsel, 1);
+    cv.add(&tmp, tmp_bytes);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
-CleanScratch clean_layout(int64_t n) {
-  CleanScratch L{};
-  size_t tb = 0;
-  hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int32_t>(0), (uint8_t*)nullptr,
-                                (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
-  L.tmp_bytes = std::max<size_t>(tb, 1);
-  const size_t nb = (size_t)((n + kCleanBlock - 1) / kCleanBlock);
-  size_t o = 0;
-  L.pend_a = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.pend_b = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.cnt = o, o += up256(sizeof(uint32_t) * kMaxLevels);
-  L.avg = o, o += up256(sizeof(double) * (size_t)n);
-  L.keep = o, o += up256((size_t)n);
-  L.partials = o, o += up256(sizeof(double) * nb);
-  L.stats = o, o += up256(sizeof(double) * kStatWords);
-  L.nsel = o, o += up256(sizeof(int32_t));
-  L.tmp = o, o += up256(L.tmp_bytes);
-  L.total = o;
-  return L;
-}
 
 // a grid of the call itself (not cached on the cloud); released after the stream has synced
 hipError_t local_grid(m3d_ctx* ctx, const m3d_cloud* c, const float* lohi, double cell, hipStream_t st, Grid* g) {
@@ -366,7 +361,7 @@ double ladder_end(const m3d_cloud* c) {
 // The box the call's grids span.  A grid spans its bounds with at most 2²⁵ cells, so a few points far
 // outside the scan (a scanner glitch at 10³ object sizes) would force cells so large that the
 // whole scan sits in a handful of them and level 0 compares every point with every other.  The
-// cell coordinate clamps to the grid (grid.hip grid_coord) for points and for a query's box ends
+// cell coordinate clamps to the grid (the one expression of nnkey.h) for points and for a query's box ends
 // alike and stays monotone, so a grid over ANY box visits every point within the radius: points
 // outside the box simply share its edge cells.  Per axis the box is cut where at most n / 256
 // points lie beyond (1024-bin histograms, one bin of margin), and only if that halves an axis;
@@ -525,11 +520,11 @@ hipError_t launch_level(const m3d_cloud* c, const Grid& g, double radius, int k,
 // the ladder: lists (idx, d2, cnt) or, with avg, the mean neighbour distances.  n ≥ 1,
 // 1 ≤ k ≤ 256.  Returns after the last level has synced.
 hipError_t knn_ladder(m3d_ctx* ctx, const m3d_cloud* c, int k, int32_t* idx, double* d2, int32_t* cnt,
-                      double* avg, char* S, const CleanScratch& L, hipStream_t st, std::string* why) {
+                      double* avg, const CleanScratch& L, hipStream_t st, std::string* why) {
   const int64_t n = c->n;
   const int kk = (int)std::min<int64_t>(k, n);
-  int32_t* pend[2] = {reinterpret_cast<int32_t*>(S + L.pend_a), reinterpret_cast<int32_t*>(S + L.pend_b)};
-  uint32_t* pcnt = reinterpret_cast<uint32_t*>(S + L.cnt);
+  int32_t* pend[2] = {L.pend_a, L.pend_b};
+  uint32_t* pcnt = L.cnt;
   const double end = ladder_end(c);
   float box[6];  // the box every grid of this call spans (the cloud's bounds, cut by robust_bounds)
   for (int a = 0; a < 3; ++a) {
@@ -594,11 +589,11 @@ hipError_t knn_ladder(m3d_ctx* ctx, const m3d_cloud* c, int k, int32_t* idx, dou
 }
 
 // keep flags → ascending kept indices (a stable select over 0 .. n − 1) and their number
-hipError_t select_kept(const uint8_t* keep, int64_t n, int32_t* index_out, int64_t* n_out, char* S,
-                       const CleanScratch& L, hipStream_t st) {
-  int32_t* nsel = reinterpret_cast<int32_t*>(S + L.nsel);
+hipError_t select_kept(const uint8_t* keep, int64_t n, int32_t* index_out, int64_t* n_out, const CleanScratch& L,
+                       hipStream_t st) {
+  int32_t* nsel = L.nsel;
   size_t tb = L.tmp_bytes;
-  hipError_t e = hipcub::DeviceSelect::Flagged(S + L.tmp, tb, hipcub::CountingInputIterator<int32_t>(0), keep,
+  hipError_t e = hipcub::DeviceSelect::Flagged(L.tmp, tb, hipcub::CountingInputIterator<int32_t>(0), keep,
                                                index_out, nsel, (int)n, st);
   int32_t h = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&h, nsel, sizeof(h), hipMemcpyDeviceToHost, st);
@@ -609,26 +604,24 @@ hipError_t select_kept(const uint8_t* keep, int64_t n, int32_t* index_out, int64
 
 }  // namespace
 
-size_t clean_scratch_bytes(int64_t n) { return n > 0 ? clean_layout(n).total : 0; }
+size_t clean_scratch_bytes(int64_t n) { return n > 0 ? CleanScratch(n, nullptr).bytes : 0; }
 
 hipError_t knn_search(m3d_ctx* ctx, const m3d_cloud* c, int k, int32_t* idx, double* d2, int32_t* cnt,
                       void* scratch, hipStream_t st, std::string* why) {
   if (c->n == 0) return hipSuccess;
-  return knn_ladder(ctx, c, k, idx, d2, cnt, nullptr, static_cast<char*>(scratch), clean_layout(c->n), st, why);
+  return knn_ladder(ctx, c, k, idx, d2, cnt, nullptr, CleanScratch(c->n, scratch), st, why);
 }
 
 hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double std_ratio, int32_t* index_out,
                                 int64_t* n_out, double stats_out[4], double* avg_out, void* scratch,
                                 hipStream_t st, std::string* why) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const CleanScratch L = clean_layout(n);
-  double* avg = avg_out != nullptr ? avg_out : reinterpret_cast<double*>(S + L.avg);
-  hipError_t e = knn_ladder(ctx, c, k, nullptr, nullptr, nullptr, avg, S, L, st, why);
+  const CleanScratch L(n, scratch);
+  double* avg = avg_out != nullptr ? avg_out : L.avg;
+  hipError_t e = knn_ladder(ctx, c, k, nullptr, nullptr, nullptr, avg, L, st, why);
   if (e != hipSuccess) return e;
-  double* partials = reinterpret_cast<double*>(S + L.partials);
-  double* stats = reinterpret_cast<double*>(S + L.stats);
-  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
+  double *partials = L.partials, *stats = L.stats;
+  uint8_t* keep = L.keep;
   const unsigned nb = (unsigned)((n + kCleanBlock - 1) / kCleanBlock);
   for (int pass = 0; pass < 2; ++pass) {
     stat_partial_kernel<<<nb, kCleanBlock, 0, st>>>(avg, n, pass, stats, partials);
@@ -638,19 +631,16 @@ hipError_t statistical_outliers(m3d_ctx* ctx, const m3d_cloud* c, int k, double 
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(stats_out, stats, sizeof(double) * kStatWords, hipMemcpyDeviceToHost, st)) != hipSuccess)
     return e;
-  return select_kept(keep, n, index_out, n_out, S, L, st);  // syncs: stats_out is complete too
+  return select_kept(keep, n, index_out, n_out, L, st);  // syncs: stats_out is complete too
 }
 
 hipError_t model_resolution(m3d_ctx* ctx, const m3d_cloud* c, double* res_out, void* scratch, hipStream_t st,
                             std::string* why) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const CleanScratch L = clean_layout(n);
-  double* avg = reinterpret_cast<double*>(S + L.avg);
-  hipError_t e = knn_ladder(ctx, c, 2, nullptr, nullptr, nullptr, avg, S, L, st, why);
+  const CleanScratch L(n, scratch);
+  double *avg = L.avg, *partials = L.partials, *stats = L.stats;
+  hipError_t e = knn_ladder(ctx, c, 2, nullptr, nullptr, nullptr, avg, L, st, why);
   if (e != hipSuccess) return e;
-  double* partials = reinterpret_cast<double*>(S + L.partials);
-  double* stats = reinterpret_cast<double*>(S + L.stats);
   const unsigned nb = (unsigned)((n + kCleanBlock - 1) / kCleanBlock);
   res_partial_kernel<<<nb, kCleanBlock, 0, st>>>(avg, n, partials);
   res_final_kernel<<<1, kCleanBlock, 0, st>>>(partials, (int64_t)nb, n, stats);
@@ -661,21 +651,19 @@ hipError_t model_resolution(m3d_ctx* ctx, const m3d_cloud* c, double* res_out, v
 
 hipError_t select_flagged(const uint8_t* keep, int64_t n, int32_t* index_out, int64_t* n_out, void* scratch,
                           hipStream_t st) {
-  return select_kept(keep, n, index_out, n_out, static_cast<char*>(scratch), clean_layout(n), st);
+  return select_kept(keep, n, index_out, n_out, CleanScratch(n, scratch), st);
 }
 
 hipError_t radius_flags(const m3d_cloud* c, const Grid* g, int32_t nb_points, double radius, int32_t* count_out,
                         uint8_t* keep, hipStream_t st) {
   const int64_t n = c->n;
-  const float Rf = box_half_width(c, radius);
-  const double r2 = radius * radius;
-  const float bf = prefilter_bound(r2, pair_eabs(c));  // the threshold is r² throughout: one bound
+  const RadiusScreen s = radius_screen(c, radius);
   const unsigned blocks = (unsigned)((n + 3) / 4);
   if (count_out != nullptr)
-    radius_count_kernel<true><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf,
+    radius_count_kernel<true><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, s.Rf, s.r2, s.bf,
                                                              nb_points, count_out, keep);
   else
-    radius_count_kernel<false><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf,
+    radius_count_kernel<false><<<blocks, kCleanBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, s.Rf, s.r2, s.bf,
                                                               nb_points, nullptr, keep);
   return hipGetLastError();
 }
@@ -684,12 +672,10 @@ hipError_t radius_outliers(const m3d_cloud* c, const Grid* g, int32_t nb_points,
                            int32_t* index_out, int64_t* n_out, int32_t* count_out, void* scratch,
                            hipStream_t st) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const CleanScratch L = clean_layout(n);
-  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
-  hipError_t e = radius_flags(c, g, nb_points, radius, count_out, keep, st);
+  const CleanScratch L(n, scratch);
+  hipError_t e = radius_flags(c, g, nb_points, radius, count_out, L.keep, st);
   if (e != hipSuccess) return e;
-  return select_kept(keep, n, index_out, n_out, S, L, st);
+  return select_kept(L.keep, n, index_out, n_out, L, st);
 }
 
 }  // namespace m3d

@@ -1,9 +1,8 @@
 // cluster.hip — DBSCAN on the device: Open3D 0.19 PointCloud::ClusterDBSCAN's labels in closed form.
 //
-// nbs[i] = {j : d²(i, j) < eps²} (strict, the point itself included), d² = (dx·dx + dy·dy) + dz·dz in
-// fp64 on the cloud's original coordinates (-ffp-contract=off), decided behind the fp32 screen of
-// clean.hip's radius count (prefilter_bound / box_half_width: a candidate the screen drops is provably
-// outside).  core[i] = |nbs[i]| ≥ min_points.  Open3D's sequential loop gives, whatever order its
+// nbs[i] = {j : d²(i, j) < eps²} (strict, the point itself included): the fixed-radius scan of
+// knn_wave.h (wave_scan_box; its contract and exactness argument are stated there).
+// core[i] = |nbs[i]| ≥ min_points.  Open3D's sequential loop gives, whatever order its
 // unordered_set pops in:
 //   core point      → the rank of its connected component in the graph on core points with an edge
 //                     for every core pair with d² < eps², components ranked by smallest member index;
@@ -102,42 +101,6 @@ __device__ __forceinline__ bool uf_unite(int32_t* parent, int32_t a, int32_t b, 
   return false;
 }
 
-// The box scan shared by the link and label kernels: for every 64-candidate chunk of the query's
-// cell rows, pre(t) in the lanes whose candidate t passes the fp32 screen — BEFORE the exact test
-// reads the candidate's coordinates, so what pre loads is in flight beside them — then, in every
-// lane, f(in, t) with `in` the exact test d² < r².
-template <class Pre, class F>
-__device__ __forceinline__ void scan_box(const double* __restrict__ xyz64, const double* q, float4 qf,
-                                         const GridDev& g, float Rf, double r2, float bf, int lane, Pre&& pre,
-                                         F&& f) {
-  const int x0 = grid_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
-  const int x1 = grid_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
-  const int y0 = grid_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
-  const int y1 = grid_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
-  const int z0 = grid_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
-  const int z1 = grid_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
-  for (int cz = z0; cz <= z1; ++cz)
-    for (int cy = y0; cy <= y1; ++cy) {
-      const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
-      const int32_t j0 = g.start[row + x0], j1 = g.start[row + x1 + 1];
-      for (int32_t jb = j0; jb < j1; jb += 64) {
-        const int32_t j = jb + lane;
-        bool in = false;
-        int32_t t = 0;
-        if (j < j1) {
-          const float4 tp = g.pts[j];
-          t = __float_as_int(tp.w);
-          const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
-          if ((fx * fx + fy * fy) + fz * fz <= bf) {
-            pre(t);
-            in = d2_exact(xyz64 + 3 * (int64_t)t, q) < r2;
-          }
-        }
-        f(in, t);
-      }
-    }
-}
-
 // parent[i] = i, sizes[i] = 0, the stats words zero
 __global__ __launch_bounds__(kClBlock) void init_kernel(int64_t n, int32_t* __restrict__ parent,
                                                         int32_t* __restrict__ sizes, int32_t* __restrict__ stats) {
@@ -169,21 +132,22 @@ __global__ __launch_bounds__(kClBlock) void link_kernel(const double* __restrict
   // unite; then i's root is read again.
   int32_t ri = i, p = 0;
   bool c = false;
-  scan_box(
+  wave_scan_box(
       xyz64, q, xyz32[i], g, Rf, r2, bf, lane,
       [&](int32_t t) {
         c = t < i && core[t] != 0;
         p = uf_load(parent, t);
       },
-      [&](bool in, int32_t t) {
+      [&](bool in, int32_t t, double, double, double) {
         const bool edge = in && c;  // in: this chunk's pre ran in this lane
         int32_t rt = ri;
         if (edge && p != ri) rt = p == t ? t : uf_find(parent, t, cap);
         if (rt < 0) ok = false, rt = ri;
-        if (__ballot(rt != ri) == 0) return;  // wave-uniform
+        if (__ballot(rt != ri) == 0) return false;  // wave-uniform
         if (rt != ri) ok = uf_unite(parent, ri, rt, cap) && ok;
         ri = __builtin_amdgcn_readfirstlane(uf_find(parent, i, cap));
         if (ri < 0) ok = false, ri = i;
+        return false;  // the whole box
       });
   if (!ok) atomicOr(stats + kStFault, 1);
 }
@@ -227,14 +191,15 @@ __global__ __launch_bounds__(kClBlock) void label_kernel(const double* __restric
   const double q[3] = {xyz64[3 * (int64_t)i], xyz64[3 * (int64_t)i + 1], xyz64[3 * (int64_t)i + 2]};
   int32_t best = INT32_MAX, p = 0;
   bool c = false;
-  scan_box(
+  wave_scan_box(
       xyz64, q, xyz32[i], g, Rf, r2, bf, lane,
       [&](int32_t t) {
         c = core[t] != 0;
         p = parent[t];
       },
-      [&](bool in, int32_t t) {
+      [&](bool in, int32_t, double, double, double) {
         if (in && c) best = min(best, p);
+        return false;  // the whole box
       });
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
@@ -285,31 +250,32 @@ __global__ __launch_bounds__(kClBlock) void largest_kernel(int64_t n, const int3
   if ((threadIdx.x & 63) == 0 && b != 0) atomicMax(best, b);
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// the pieces of a call's scratch for n points, placed onto `scratch` (null: the layout's size alone)
 struct ClusterScratch {
-  size_t core, parent, root, rank, sizes, stats, tmp, tmp_bytes, total;
+  uint8_t* core = nullptr;
+  int32_t *parent = nullptr, *root = nullptr, *rank = nullptr, *sizes = nullptr, *stats = nullptr;
+  char* tmp = nullptr;
+  size_t tmp_bytes = 0, bytes = 0;
+  ClusterScratch(int64_t n, void* scratch) {
+    size_t tb = 0;
+    hipcub::DeviceScan::InclusiveSum(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
+    tmp_bytes = std::max<size_t>(tb, 1);
+    Carve cv;
+    cv.add(&core, (size_t)n);
+    cv.add(&parent, (size_t)n);
+    cv.add(&root, (size_t)n);
+    cv.add(&rank, (size_t)n);
+    cv.add(&sizes, (size_t)n);
+    cv.add(&stats, kStWords);
+    cv.add(&tmp, tmp_bytes);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
-ClusterScratch cluster_layout(int64_t n) {
-  ClusterScratch L{};
-  size_t tb = 0;
-  hipcub::DeviceScan::InclusiveSum(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
-  L.tmp_bytes = std::max<size_t>(tb, 1);
-  size_t o = 0;
-  L.core = o, o += up256((size_t)n);
-  L.parent = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.root = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.rank = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.sizes = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.stats = o, o += up256(sizeof(int32_t) * kStWords);
-  L.tmp = o, o += up256(L.tmp_bytes);
-  L.total = o;
-  return L;
-}
 
 }  // namespace
 
-size_t cluster_scratch_bytes(int64_t n) { return n > 0 ? cluster_layout(n).total : 0; }
+size_t cluster_scratch_bytes(int64_t n) { return n > 0 ? ClusterScratch(n, nullptr).bytes : 0; }
 
 // Profiling (m3d_profile_*): core flags under M3D_KERNEL_SCORE, link under M3D_KERNEL_NN, flatten
 // and the root scan under M3D_KERNEL_LOOP, label under M3D_KERNEL_TERMS, sizes / counts / largest
@@ -318,17 +284,11 @@ hipError_t cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* c, const Grid* g, doubl
                           int32_t* labels_out, m3d_dbscan_result* out, int32_t* sizes_out, int32_t* count_out,
                           void* scratch, hipStream_t st, std::string* why) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const ClusterScratch L = cluster_layout(n);
-  uint8_t* core = reinterpret_cast<uint8_t*>(S + L.core);
-  int32_t* parent = reinterpret_cast<int32_t*>(S + L.parent);
-  int32_t* root = reinterpret_cast<int32_t*>(S + L.root);
-  int32_t* rank = reinterpret_cast<int32_t*>(S + L.rank);
-  int32_t* sizes = sizes_out != nullptr ? sizes_out : reinterpret_cast<int32_t*>(S + L.sizes);
-  int32_t* stats = reinterpret_cast<int32_t*>(S + L.stats);
-  const float Rf = box_half_width(c, eps);
-  const double r2 = eps * eps;
-  const float bf = prefilter_bound(r2, pair_eabs(c));
+  const ClusterScratch L(n, scratch);
+  uint8_t* core = L.core;
+  int32_t *parent = L.parent, *root = L.root, *rank = L.rank, *stats = L.stats;
+  int32_t* sizes = sizes_out != nullptr ? sizes_out : L.sizes;
+  const RadiusScreen s = radius_screen(c, eps);
   const unsigned per_thread = (unsigned)((n + kClBlock - 1) / kClBlock);
   const unsigned per_wave = (unsigned)((n + kClWaves - 1) / kClWaves);
   hipError_t e = hipSuccess;
@@ -340,7 +300,7 @@ hipError_t cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* c, const Grid* g, doubl
   }
   {
     KTimer t(ctx, M3D_KERNEL_NN, st);
-    link_kernel<<<per_wave, kClBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf, core, parent, stats);
+    link_kernel<<<per_wave, kClBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, s.Rf, s.r2, s.bf, core, parent, stats);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   {
@@ -348,12 +308,12 @@ hipError_t cluster_dbscan(m3d_ctx* ctx, const m3d_cloud* c, const Grid* g, doubl
     flatten_kernel<<<per_thread, kClBlock, 0, st>>>(n, core, parent, root, stats);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t tb = L.tmp_bytes;
-    if ((e = hipcub::DeviceScan::InclusiveSum(S + L.tmp, tb, root, rank, (int)n, st)) != hipSuccess) return e;
+    if ((e = hipcub::DeviceScan::InclusiveSum(L.tmp, tb, root, rank, (int)n, st)) != hipSuccess) return e;
   }
   {
     KTimer t(ctx, M3D_KERNEL_TERMS, st);
-    label_kernel<<<per_wave, kClBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, Rf, r2, bf, core, parent, rank,
-                                                labels_out);
+    label_kernel<<<per_wave, kClBlock, 0, st>>>(c->xyz64, c->xyz32, n, g->dev, s.Rf, s.r2, s.bf, core, parent,
+                                                rank, labels_out);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   {

@@ -28,6 +28,7 @@
 #include "linalg.h"
 #include "m3d_internal.h"
 #include "nnkey.h"
+#include "sampler.h"
 
 namespace m3d {
 
@@ -208,25 +209,17 @@ hipError_t feature_correspondences(const double* fs, int64_t ns, const double* f
 }
 
 // ------------------------------------------------------------------------------- a6 hypotheses
-__device__ __forceinline__ uint64_t fsplitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __global__ void feat_hyp_kernel(const double* __restrict__ src, const double* __restrict__ tgt,
                                 const int32_t* __restrict__ corr, int64_t nc, uint64_t seed,
                                 int64_t H, double edge, double dist, double* __restrict__ T_out,
                                 int32_t* __restrict__ pass) {
   const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (h >= H) return;
-  const uint64_t base = fsplitmix64(seed ^ ((uint64_t)h * 0x9E3779B97F4A7C15ull));
+  int64_t r[3];
+  trial_rows(seed, h, nc, r);  // sampler.h: WITH replacement
   double ps[3][3], qs[3][3];
-  for (int k = 0; k < 3; ++k) {  // WITH replacement, like Open3D's rand_gen() per row
-    const uint64_t v = fsplitmix64(base + (uint64_t)k);
-    const int64_t r = (int64_t)(((v >> 32) * (uint64_t)nc) >> 32);
-    const int64_t a = corr[2 * r], b = corr[2 * r + 1];
+  for (int k = 0; k < 3; ++k) {
+    const int64_t a = corr[2 * r[k]], b = corr[2 * r[k] + 1];
     for (int c = 0; c < 3; ++c) {
       ps[k][c] = src[3 * a + c];
       qs[k][c] = tgt[3 * b + c];

@@ -38,6 +38,7 @@
 
 #include "linalg.h"
 #include "m3d_internal.h"
+#include "sampler.h"
 
 namespace m3d {
 namespace {
@@ -65,26 +66,6 @@ struct LoopArgs {
   int32_t iters, decrease_mu;
   double maxcd, div;
 };
-
-__device__ __forceinline__ uint64_t fg_splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// feat.hip feat_hyp_kernel's rows: three draws WITH replacement
-__device__ __forceinline__ void trial_rows(uint64_t seed, int64_t h, int64_t n, int64_t r[3]) {
-  const uint64_t base = fg_splitmix64(seed ^ ((uint64_t)h * 0x9E3779B97F4A7C15ull));
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = (int64_t)(((fg_splitmix64(base + (uint64_t)k) >> 32) * (uint64_t)n) >> 32);
-}
-
-__device__ __forceinline__ double wave_tree(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
@@ -126,7 +107,7 @@ __global__ __launch_bounds__(kMultiBlock) void fgr_mean_partial_kernel(const dou
   }
 #pragma unroll
   for (int v = 0; v < 3; ++v) {
-    const double t = wave_tree(a[v]);
+    const double t = wave_sum(a[v]);
     if (lane == 0) part[seg * 3 + v] = t;
   }
 }
@@ -141,7 +122,7 @@ __global__ __launch_bounds__(kWave) void fgr_mean_final_kernel(const double* __r
   }
 #pragma unroll
   for (int v = 0; v < 3; ++v) {
-    const double t = wave_tree(a[v]);
+    const double t = wave_sum(a[v]);
     if (lane == 0) s->mean[which][v] = t / (double)n;
   }
 }
@@ -383,7 +364,7 @@ __global__ __launch_bounds__(kOneWgThreads) void fgr_loop_one_kernel(const doubl
         row_terms(P[k][0], P[k][1], P[k][2], Q[k][0], Q[k][1], Q[k][2], par, acc);
 #pragma unroll
     for (int v = 0; v < kNS; ++v) {
-      const double t = wave_tree(acc[v]);
+      const double t = wave_sum(acc[v]);
       if (lane == 0) part[itr & 1][wave][v] = t;
     }
     __syncthreads();
@@ -393,7 +374,7 @@ __global__ __launch_bounds__(kOneWgThreads) void fgr_loop_one_kernel(const doubl
     for (int v = 0; v < kNS; ++v) {
       double t = 0.0;
       if (lane < kOneWgWaves) t += part[itr & 1][lane][v];
-      S[v] = wave_tree(t);
+      S[v] = wave_sum(t);
     }
     if (sums_only) {
       if (threadIdx.x < kNS) {
@@ -453,7 +434,7 @@ __global__ __launch_bounds__(kMultiBlock) void fgr_loop_multi_kernel(const doubl
     }
 #pragma unroll
     for (int v = 0; v < kNS; ++v) {
-      const double t = wave_tree(acc[v]);
+      const double t = wave_sum(acc[v]);
       if (lane == 0) st_wt(part + seg * kNS + v, t);
     }
   }
@@ -473,7 +454,7 @@ __global__ __launch_bounds__(kMultiBlock) void fgr_loop_multi_kernel(const doubl
 #pragma unroll
     for (int v = 0; v < kNS; ++v) S[v] += ld_wt(part + g * kNS + v);
 #pragma unroll
-  for (int v = 0; v < kNS; ++v) S[v] = wave_tree(S[v]);
+  for (int v = 0; v < kNS; ++v) S[v] = wave_sum(S[v]);
   if (lane == 0) s->ticket = 0;
   if (sums_only) {
     if (lane == 0)
@@ -496,37 +477,57 @@ __global__ __launch_bounds__(kMultiBlock) void fgr_loop_multi_kernel(const doubl
   }
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 int64_t segs_of(int64_t n) { return (n + kFgrSegRows - 1) / kFgrSegRows; }
 
+// the pieces of a call's scratch, placed onto `scratch` (null: the layout's size alone)
 struct FgrScratch {
-  size_t state, mpart, pr, qr, flag, sel, nsel, accepted, p, q, lpart, tmp, tmp_bytes, total;
+  FgrState* state = nullptr;
+  double *mpart = nullptr, *pr = nullptr, *qr = nullptr;
+  uint8_t* flag = nullptr;
+  int64_t* sel = nullptr;
+  int32_t* nsel = nullptr;
+  int64_t* accepted = nullptr;
+  double *p = nullptr, *q = nullptr, *lpart = nullptr;
+  char* tmp = nullptr;
+  size_t tmp_bytes = 0, bytes = 0;
+  FgrScratch(int64_t ns, int64_t nt, int64_t nc, int64_t cap, void* scratch) {
+    size_t tb = 0;
+    hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int64_t>(0), (uint8_t*)nullptr,
+                                  (int64_t*)nullptr, (int32_t*)nullptr, kFgrTrialBatch, (hipStream_t)0);
+    tmp_bytes = std::max<size_t>(tb, 1);
+    const size_t rows = (size_t)std::max<int64_t>(std::max<int64_t>(3 * cap, nc), 1);
+    const size_t c1 = (size_t)std::max<int64_t>(nc, 1);
+    Carve cv;
+    cv.add(&state, 1);
+    cv.add(&mpart, 3 * (size_t)segs_of(std::max(ns, nt)));
+    cv.add(&pr, 3 * c1);
+    cv.add(&qr, 3 * c1);
+    cv.add(&flag, kFgrTrialBatch);
+    cv.add(&sel, kFgrTrialBatch);
+    cv.add(&nsel, 1);
+    cv.add(&accepted, (size_t)cap);
+    cv.add(&p, 3 * rows);
+    cv.add(&q, 3 * rows);
+    cv.add(&lpart, kNS * (size_t)segs_of((int64_t)rows));
+    cv.add(&tmp, tmp_bytes);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
 
-FgrScratch fgr_layout(int64_t ns, int64_t nt, int64_t nc, int64_t cap) {
-  FgrScratch L{};
-  size_t tb = 0;
-  hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int64_t>(0), (uint8_t*)nullptr,
-                                (int64_t*)nullptr, (int32_t*)nullptr, kFgrTrialBatch, (hipStream_t)0);
-  L.tmp_bytes = std::max<size_t>(tb, 1);
-  const size_t rows = (size_t)std::max<int64_t>(std::max<int64_t>(3 * cap, nc), 1);
-  const size_t c1 = (size_t)std::max<int64_t>(nc, 1);
-  size_t o = 0;
-  L.state = o, o += up256(sizeof(FgrState));
-  L.mpart = o, o += up256(sizeof(double) * 3 * (size_t)std::max<int64_t>(segs_of(std::max(ns, nt)), 1));
-  L.pr = o, o += up256(sizeof(double) * 3 * c1);
-  L.qr = o, o += up256(sizeof(double) * 3 * c1);
-  L.flag = o, o += up256(kFgrTrialBatch);
-  L.sel = o, o += up256(sizeof(int64_t) * kFgrTrialBatch);
-  L.nsel = o, o += up256(sizeof(int32_t));
-  L.accepted = o, o += up256(sizeof(int64_t) * (size_t)std::max<int64_t>(cap, 1));
-  L.p = o, o += up256(sizeof(double) * 3 * rows);
-  L.q = o, o += up256(sizeof(double) * 3 * rows);
-  L.lpart = o, o += up256(sizeof(double) * kNS * (size_t)segs_of((int64_t)rows));
-  L.tmp = o, o += up256(L.tmp_bytes);
-  L.total = o;
-  return L;
-}
+// fgr_terms' scratch: the state and one row of partials per segment of n rows
+struct FgrTermsScratch {
+  FgrState* state = nullptr;
+  double* part = nullptr;
+  size_t bytes = 0;
+  FgrTermsScratch(int64_t n, void* scratch) {
+    Carve cv;
+    cv.add(&state, 1);
+    cv.add(&part, kNS * (size_t)segs_of(n));
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
+};
 
 hipError_t read_state(const FgrState* s, FgrState* h, hipStream_t st) {
   hipError_t e = hipMemcpyAsync(h, s, sizeof(FgrState), hipMemcpyDeviceToHost, st);
@@ -541,24 +542,20 @@ int64_t fgr_tuple_cap(const m3d_fgr_params* p, int64_t nc) {
   return std::min<int64_t>(std::max<int64_t>(p->maximum_tuple_count, 1), std::max<int64_t>(100 * nc, 1));
 }
 
-size_t fgr_scratch_bytes(int64_t ns, int64_t nt, int64_t nc, int64_t cap) { return fgr_layout(ns, nt, nc, cap).total; }
+size_t fgr_scratch_bytes(int64_t ns, int64_t nt, int64_t nc, int64_t cap) {
+  return FgrScratch(ns, nt, nc, cap, nullptr).bytes;
+}
 
 hipError_t fgr_rows(m3d_ctx* ctx, const double* src, int64_t ns, const double* tgt, int64_t nt,
                     const int32_t* corr, int64_t nc, const m3d_fgr_params* p, m3d_fgr_result* out,
                     int32_t* rows_out, void* scratch, hipStream_t st, int* bad_row) {
   const int64_t cap = fgr_tuple_cap(p, nc);
-  const FgrScratch L = fgr_layout(ns, nt, nc, cap);
-  char* S = static_cast<char*>(scratch);
-  FgrState* s = reinterpret_cast<FgrState*>(S + L.state);
-  double* mpart = reinterpret_cast<double*>(S + L.mpart);
-  double* pr = reinterpret_cast<double*>(S + L.pr);
-  double* qr = reinterpret_cast<double*>(S + L.qr);
-  double* pp = reinterpret_cast<double*>(S + L.p);
-  double* qq = reinterpret_cast<double*>(S + L.q);
-  uint8_t* flag = reinterpret_cast<uint8_t*>(S + L.flag);
-  int64_t* sel = reinterpret_cast<int64_t*>(S + L.sel);
-  int32_t* nsel = reinterpret_cast<int32_t*>(S + L.nsel);
-  int64_t* accepted = reinterpret_cast<int64_t*>(S + L.accepted);
+  const FgrScratch L(ns, nt, nc, cap, scratch);
+  FgrState* s = L.state;
+  double *mpart = L.mpart, *pr = L.pr, *qr = L.qr, *pp = L.p, *qq = L.q;
+  uint8_t* flag = L.flag;
+  int64_t *sel = L.sel, *accepted = L.accepted;
+  int32_t* nsel = L.nsel;
   *bad_row = 0;
   hipError_t e;
   {  // step 2 (ns, nt ≥ 1)
@@ -597,7 +594,7 @@ hipError_t fgr_rows(m3d_ctx* ctx, const double* src, int64_t ns, const double* t
             pr, qr, nc, p->seed, h0, count, p->tuple_scale, flag, s);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         size_t tb = L.tmp_bytes;
-        e = hipcub::DeviceSelect::Flagged(S + L.tmp, tb, hipcub::CountingInputIterator<int64_t>(h0), flag, sel, nsel,
+        e = hipcub::DeviceSelect::Flagged(L.tmp, tb, hipcub::CountingInputIterator<int64_t>(h0), flag, sel, nsel,
                                           count, st);
         if (e != hipSuccess) return e;
         fgr_tuple_append_kernel<<<1, kMultiBlock, 0, st>>>(sel, nsel, cap, accepted, h0 + count, s);
@@ -656,15 +653,13 @@ hipError_t run_loop(m3d_ctx* ctx, const double* p, double* q, int64_t n, const L
 
 hipError_t fgr_optimise(m3d_ctx* ctx, int64_t ns, int64_t nt, int64_t nc, const m3d_fgr_params* p,
                         m3d_fgr_result* out, void* scratch, hipStream_t st) {
-  const FgrScratch L = fgr_layout(ns, nt, nc, fgr_tuple_cap(p, nc));
-  char* S = static_cast<char*>(scratch);
-  FgrState* s = reinterpret_cast<FgrState*>(S + L.state);
+  const FgrScratch L(ns, nt, nc, fgr_tuple_cap(p, nc), scratch);
+  FgrState* s = L.state;
   const int64_t n = out->n_rows;
   for (int k = 0; k < 16; ++k) out->T_norm[k] = (k % 5 == 0) ? 1.0 : 0.0;
   if (n < 10 || p->iteration_number <= 0) return hipSuccess;  // T = I, par = par₀
   const LoopArgs a{p->iteration_number, p->decrease_mu ? 1 : 0, p->maximum_correspondence_distance, p->division_factor};
-  hipError_t e = run_loop(ctx, reinterpret_cast<double*>(S + L.p), reinterpret_cast<double*>(S + L.q), n, a, p->path,
-                          reinterpret_cast<double*>(S + L.lpart), s, st);
+  hipError_t e = run_loop(ctx, L.p, L.q, n, a, p->path, L.lpart, s, st);
   if (e != hipSuccess) return e;
   FgrState hs;
   if ((e = read_state(s, &hs, st)) != hipSuccess) return e;
@@ -673,13 +668,13 @@ hipError_t fgr_optimise(m3d_ctx* ctx, int64_t ns, int64_t nt, int64_t nc, const 
   return hipSuccess;
 }
 
-size_t fgr_terms_scratch_bytes(int64_t n) { return up256(sizeof(FgrState)) + up256(sizeof(double) * kNS * (size_t)std::max<int64_t>(segs_of(n), 1)); }
+size_t fgr_terms_scratch_bytes(int64_t n) { return FgrTermsScratch(n, nullptr).bytes; }
 
 hipError_t fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, int path,
                      double sums27[27], void* scratch, hipStream_t st) {
-  char* S = static_cast<char*>(scratch);
-  FgrState* s = reinterpret_cast<FgrState*>(S);
-  double* part = reinterpret_cast<double*>(S + up256(sizeof(FgrState)));
+  const FgrTermsScratch L(n, scratch);
+  FgrState* s = L.state;
+  double* part = L.part;
   const LoopArgs a{1, 0, 0.0, 1.0};
   fgr_init_kernel<<<1, kMultiBlock, 0, st>>>(s);
   {

@@ -1,17 +1,16 @@
 // iss.hip — ISS keypoints on the device: Open3D 0.19 keypoint::ComputeISSKeypoints (the contract is
 // in include/m3d.h).
 //
-// S(i) = {j : d²(i, j) < rs²}, N(i) = {j : d²(i, j) < rn²} (strict, the point itself included),
-// d² = (dx·dx + dy·dy) + dz·dz in fp64 on the cloud's original coordinates (-ffp-contract=off),
-// decided behind the fp32 screen of clean.hip's radius count (prefilter_bound / box_half_width: a
-// candidate the screen drops is provably outside).
+// S(i) = {j : d²(i, j) < rs²}, N(i) = {j : d²(i, j) < rn²} (strict, the point itself included):
+// the fixed-radius scan of knn_wave.h (wave_scan_box; its contract and exactness argument are
+// stated there).
 //
 //   A. moments   ONE WAVE per point in the cell order of the grid of cell rs, lanes over the
 //                candidates of a cell row.  Each lane adds, for its candidates inside, d = pⱼ − pᵢ
-//                into nine fp64 sums (Σd, Σd dᵀ) and mix64(j) into a 64-bit integer sum; then a
+//                into nine fp64 sums (Σd, Σd dᵀ) and splitmix64(j) into a 64-bit integer sum; then a
 //                fixed xor butterfly.  The sums are centred on the query, so nothing cancels but
 //                the mean of the neighbourhood itself.  Written: the nine sums, the signature
-//                (count, Σ mix64(j) mod 2⁶⁴) and the count.
+//                (count, Σ splitmix64(j) mod 2⁶⁴) and the count.
 //   eigen        one THREAD per point: m = S1 / count, C = S2 / count − m mᵀ, Eigen's isZero, the
 //                eigenvalues (linalg.h sym3_eigenvalues), the two ratio tests → third[i].  Jacobi
 //                is a long chain of dependent fp64 operations; at the end of pass A it occupies a
@@ -33,6 +32,7 @@
 #include "m3d_internal.h"
 #include "knn_wave.h"
 #include "linalg.h"
+#include "sampler.h"
 
 namespace m3d {
 namespace {
@@ -40,53 +40,6 @@ namespace {
 constexpr int kIssBlock = 256;
 constexpr int kIssWaves = kIssBlock / kWave;
 constexpr int kTallySalient = 0, kTallyCounted = 1, kTallyWords = 2;
-
-// splitmix64's finaliser: the per-index term of a set's signature
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-// The box scan of both passes: for every 64-candidate chunk of the query's cell rows, pre(t) in
-// the lanes whose candidate t passes the fp32 screen — before the exact test reads the candidate's
-// coordinates — then, in every lane, f(in, t, dx, dy, dz) with d = p_t − q and `in` the exact test
-// d² < r².  f returns true (wave-uniform) to leave the box.
-template <class Pre, class F>
-__device__ __forceinline__ void iss_scan(const double* __restrict__ xyz64, const double* q, float4 qf,
-                                         const GridDev& g, float Rf, double r2, float bf, int lane, Pre&& pre,
-                                         F&& f) {
-  const int x0 = grid_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
-  const int x1 = grid_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
-  const int y0 = grid_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
-  const int y1 = grid_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
-  const int z0 = grid_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
-  const int z1 = grid_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
-  for (int cz = z0; cz <= z1; ++cz)
-    for (int cy = y0; cy <= y1; ++cy) {
-      const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
-      const int32_t j0 = g.start[row + x0], j1 = g.start[row + x1 + 1];
-      for (int32_t jb = j0; jb < j1; jb += 64) {
-        const int32_t j = jb + lane;
-        bool in = false;
-        int32_t t = 0;
-        double dx = 0.0, dy = 0.0, dz = 0.0;
-        if (j < j1) {
-          const float4 tp = g.pts[j];
-          t = __float_as_int(tp.w);
-          const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
-          if ((fx * fx + fy * fy) + fz * fz <= bf) {
-            pre(t);
-            const double* p = xyz64 + 3 * (int64_t)t;
-            dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-            in = (dx * dx + dy * dy) + dz * dz < r2;  // knn_wave.h d2_exact's expression
-          }
-        }
-        if (f(in, t, dx, dy, dz)) return;
-      }
-    }
-}
 
 // pass A.  sums: n × 9 doubles (Σdx Σdy Σdz, Σdx² Σdxdy Σdxdz Σdy² Σdydz Σdz²)
 __global__ __launch_bounds__(kIssBlock) void moments_kernel(const double* __restrict__ xyz64,
@@ -102,14 +55,14 @@ __global__ __launch_bounds__(kIssBlock) void moments_kernel(const double* __rest
   double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
   uint64_t h = 0;
   int32_t total = 0;
-  iss_scan(
+  wave_scan_box(
       xyz64, q, xyz32[i], g, Rf, r2, bf, lane, [](int32_t) {},
       [&](bool in, int32_t t, double dx, double dy, double dz) {
         if (in) {
           sx += dx, sy += dy, sz += dz;
           sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
           syy += dy * dy, syz += dy * dz, szz += dz * dz;
-          h += mix64((uint64_t)(uint32_t)t);
+          h += splitmix64((uint64_t)(uint32_t)t);  // sampler.h: the per-index term of a set's signature
         }
         total += (int32_t)__popcll(__ballot(in));
         return false;
@@ -193,7 +146,7 @@ __global__ __launch_bounds__(kIssBlock) void nonmax_kernel(const double* __restr
   bool beaten = false;  // wave-uniform
   double tt = 0.0;
   bool other = false;
-  iss_scan(
+  wave_scan_box(
       xyz64, q, xyz32[i], g, Rf, r2, bf, lane,
       [&](int32_t t) {
         tt = third[t];
@@ -207,27 +160,31 @@ __global__ __launch_bounds__(kIssBlock) void nonmax_kernel(const double* __restr
   if (lane == 0) keep[i] = (!beaten && total >= min_neighbors) ? 1 : 0;
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// the pieces of a call's scratch for n points, placed onto `scratch` (null: the layout's size alone)
 struct IssScratch {
-  size_t sums, sig, third, count, keep, tally, total;
+  double* sums = nullptr;
+  uint64_t* sig = nullptr;
+  double* third = nullptr;
+  int32_t* count = nullptr;
+  uint8_t* keep = nullptr;
+  int32_t* tally = nullptr;
+  size_t bytes = 0;
+  IssScratch(int64_t n, void* scratch) {
+    Carve cv;
+    cv.add(&sums, 9 * (size_t)n);
+    cv.add(&sig, (size_t)n);
+    cv.add(&third, (size_t)n);
+    cv.add(&count, (size_t)n);
+    cv.add(&keep, (size_t)n);
+    cv.add(&tally, kTallyWords);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
-IssScratch iss_layout(int64_t n) {
-  IssScratch L{};
-  size_t o = 0;
-  L.sums = o, o += up256(sizeof(double) * 9 * (size_t)n);
-  L.sig = o, o += up256(sizeof(uint64_t) * (size_t)n);
-  L.third = o, o += up256(sizeof(double) * (size_t)n);
-  L.count = o, o += up256(sizeof(int32_t) * (size_t)n);
-  L.keep = o, o += up256((size_t)n);
-  L.tally = o, o += up256(sizeof(int32_t) * kTallyWords);
-  L.total = o;
-  return L;
-}
 
 }  // namespace
 
-size_t iss_scratch_bytes(int64_t n) { return n > 0 ? iss_layout(n).total : 0; }
+size_t iss_scratch_bytes(int64_t n) { return n > 0 ? IssScratch(n, nullptr).bytes : 0; }
 
 // Profiling (m3d_profile_*): pass A under M3D_KERNEL_SCORE, the eigen launch under M3D_KERNEL_LOOP,
 // pass B under M3D_KERNEL_NN, the compaction under M3D_KERNEL_KABSCH.
@@ -236,23 +193,20 @@ hipError_t iss_keypoints(m3d_ctx* ctx, const m3d_cloud* c, const Grid* gs, const
                          double* third_out, int32_t* count_out, int64_t tally_out[3], void* scratch,
                          void* clean_scratch, hipStream_t st) {
   const int64_t n = c->n;
-  char* S = static_cast<char*>(scratch);
-  const IssScratch L = iss_layout(n);
-  double* sums = reinterpret_cast<double*>(S + L.sums);
-  uint64_t* sig = reinterpret_cast<uint64_t*>(S + L.sig);
-  double* third = third_out != nullptr ? third_out : reinterpret_cast<double*>(S + L.third);
-  int32_t* count = count_out != nullptr ? count_out : reinterpret_cast<int32_t*>(S + L.count);
-  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
-  int32_t* tally = reinterpret_cast<int32_t*>(S + L.tally);
-  const double eabs = pair_eabs(c);
+  const IssScratch L(n, scratch);
+  double* sums = L.sums;
+  uint64_t* sig = L.sig;
+  double* third = third_out != nullptr ? third_out : L.third;
+  int32_t* count = count_out != nullptr ? count_out : L.count;
+  uint8_t* keep = L.keep;
+  int32_t* tally = L.tally;
   const unsigned per_thread = (unsigned)((n + kIssBlock - 1) / kIssBlock);
   const unsigned per_wave = (unsigned)((n + kIssWaves - 1) / kIssWaves);
   hipError_t e = hipSuccess;
   {
     KTimer t(ctx, M3D_KERNEL_SCORE, st);
-    const double r2 = rs * rs;
-    moments_kernel<<<per_wave, kIssBlock, 0, st>>>(c->xyz64, c->xyz32, n, gs->dev, box_half_width(c, rs), r2,
-                                                   prefilter_bound(r2, eabs), sums, sig, count);
+    const RadiusScreen s = radius_screen(c, rs);
+    moments_kernel<<<per_wave, kIssBlock, 0, st>>>(c->xyz64, c->xyz32, n, gs->dev, s.Rf, s.r2, s.bf, sums, sig, count);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   {
@@ -263,9 +217,9 @@ hipError_t iss_keypoints(m3d_ctx* ctx, const m3d_cloud* c, const Grid* gs, const
   }
   {
     KTimer t(ctx, M3D_KERNEL_NN, st);
-    const double r2 = rn * rn;
-    nonmax_kernel<<<per_wave, kIssBlock, 0, st>>>(c->xyz64, c->xyz32, n, gn->dev, box_half_width(c, rn), r2,
-                                                  prefilter_bound(r2, eabs), third, sig, count, min_neighbors, keep);
+    const RadiusScreen s = radius_screen(c, rn);
+    nonmax_kernel<<<per_wave, kIssBlock, 0, st>>>(c->xyz64, c->xyz32, n, gn->dev, s.Rf, s.r2, s.bf, third, sig, count,
+                                                  min_neighbors, keep);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   int32_t h[kTallyWords] = {0};

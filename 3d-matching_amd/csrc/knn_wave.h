@@ -1,14 +1,20 @@
-// knn_wave.h — the wave-held k-nearest list and the cell-box scan that fills it, shared by the
-// hybrid search (prep.hip hybrid_search_wave_kernel) and the k-NN ladder (clean.hip
-// knn_level_kernel).  This is the one place where the list and its exactness argument live.
+// knn_wave.h — the wave-per-point neighbourhood scans: ONE WAVE walks the cell box of a query, lanes
+// over the candidates of a cell row.  The walk (wave_box_chunks) and the two scans on top of it:
+//   wave_scan_box      the fixed-radius scan: every point with d² < r² (cluster.hip link / label,
+//                      iss.hip moments / non-max; clean.hip radius_count_kernel keeps the same
+//                      scan written out, for its speed);
+//   wave_knn_scan_box  the kk nearest of those in a wave-held sorted list (prep.hip
+//                      hybrid_search_wave_kernel, clean.hip knn_level_kernel).
+// This is the one place where the walk, the list and their exactness argument live.
 //
-// Contract: for a query q, the kk smallest (d², index) keys, in ascending order, over the points
-// with d² < r², d² = (dx·dx + dy·dy) + dz·dz in fp64 on the cloud's original coordinates
-// (-ffp-contract=off), ties by index — the oracle's list bit for bit.  The centred fp32 grid
-// points only screen candidates (prefilter_bound) and size the cell box (box_half_width): a
-// candidate the screen passes is decided by its exact d², one it drops is provably outside the
-// current threshold.  The box is cut out of the grid with grid_coord (nnkey.h), the expression
-// that placed the points, so the covering argument holds by construction.
+// Contract of both scans: membership is d² < r² (strict, the query itself included), d² =
+// (dx·dx + dy·dy) + dz·dz with d = p_t − q in fp64 on the cloud's original coordinates
+// (-ffp-contract=off) — the oracles' test bit for bit.  The centred fp32 grid points only screen
+// candidates (prefilter_bound) and size the cell box (box_half_width): a candidate the screen
+// passes is decided by its exact d², one it drops is provably outside the current threshold (r²,
+// or the list's kk-th entry).  The box is cut out of the grid with grid_coord (nnkey.h), the
+// expression that placed the points, so the covering argument holds by construction.
+// The list adds: the kk smallest (d², index) keys in ascending order, ties by index.
 #pragma once
 
 #include <float.h>
@@ -49,8 +55,9 @@ __device__ __forceinline__ bool key_less(double d, int32_t t, double D, int32_t 
 // bound on |fp32 distance − fp64 distance| of two centred points (pair_eabs), any point whose
 // fp64 d² ≤ thr has a directly computed fp32 d² (three roundings of relative u each, covered by
 // the 4e-6 factors) ≤ this bound — so a candidate above it can be skipped without its fp64 gather.
-// Host and device give the same float (the conversion rounds up on both): radius_outliers forms
-// its one bound on the host, the list kernels follow their threshold on the device.
+// Host and device give the same float (the conversion rounds up on both): the fixed-radius scans
+// take their one bound from the host (radius_screen), the list kernels follow their threshold on
+// the device.
 __host__ __device__ __forceinline__ float prefilter_bound(double thr, double e) {
   const double b = (sqrt(thr) + e) * (1.0 + 4e-6);
   const double b2 = b * b * (1.0 + 4e-6);
@@ -61,6 +68,18 @@ __host__ __device__ __forceinline__ float prefilter_bound(double thr, double e) 
   if ((double)f < b2) f = std::nextafter(f, INFINITY);
 #endif
   return std::isfinite(f) ? f : FLT_MAX;
+}
+
+// what a fixed-radius scan (wave_scan_box) of cloud c takes: the box half-width, the exact r² and
+// the fp32 screen bound of r², formed once on the host (the threshold never moves)
+struct RadiusScreen {
+  float Rf;
+  double r2;
+  float bf;
+};
+inline RadiusScreen radius_screen(const m3d_cloud* c, double radius) {
+  const double r2 = radius * radius;
+  return {box_half_width(c, radius), r2, prefilter_bound(r2, pair_eabs(c))};
 }
 
 // lane l ← lane l − 1 across the whole wave (gfx9 DPP wave_shr:1; lane 0 keeps `old`): a VALU
@@ -217,62 +236,103 @@ struct WaveKnnList {
   }
 };
 
-// The cell box of half-width Rf around the fp32 query qf scanned into the list by one wave: of
-// every cell row the 64-point chunks chunk0, chunk0 + stride, … (point offsets; 0 and 64: all of
-// them), read coalesced (the rows are contiguous in the sorted grid), screened in fp32 against
-// prefilter_bound of the current threshold, the survivors' exact fp64 d² evaluated and the
-// qualifying ones merged (kS == 1, three or more) or inserted one by one.  The fp32 screen bound
-// follows the kk-th entry once per chunk: the entries of a chunk are tested against the exact
-// thr, bf only screens the next chunk.  lds_*_row: 64 entries owned by this wave (kS == 1 only).
-// Every loop is bounded by the grid's dimensions, a cell row's length or the 64 bits of a ballot.
-template <int kS>
-__device__ __forceinline__ void wave_knn_scan_box(WaveKnnList<kS>& L, const double* __restrict__ xyz64,
-                                                  const double* q, const float4 qf, const GridDev& g, float Rf,
-                                                  double r2, double eabs, int kk, int chunk0, int stride,
-                                                  double* lds_d_row, int32_t* lds_t_row) {
-  const int lane = threadIdx.x & 63;
+// ------------------------------------------------------------------------------- the walk
+// The cell box of half-width Rf around the fp32 query qf, walked by one wave: of every cell row
+// [j0, j1) of the sorted grid (the rows are contiguous, so a chunk is read coalesced) the
+// 64-candidate chunks starting at jb = j0 + chunk0, + stride, … (point offsets; 0 and 64: all of
+// them): body(jb, j1).  body returns true (wave-uniform) to leave the box.  Every loop is bounded
+// by the grid's dimensions or a cell row's length.
+template <class Body>
+__device__ __forceinline__ void wave_box_chunks(const float4 qf, const GridDev& g, float Rf, int chunk0,
+                                                int stride, Body&& body) {
   const int x0 = grid_coord(qf.x - Rf, g.o[0], g.inv_h, g.n[0]);
   const int x1 = grid_coord(qf.x + Rf, g.o[0], g.inv_h, g.n[0]);
   const int y0 = grid_coord(qf.y - Rf, g.o[1], g.inv_h, g.n[1]);
   const int y1 = grid_coord(qf.y + Rf, g.o[1], g.inv_h, g.n[1]);
   const int z0 = grid_coord(qf.z - Rf, g.o[2], g.inv_h, g.n[2]);
   const int z1 = grid_coord(qf.z + Rf, g.o[2], g.inv_h, g.n[2]);
-  for (int cz = z0; cz <= z1; ++cz)
-    for (int cy = y0; cy <= y1; ++cy) {
+  bool stop = false;  // wave-uniform
+  for (int cz = z0; cz <= z1 && !stop; ++cz)
+    for (int cy = y0; cy <= y1 && !stop; ++cy) {
       const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
       const int32_t j0 = g.start[row + x0], j1 = g.start[row + x1 + 1];
-      for (int32_t jb = j0 + chunk0; jb < j1; jb += stride) {
-        const int32_t j = jb + lane;
-        bool cand = false;
-        double d = 0.0;
-        int32_t t = -1;
-        if (j < j1) {
-          const float4 tp = g.pts[j];
-          const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
-          if ((fx * fx + fy * fy) + fz * fz <= L.bf) {
-            t = __float_as_int(tp.w);
-            d = d2_exact(xyz64 + 3 * (int64_t)t, q);
-            cand = d < r2 && L.accepts(d, t, kk);
-          }
-        }
-        uint64_t m = __ballot(cand);
-        if constexpr (kS == 1) {
-          if (__popcll(m) >= 3) {
-            L.merge_chunk(m, cand, d, t, kk, lds_d_row, lds_t_row);
-            m = 0;
-          }
-        }
-        while (m != 0) {
-          const int src = __builtin_ctzll(m);
-          m &= m - 1;
-          const double x = readlane_f64(d, src);
-          const int32_t xt = __builtin_amdgcn_readlane(t, src);
-          if (!L.accepts(x, xt, kk)) continue;  // the threshold moved
-          L.insert(x, xt, kk);
-        }
-        if (L.cnt == kk) L.bf = prefilter_bound(L.thr, eabs);
+      for (int32_t jb = j0 + chunk0; jb < j1 && !stop; jb += stride) stop = body(jb, j1);
+    }
+}
+
+// The fixed-radius scan: for every chunk of the box, pre(t) in the lanes whose candidate t passes
+// the fp32 screen bf — BEFORE the exact test reads the candidate's coordinates, so what pre loads is
+// in flight beside them — then, in every lane, f(in, t, dx, dy, dz) with d = p_t − q and `in` the
+// exact test d² < r² (false in a lane without a candidate or behind the screen).  f returns true
+// (wave-uniform) to leave the box.
+template <class Pre, class F>
+__device__ __forceinline__ void wave_scan_box(const double* __restrict__ xyz64, const double* q, const float4 qf,
+                                              const GridDev& g, float Rf, double r2, float bf, int lane,
+                                              Pre&& pre, F&& f) {
+  wave_box_chunks(qf, g, Rf, 0, 64, [&](int32_t jb, int32_t j1) {
+    const int32_t j = jb + lane;
+    bool in = false;
+    int32_t t = 0;
+    double dx = 0.0, dy = 0.0, dz = 0.0;
+    if (j < j1) {
+      const float4 tp = g.pts[j];
+      t = __float_as_int(tp.w);
+      const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
+      if ((fx * fx + fy * fy) + fz * fz <= bf) {
+        pre(t);
+        const double* p = xyz64 + 3 * (int64_t)t;
+        dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+        in = (dx * dx + dy * dy) + dz * dz < r2;  // d2_exact's expression
       }
     }
+    return f(in, t, dx, dy, dz);
+  });
+}
+
+// The box scanned into the list: the candidates of a chunk are screened in fp32 against
+// prefilter_bound of the current threshold, the survivors' exact fp64 d² evaluated and the
+// qualifying ones merged (kS == 1, three or more) or inserted one by one.  The fp32 screen bound
+// follows the kk-th entry once per chunk: the entries of a chunk are tested against the exact
+// thr, bf only screens the next chunk.  lds_*_row: 64 entries owned by this wave (kS == 1 only).
+// The inner loops are bounded by the 64 bits of a ballot.
+template <int kS>
+__device__ __forceinline__ void wave_knn_scan_box(WaveKnnList<kS>& L, const double* __restrict__ xyz64,
+                                                  const double* q, const float4 qf, const GridDev& g, float Rf,
+                                                  double r2, double eabs, int kk, int chunk0, int stride,
+                                                  double* lds_d_row, int32_t* lds_t_row) {
+  const int lane = threadIdx.x & 63;
+  wave_box_chunks(qf, g, Rf, chunk0, stride, [&](int32_t jb, int32_t j1) {
+    const int32_t j = jb + lane;
+    bool cand = false;
+    double d = 0.0;
+    int32_t t = -1;
+    if (j < j1) {
+      const float4 tp = g.pts[j];
+      const float fx = qf.x - tp.x, fy = qf.y - tp.y, fz = qf.z - tp.z;
+      if ((fx * fx + fy * fy) + fz * fz <= L.bf) {
+        t = __float_as_int(tp.w);
+        d = d2_exact(xyz64 + 3 * (int64_t)t, q);
+        cand = d < r2 && L.accepts(d, t, kk);
+      }
+    }
+    uint64_t m = __ballot(cand);
+    if constexpr (kS == 1) {
+      if (__popcll(m) >= 3) {
+        L.merge_chunk(m, cand, d, t, kk, lds_d_row, lds_t_row);
+        m = 0;
+      }
+    }
+    while (m != 0) {
+      const int src = __builtin_ctzll(m);
+      m &= m - 1;
+      const double x = readlane_f64(d, src);
+      const int32_t xt = __builtin_amdgcn_readlane(t, src);
+      if (!L.accepts(x, xt, kk)) continue;  // the threshold moved
+      L.insert(x, xt, kk);
+    }
+    if (L.cnt == kk) L.bf = prefilter_bound(L.thr, eabs);
+    return false;  // the whole box, always
+  });
 }
 
 }  // namespace m3d

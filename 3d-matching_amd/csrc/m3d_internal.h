@@ -24,6 +24,15 @@ namespace m3d {
 
 constexpr int kWave = 64;
 
+// the sum of a wave's 64 values in every lane: an xor butterfly, offsets 32, 16, …, 1 (the fixed
+// order every fixed-order reduction outside the ICP loop relies on; nnkey.h wave_sum_dpp is the
+// same tree by DPP for the ICP kernels)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // fp32 hypothesis block for the scoring screen (64 B = one s_load_dwordx16).
 // r: rotation row-major, t: translation in the centred frames (T p + t - q evaluated as
 // R p_c + t' - q_c with p_c = p - c_src, q_c = q - c_tgt), lo/hi: guard band around thr².

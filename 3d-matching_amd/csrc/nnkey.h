@@ -429,7 +429,7 @@ __device__ __forceinline__ SlotWinner slot_winner(int64_t i0, const double* __re
 // values v of slot blockIdx.x·kBlock + t; each wave adds its 64 lanes in an xor butterfly (32,
 // 16, …, 1: every lane ends with the same sum), then the wave sums are added in wave order into
 // partials[blockIdx.x·kSlots + k].  Columns kUsed .. kSlots are written as 0.0.
-__device__ __forceinline__ double wave_sum(double v) {
+__device__ __forceinline__ double wave_sum_dpp(double v) {
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) v += xor_lane_f64(v, o);
   return v;
@@ -440,7 +440,7 @@ __device__ __forceinline__ void block_partial(const double (&v)[kUsed], double* 
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
 #pragma unroll
   for (int k = 0; k < kUsed; ++k) {
-    const double t = wave_sum(v[k]);
+    const double t = wave_sum_dpp(v[k]);
     if (lane == 0) red[w][k] = t;
   }
   __syncthreads();

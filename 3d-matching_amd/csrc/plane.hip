@@ -32,6 +32,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "m3d_internal.h"
+#include "sampler.h"
 
 namespace m3d {
 namespace {
@@ -52,27 +53,6 @@ struct PlaneState {
   int64_t best_count, best_index, evaluated, iterations;
   int32_t done, bad;
 };
-
-__device__ __forceinline__ uint64_t pl_splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// ransac.hip native_triple for m distinct indices of [0, n); n >= m
-__device__ void native_sample(uint64_t seed, int64_t h, int64_t n, int m, int32_t* out) {
-  const uint64_t base = pl_splitmix64(seed ^ ((uint64_t)h * 0x9E3779B97F4A7C15ull));
-  int got = 0;
-  for (uint64_t k = 0; got < m && k < (1u << 20); ++k) {
-    const uint64_t v = pl_splitmix64(base + k);
-    const int32_t idx = (int32_t)(((v >> 32) * (uint64_t)n) >> 32);
-    bool dup = false;
-    for (int j = 0; j < got; ++j) dup |= (out[j] == idx);
-    if (!dup) out[got++] = idx;
-  }
-  for (; got < m; ++got) out[got] = got;  // unreachable for n >= m
-}
 
 // GetPlaneFromPoints' tail: centroid c, q = Σ (xx, xy, xz, yy, yz, zz) of r = p − c
 __device__ void plane_from_moments(const double c[3], const double q[6], double pl[4]) {
@@ -362,12 +342,6 @@ __global__ __launch_bounds__(kPlaneBlock) void plane_flag_kernel(const double* _
   keep[i] = dist < thr ? 1 : 0;
 }
 
-__device__ __forceinline__ double pl_wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // refit pass 0: Σ p over the inliers; pass 1: Σ of the six products of r = p − centroid.
 // partials: [block][6] (pass 0 uses three).
 __global__ __launch_bounds__(kPlaneBlock) void plane_refit_partial_kernel(const double* __restrict__ xyz64,
@@ -390,7 +364,7 @@ __global__ __launch_bounds__(kPlaneBlock) void plane_refit_partial_kernel(const 
   }
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
-    const double t = pl_wave_sum(v[q]);
+    const double t = wave_sum(v[q]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = t;
   }
   __syncthreads();
@@ -427,31 +401,32 @@ __global__ __launch_bounds__(kPlaneBlock) void plane_refit_final_kernel(const do
   }
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 int64_t chunks_of(int64_t n) { return (n + kPlaneChunk - 1) / kPlaneChunk; }
 
+// the per-(chunk, plane) partials of a batch of hb planes over n points, placed onto `scratch`
+// (null: the layout's size alone)
 struct ScoreScratch {
-  size_t pcnt, perr, total;
+  double* perr = nullptr;
+  int32_t* pcnt = nullptr;
+  size_t bytes = 0;
+  ScoreScratch(int64_t n, int64_t hb, void* scratch) {
+    const size_t cells = (size_t)chunks_of(n) * (size_t)std::max<int64_t>(hb, 1);
+    Carve cv;
+    cv.add(&perr, cells);
+    cv.add(&pcnt, cells);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
-ScoreScratch score_layout(int64_t n, int64_t hb) {
-  ScoreScratch L{};
-  const size_t cells = (size_t)chunks_of(n) * (size_t)std::max<int64_t>(hb, 1);
-  size_t o = 0;
-  L.perr = o, o += up256(sizeof(double) * cells);
-  L.pcnt = o, o += up256(sizeof(int32_t) * cells);
-  L.total = o;
-  return L;
-}
 
 // score + reduce of H <= plane_batch_cap(n) planes; n >= 1, H >= 1
 // (profiling: the score kernel under M3D_KERNEL_SCORE, the reduce under M3D_KERNEL_LOOP)
 hipError_t score_batch(m3d_ctx* ctx, const double* xyz64, int64_t n, const double* planes, int H, double thr,
-                       int32_t* counts, double* err, char* S, const ScoreScratch& L, const int32_t* done,
-                       hipStream_t st) {
+                       int32_t* counts, double* err, const ScoreScratch& L, const int32_t* done, hipStream_t st) {
   const int nchunks = (int)chunks_of(n);
   const int ngroups = (H + 63) / 64;
-  int32_t* pcnt = reinterpret_cast<int32_t*>(S + L.pcnt);
-  double* perr = reinterpret_cast<double*>(S + L.perr);
+  int32_t* pcnt = L.pcnt;
+  double* perr = L.perr;
   const int64_t waves = (int64_t)nchunks * ngroups;
   const unsigned blocks = (unsigned)((waves + kPlaneBlock / kWave - 1) / (kPlaneBlock / kWave));
   {
@@ -464,33 +439,39 @@ hipError_t score_batch(m3d_ctx* ctx, const double* xyz64, int64_t n, const doubl
   return hipGetLastError();
 }
 
+// the pieces of a segment_plane call's scratch, placed onto `scratch` (null: the layout's size alone)
 struct SegScratch {
-  size_t state, planes, zflag, bcnt, berr, score, keep, nsel, partials, tmp, tmp_bytes, total;
-  ScoreScratch sc;
+  PlaneState* state = nullptr;
+  double* planes = nullptr;
+  int32_t *zflag = nullptr, *bcnt = nullptr;
+  double* berr = nullptr;
+  char* score = nullptr;  // a ScoreScratch of `batch` planes
+  uint8_t* keep = nullptr;
+  int32_t* nsel = nullptr;
+  double* partials = nullptr;
+  char* tmp = nullptr;
+  size_t tmp_bytes = 0, bytes = 0;
+  SegScratch(int64_t n, int batch, void* scratch) {
+    size_t tb = 0;
+    hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int32_t>(0), (uint8_t*)nullptr,
+                                  (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
+    tmp_bytes = std::max<size_t>(tb, 1);
+    const size_t B = (size_t)std::max(batch, 1);
+    Carve cv;
+    cv.add(&state, 1);
+    cv.add(&planes, 4 * B);
+    cv.add(&zflag, B);
+    cv.add(&bcnt, B);
+    cv.add(&berr, B);
+    cv.add(&score, ScoreScratch(n, batch, nullptr).bytes);
+    cv.add(&keep, (size_t)n);
+    cv.add(&nsel, 1);
+    cv.add(&partials, 6 * (size_t)((n + kPlaneBlock - 1) / kPlaneBlock));
+    cv.add(&tmp, tmp_bytes);
+    bytes = cv.bytes();
+    if (scratch != nullptr) cv.place(scratch);
+  }
 };
-SegScratch seg_layout(int64_t n, int batch) {
-  SegScratch L{};
-  size_t tb = 0;
-  hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<int32_t>(0), (uint8_t*)nullptr,
-                                (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
-  L.tmp_bytes = std::max<size_t>(tb, 1);
-  L.sc = score_layout(n, batch);
-  const size_t nb = (size_t)((n + kPlaneBlock - 1) / kPlaneBlock);
-  const size_t B = (size_t)std::max(batch, 1);
-  size_t o = 0;
-  L.state = o, o += up256(sizeof(PlaneState));
-  L.planes = o, o += up256(sizeof(double) * 4 * B);
-  L.zflag = o, o += up256(sizeof(int32_t) * B);
-  L.bcnt = o, o += up256(sizeof(int32_t) * B);
-  L.berr = o, o += up256(sizeof(double) * B);
-  L.score = o, o += up256(L.sc.total);
-  L.keep = o, o += up256((size_t)n);
-  L.nsel = o, o += up256(sizeof(int32_t));
-  L.partials = o, o += up256(sizeof(double) * 6 * std::max<size_t>(nb, 1));
-  L.tmp = o, o += up256(L.tmp_bytes);
-  L.total = o;
-  return L;
-}
 
 }  // namespace
 
@@ -500,7 +481,7 @@ int64_t plane_batch_cap(int64_t n) {
 }
 
 size_t plane_score_scratch_bytes(int64_t n, int64_t H) {
-  return n > 0 && H > 0 ? score_layout(n, std::min(H, plane_batch_cap(n))).total : 0;
+  return n > 0 && H > 0 ? ScoreScratch(n, std::min(H, plane_batch_cap(n)), nullptr).bytes : 0;
 }
 
 hipError_t plane_score(const m3d_cloud* c, const double* planes, int64_t H, double thr, int32_t* counts,
@@ -508,11 +489,11 @@ hipError_t plane_score(const m3d_cloud* c, const double* planes, int64_t H, doub
   const int64_t n = c->n;
   if (n <= 0 || H <= 0) return hipSuccess;  // nothing is launched: no array is touched
   const int64_t cap = plane_batch_cap(n);
-  const ScoreScratch L = score_layout(n, std::min(H, cap));
+  const ScoreScratch L(n, std::min(H, cap), scratch);
   for (int64_t h0 = 0; h0 < H; h0 += cap) {
     const int hb = (int)std::min(cap, H - h0);
     const hipError_t e = score_batch(c->ctx, c->xyz64, n, planes + 4 * h0, hb, thr, counts + h0,
-                                     err != nullptr ? err + h0 : nullptr, static_cast<char*>(scratch), L, nullptr, st);
+                                     err != nullptr ? err + h0 : nullptr, L, nullptr, st);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -530,7 +511,7 @@ int segment_plane_batch(int64_t n, const m3d_plane_params* p) {
   return (int)std::min<int64_t>(b, plane_batch_cap(n));
 }
 
-size_t segment_plane_scratch_bytes(int64_t n, int batch) { return seg_layout(n, batch).total; }
+size_t segment_plane_scratch_bytes(int64_t n, int batch) { return SegScratch(n, batch, nullptr).bytes; }
 
 hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batch, const int32_t* samples,
                          m3d_plane_result* out, int32_t* inliers_out, int32_t* counts_out, double* err_out,
@@ -539,16 +520,12 @@ hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batc
   const int64_t H = p->num_iterations;
   const int rn = p->ransac_n;
   const double thr = p->distance_threshold;
-  char* S = static_cast<char*>(scratch);
-  const SegScratch L = seg_layout(n, batch);
-  PlaneState* s = reinterpret_cast<PlaneState*>(S + L.state);
-  double* planes = reinterpret_cast<double*>(S + L.planes);
-  int32_t* zflag = reinterpret_cast<int32_t*>(S + L.zflag);
-  int32_t* bcnt = reinterpret_cast<int32_t*>(S + L.bcnt);
-  double* berr = reinterpret_cast<double*>(S + L.berr);
-  uint8_t* keep = reinterpret_cast<uint8_t*>(S + L.keep);
-  int32_t* nsel = reinterpret_cast<int32_t*>(S + L.nsel);
-  double* partials = reinterpret_cast<double*>(S + L.partials);
+  const SegScratch L(n, batch, scratch);
+  const ScoreScratch Lsc(n, batch, L.score);
+  PlaneState* s = L.state;
+  double *planes = L.planes, *berr = L.berr, *partials = L.partials;
+  int32_t *zflag = L.zflag, *bcnt = L.bcnt, *nsel = L.nsel;
+  uint8_t* keep = L.keep;
   m3d_ctx* ctx = c->ctx;
   *bad_sample = 0;
   hipError_t e;
@@ -574,7 +551,7 @@ hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batc
         plane_fit_kernel<<<(unsigned)((hb + kPlaneBlock - 1) / kPlaneBlock), kPlaneBlock, 0, st>>>(
             c->xyz64, n, samples, p->seed, h0, hb, rn, planes, zflag, s);
       }
-      if ((e = score_batch(ctx, c->xyz64, n, planes, hb, thr, bcnt, berr, S + L.score, L.sc, &s->done, st)) != hipSuccess)
+      if ((e = score_batch(ctx, c->xyz64, n, planes, hb, thr, bcnt, berr, Lsc, &s->done, st)) != hipSuccess)
         return e;
       {
         KTimer t(ctx, M3D_KERNEL_LOOP, st);
@@ -597,7 +574,7 @@ hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batc
     plane_flag_kernel<<<(unsigned)((n + kPlaneBlock - 1) / kPlaneBlock), kPlaneBlock, 0, st>>>(c->xyz64, n, s, thr, keep);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t tb = L.tmp_bytes;
-    e = hipcub::DeviceSelect::Flagged(S + L.tmp, tb, hipcub::CountingInputIterator<int32_t>(0), keep, inliers_out,
+    e = hipcub::DeviceSelect::Flagged(L.tmp, tb, hipcub::CountingInputIterator<int32_t>(0), keep, inliers_out,
                                       nsel, (int)n, st);
     if (e != hipSuccess) return e;
   }

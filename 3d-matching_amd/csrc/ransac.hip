@@ -27,6 +27,7 @@
 #include "lds_dma.h"
 #include "linalg.h"
 #include "m3d_internal.h"
+#include "sampler.h"
 
 namespace m3d {
 
@@ -205,28 +206,6 @@ __global__ __launch_bounds__(256) void cloud_summary_kernel(const float* __restr
   if (cdev != nullptr && threadIdx.x < 3) out_c[threadIdx.x] = cdev[threadIdx.x];
 }
 
-// ------------------------------------------------------------------------------- sampler
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// Counter-based sampler; oracle/ransac_oracle.py::native_triples restates it bit for bit.
-__device__ void native_triple(uint64_t seed, int64_t h, int64_t nc, int out[3]) {
-  const uint64_t base = splitmix64(seed ^ ((uint64_t)h * 0x9E3779B97F4A7C15ull));
-  int got = 0;
-  for (uint64_t k = 0; got < 3 && k < (1u << 20); ++k) {
-    const uint64_t v = splitmix64(base + k);
-    const int idx = (int)(((v >> 32) * (uint64_t)nc) >> 32);
-    bool dup = false;
-    for (int j = 0; j < got; ++j) dup |= (out[j] == idx);
-    if (!dup) out[got++] = idx;
-  }
-  for (; got < 3; ++got) out[got] = got;  // unreachable for nc >= 3
-}
-
 // ------------------------------------------------------------------------------- Kabsch
 struct GuardParams {
   double cs[3], ct[3];
@@ -318,7 +297,7 @@ __global__ __launch_bounds__(256) void kabsch3_kernel(const double* __restrict__
         id[k] = (v < 0 || v >= nc) ? 0 : v;
       }
     } else {
-      native_triple(seed, hyp0 + h, nc, id);
+      native_sample(seed, hyp0 + h, nc, 3, id);  // sampler.h
     }
     double ps[3][3], qs[3][3];
     for (int k = 0; k < 3; ++k)

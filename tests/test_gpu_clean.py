@@ -115,6 +115,43 @@ def test_radius_filter(name, radius, nb):
     assert 0 < len(keep) < len(P) or radius == 0.25
 
 
+def _early_leave_cloud(name):
+    """tests/test_gpu_dbscan.py's shapes of the same names."""
+    rng = np.random.default_rng(21)
+    if name == "n65":  # one wave of candidates plus one, all within the radius of each other
+        return np.ascontiguousarray(np.array([7.0, 7.0, 7.0]) + rng.uniform(-0.01, 0.01, (65, 3)))
+    P = np.concatenate([np.tile([[0.5, 0.5, 0.5]], (200, 1)), rng.uniform(0.0, 1.0, (40, 3))])
+    return np.ascontiguousarray(P[rng.permutation(len(P))])  # a cell holding 200 coincident points
+
+
+EARLY_CLOUDS = {name: _early_leave_cloud(name) for name in ("cell200", "n65")}
+EARLY_COUNTS = {name: R.radius_counts(P, 0.1) for name, P in EARLY_CLOUDS.items()}
+
+
+@pytest.mark.parametrize("nb", [0, 63, 64, 65, 127, 128, 199, 200])
+@pytest.mark.parametrize("name", ["cell200", "n65"])
+def test_radius_filter_early_leave_across_chunks(name, nb):
+    """The count without with_counts stops once it exceeds nb: in the first, second, third and last
+    64-candidate chunk of the dense cell's row, and never.  nb = 0 is no filter parameter (Open3D
+    and the C ABI refuse nb_points < 1): the kernel meets it as DBSCAN's core pass at min_points = 1,
+    so that case compares there — the full counts, and every point core with and without them."""
+    P, want = EARLY_CLOUDS[name], EARLY_COUNTS[name]
+    assert want.max() >= (200 if name == "cell200" else 65)
+    keep = np.flatnonzero(want > nb).astype(np.int32)
+    if nb == 0:
+        with pytest.raises(ValueError):
+            prep.remove_radius_outlier(P, 0, 0.1)
+        labels, out = prep.cluster_dbscan(P, 0.1, 1, with_details=True)
+        np.testing.assert_array_equal(out.counts, want)
+        assert out.num_core == len(keep) == len(P) and out.num_noise == 0 and (labels >= 0).all()
+        np.testing.assert_array_equal(prep.cluster_dbscan(P, 0.1, 1), labels)  # the count stops at 1
+        return
+    ind, cnt = prep.remove_radius_outlier(P, nb, 0.1, with_counts=True)
+    np.testing.assert_array_equal(cnt, want)
+    np.testing.assert_array_equal(ind, keep)
+    np.testing.assert_array_equal(prep.remove_radius_outlier(P, nb, 0.1), keep)
+
+
 def test_determinism_stale_scratch_and_cached_grids():
     P = R.points("A")
     c = Cloud(P)

@@ -14,7 +14,8 @@ mean is dominated by the strays, whose nearest neighbours lie ten times as far (
 * sklearn's DBSCAN (kd_tree, every host core it is given) on the same points, once; its labels are
   compared with the device's (equal unless a pair sits within rounding of the radius).
 
-Needs the GPU; prints readable lines and one JSON line.
+Needs the GPU; prints readable lines and one JSON line.  ``AB_LIB=tools/ab/NAME.so`` times another
+build of the library (tools/ab_build.sh).
 Usage: python tools/dbscan_timing.py [--repeats 15] [--warmup 3] [--small-only] [--no-sklearn]"""
 import argparse
 import json
@@ -31,6 +32,9 @@ import torch
 
 from m3d import _lib, prep
 from m3d.core import Cloud, context
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 
 THR = 0.012
 MIN_POINTS = 10
