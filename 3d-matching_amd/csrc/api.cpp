@@ -2410,6 +2410,178 @@ int m3d_hybrid_search(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, int32
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- Colored ICP
+// colored.hip.  The loop object is the point-to-plane loop's (state, NN scan, solve); the target's
+// gradient records, the source's intensities in slot order and the terms pass's partials live in
+// one block of their own beside it, as Generalized ICP's covariances do.
+extern "C++" {
+namespace {
+struct ColoredArrays {
+  void* block = nullptr;
+  double* rec_t = nullptr;  // nt × 4: gradient, intensity
+  double* is_s = nullptr;   // ns, slot order
+  double* partials = nullptr;
+  m3d_ctx* ctx = nullptr;
+  hipStream_t st = nullptr;
+  // back to the block cache, marked after the work this call enqueued on its stream
+  ~ColoredArrays() {
+    if (block == nullptr) return;
+    ctx_touch(ctx, st);
+    ReleaseScope rs(ctx, ctx->id);
+    block_release(block);
+  }
+};
+
+constexpr int kColoredMaxNn = 30;  // KDTreeSearchParamHybrid(2·max_dist, 30)
+
+// the gradients of cloud c with the given normals and colours: rec (n × 4) and / or out3 (n × 3)
+int color_gradients(m3d_ctx* ctx, const m3d_cloud* c, const double* colors, double radius, int k, double* rec,
+                    double* out3, hipStream_t st) {
+  if (c->n == 0) return M3D_OK;
+  const Grid *g = nullptr, *gf = nullptr;
+  double hf = 0.0;
+  const int rc = search_grids(ctx, c, radius, k, st, &g, &gf, &hf);
+  if (rc) return rc;
+  HIPX(ctx, launch_color_gradients(c, c->nrm64, colors, g, radius, k, rec, out3, st, gf, hf));
+  return M3D_OK;
+}
+
+int colored_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                  const double* tgt_colors, double max_dist, int32_t nn_method, double lambda,
+                  const m3d_robust_kernel* kernel) {
+  CHECK_ARG(ctx, src && tgt, "invalid arguments");
+  CHECK_ARG(ctx, max_dist > 0.0, "Invalid max_correspondence_distance.");
+  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
+  CHECK_ARG(ctx, lambda >= 0.0 && lambda <= 1.0, "lambda_geometric must lie in [0, 1]");
+  CHECK_ARG(ctx, tgt->nrm64 != nullptr || tgt->n == 0,
+            "ColoredICP requires pre-computed normal vectors for target PointCloud.");
+  CHECK_ARG(ctx, (src_colors != nullptr || src->n == 0) && (tgt_colors != nullptr || tgt->n == 0),
+            "ColoredICP requires pre-computed colors for source and target PointCloud.");
+  return kernel != nullptr ? robust_check(ctx, kernel) : M3D_OK;
+}
+
+// allocate the arrays; the target's records from the caller's gradients, else computed
+int colored_setup_target(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* tgt_colors,
+                         const double* tgt_gradient, double max_dist, hipStream_t st, ColoredArrays* ca) {
+  ca->ctx = ctx;
+  ca->st = st;
+  Carve cc;
+  cc.add(&ca->rec_t, 4 * (size_t)tgt->n);
+  cc.add(&ca->is_s, (size_t)src->n);
+  cc.add(&ca->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(colored_blocks(src->n), 1));
+  size_t bytes = 0;
+  if (cc.alloc(&ca->block, &bytes, st) != hipSuccess)
+    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (Colored ICP arrays)");
+  if (tgt_gradient != nullptr) {
+    HIPX(ctx, launch_color_rec_pack(tgt_gradient, tgt_colors, tgt->n, ca->rec_t, st));
+    return M3D_OK;
+  }
+  return color_gradients(ctx, tgt, tgt_colors, 2.0 * max_dist, kColoredMaxNn, ca->rec_t, nullptr, st);
+}
+
+// the loop object of a Colored-ICP call (the point-to-plane loop's) and the source's intensities
+// gathered into its slot order
+int colored_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                   double max_dist, double rel_fit, double rel_rmse, int32_t max_iteration, int32_t nn_method,
+                   hipStream_t st, ColoredArrays* ca, m3d_icp** out) {
+  m3d_icp_params p{rel_fit, rel_rmse, max_iteration, M3D_EST_POINT_TO_PLANE, nn_method, 0};
+  const int rc = icp_create(ctx, src, tgt, max_dist, &p, out, true);
+  if (rc) return rc;
+  HIPX(ctx, launch_intensity_pack(src_colors, (*out)->src->slot, (*out)->src->n, ca->is_s, st));
+  return M3D_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int m3d_color_gradients(m3d_ctx* ctx, const m3d_cloud* cloud, const double* colors, double radius,
+                        int32_t max_nn, double* out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud != nullptr, "invalid arguments");
+  CHECK_ARG(ctx, radius > 0.0 && max_nn >= 1 && max_nn <= 64, "radius > 0 and 1 <= max_nn <= 64");
+  CHECK_ARG(ctx, cloud->nrm64 != nullptr || cloud->n == 0, "color gradients: the cloud has no normals");
+  CHECK_ARG(ctx, (colors != nullptr && out != nullptr) || cloud->n == 0, "color gradients: null colors or output");
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const int rc = color_gradients(ctx, cloud, colors, radius, max_nn, nullptr, out, st);
+  if (rc) return rc;
+  HIPX(ctx, hipStreamSynchronize(st));
+  return M3D_OK;
+}
+
+int m3d_colored_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                      const double* tgt_colors, const double* tgt_gradient, const double* T_host,
+                      double max_dist, int32_t nn_method, double lambda_geometric,
+                      const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  CHECK_ARG(ctx, sums_out != nullptr, "null output");
+  int rc = colored_check(ctx, src, tgt, src_colors, tgt_colors, max_dist, nn_method, lambda_geometric, kernel);
+  if (rc) return rc;
+  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
+  const int64_t ns = src->n, nt = tgt->n;
+  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
+    hipSetDevice(ctx->device);
+    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    return M3D_OK;
+  }
+  hipSetDevice(ctx->device);
+  ColoredArrays ca;
+  rc = colored_setup_target(ctx, src, tgt, tgt_colors, tgt_gradient, max_dist, st, &ca);
+  if (rc) return rc;
+  ScopedLoop s;
+  rc = colored_create(ctx, src, tgt, src_colors, max_dist, 1e-6, 1e-6, 0, nn_method, st, &ca, &s.s);
+  if (rc) return rc;
+  const int32_t kind = kernel != nullptr ? kernel->kind : M3D_KERNEL_L2;
+  const double kk = kernel != nullptr ? kernel->k : 0.0;
+  double sums[kTermSlots] = {};
+  rc = one_evaluation(s, T_host, true, [&](double* pin) {
+    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+    return launch_colored_terms(s, ca.rec_t, ca.is_s, lambda_geometric, kind, kk, ca.partials, pin, true, st);
+  }, corr_idx, kTermSlots, sums, st);
+  if (rc) return rc;
+  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
+  return M3D_OK;
+}
+
+int m3d_colored_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                        const double* tgt_colors, const double* tgt_gradient, const double* init,
+                        double max_dist, const m3d_colored_params* params, const m3d_robust_kernel* kernel,
+                        m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
+  int rc = colored_check(ctx, src, tgt, src_colors, tgt_colors, max_dist, params->nn_method,
+                         params->lambda_geometric, kernel);
+  if (rc) return rc;
+  CHECK_ARG(ctx, params->max_iteration >= 0, "max_iteration must be >= 0");
+  hipSetDevice(ctx->device);
+  ColoredArrays ca;
+  rc = colored_setup_target(ctx, src, tgt, tgt_colors, tgt_gradient, max_dist, st, &ca);
+  if (rc) return rc;
+  ScopedLoop s;
+  rc = colored_create(ctx, src, tgt, src_colors, max_dist, params->relative_fitness, params->relative_rmse,
+                      params->max_iteration, params->nn_method, st, &ca, &s.s);
+  if (rc) {
+    (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
+    return rc;
+  }
+  const int32_t kind = kernel != nullptr ? kernel->kind : M3D_KERNEL_L2;
+  const double kk = kernel != nullptr ? kernel->k : 0.0;
+  const double lambda = params->lambda_geometric;
+  rc = m3d_icp_reset(s, init, stream);
+  if (!rc)
+    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
+      return launch_colored_terms(s, ca.rec_t, ca.is_s, lambda, kind, kk, ca.partials, sums, false, st);
+    }, out, corr_idx, st);
+  if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
+  return rc;
+}
+
 int m3d_estimate_normals(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, int32_t max_nn,
                          double* normals_out, void* stream) {
   if (!ctx) return M3D_ERR_INVALID;

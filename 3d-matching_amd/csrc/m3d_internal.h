@@ -553,6 +553,20 @@ hipError_t launch_robust_plane_terms(const m3d_icp* s, int32_t kind, double k, d
                                      bool with_defer, hipStream_t st);
 hipError_t launch_robust_gicp_terms(const m3d_icp* s, int32_t kind, double k, double* cov_s, const double* cov_t,
                                     double* partials, double* sums, bool with_defer, hipStream_t st);
+// colored.hip: the colour gradients of a cloud (one wave per point on its hybrid list, g / gf /
+// hfine as hybrid_search; rec n × 4 = gradient and intensity, out3 n × 3, either may be null), a
+// caller's gradients packed into records, intensities gathered through slot, and the two-row terms
+// pass after a loop's NN scan (rec_t in target index order, is_s in slot order, partials:
+// colored_blocks(ns) × kTermSlots doubles)
+int64_t colored_blocks(int64_t ns);
+hipError_t launch_color_gradients(const m3d_cloud* c, const double* nrm, const double* colors, const Grid* g,
+                                  double radius, int k, double* rec, double* out3, hipStream_t st,
+                                  const Grid* gf = nullptr, double hfine = 0.0);
+hipError_t launch_color_rec_pack(const double* grad, const double* colors, int64_t n, double* rec, hipStream_t st);
+hipError_t launch_intensity_pack(const double* colors, const int32_t* slot, int64_t n, double* out, hipStream_t st);
+hipError_t launch_colored_terms(const m3d_icp* s, const double* rec_t, const double* is_s, double lambda,
+                                int32_t kind, double k, double* partials, double* sums, bool with_defer,
+                                hipStream_t st);
 // claim/dmin: target-shard exchange results (m3d_icp_shard_claim), or null
 hipError_t launch_icp_terms_mode(const m3d_icp* s, int64_t off, const int32_t* claim,
                                  const int64_t* dmin, hipStream_t st);

@@ -90,6 +90,11 @@ class RobustKernel(C.Structure):
     _fields_ = [("kind", i32), ("k", dbl)]
 
 
+class ColoredParams(C.Structure):
+    _fields_ = [("lambda_geometric", dbl), ("relative_fitness", dbl), ("relative_rmse", dbl),
+                ("max_iteration", i32), ("nn_method", i32)]
+
+
 class OutlierStats(C.Structure):
     _fields_ = [("kept", i64), ("valid", i64), ("mean", dbl), ("std_dev", dbl), ("threshold", dbl)]
 
@@ -173,6 +178,11 @@ SIGNATURES = {
     "m3d_gicp_terms_robust": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, i32, dbl, C.POINTER(RobustKernel),
                                         C.POINTER(dbl), vp, vp]),
     "m3d_gicp_run_robust": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(GicpParams),
+                                      C.POINTER(RobustKernel), C.POINTER(IcpResult), vp, vp]),
+    "m3d_color_gradients": (C.c_int, [vp, vp, vp, dbl, i32, vp, vp]),
+    "m3d_colored_terms": (C.c_int, [vp, vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, i32, dbl, C.POINTER(RobustKernel),
+                                    C.POINTER(dbl), vp, vp]),
+    "m3d_colored_icp_run": (C.c_int, [vp, vp, vp, vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(ColoredParams),
                                       C.POINTER(RobustKernel), C.POINTER(IcpResult), vp, vp]),
     "m3d_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams),
                               C.POINTER(IcpResult), vp, vp]),

@@ -614,6 +614,97 @@ def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_c
                       np.array(res.update[:]).reshape(4, 4))
 
 
+def _colors_device(colors, n: int, what: str):
+    """A cloud's colours (n×3 f64 in [0, 1]) as an (n, 3) cuda tensor; None or empty raises (Colored
+    ICP needs colours on both sides)."""
+    if colors is None or (n > 0 and len(colors) == 0):
+        raise ValueError(f"ColoredICP requires pre-computed colors for the {what} PointCloud.")
+    t = to_device(colors, "float64", (3,))
+    if t.shape[0] != n:
+        raise ValueError(f"{what} colors must be {n}×3")
+    return t
+
+
+def _gradient_device(grad, n: int):
+    if grad is None:
+        return None
+    t = to_device(grad, "float64", (3,))
+    if t.shape[0] != n:
+        raise ValueError(f"target gradients must be {n}×3")
+    return t
+
+
+def _colored_kernel(kernel):
+    return None if kernel is None else _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
+
+
+def color_gradients(cloud: Cloud, colors, radius: float, max_nn: int = 30) -> np.ndarray:
+    """The colour gradient of every point of ``cloud`` (m3d_color_gradients; Open3D's
+    ``InitializePointCloudForColoredICP``): over the hybrid neighbourhood (radius, max_nn ≤ 64) the
+    least-squares gradient of the intensity (r + g + b) / 3 in the point's tangent plane → (n, 3)
+    f64.  The cloud must carry normals."""
+    if not radius > 0.0:
+        raise ValueError("radius must be > 0")
+    if not cloud.has_normals and cloud.n > 0:
+        raise ValueError("color gradients: the cloud has no normals")
+    torch = _torch()
+    c = _colors_device(colors, cloud.n, "given")
+    out = device_empty((max(cloud.n, 1), 3), torch.float64)
+    cloud.ctx.check(cloud.ctx.lib.m3d_color_gradients(cloud.ctx.h, cloud.h, ptr(c), float(radius), int(max_nn),
+                                                      ptr(out), stream_handle()), "color_gradients")
+    return out[: cloud.n].cpu().numpy()
+
+
+def colored_terms(src: Cloud, tgt: Cloud, src_colors, tgt_colors, T=None, max_dist: float = 0.0,
+                  lambda_geometric: float = 0.968, tgt_gradient=None, nn: str = "grid", with_correspondences=True,
+                  kernel=None):
+    """One Colored-ICP evaluation at the transform T (m3d_colored_terms): the exact radius 1-NN,
+    then the geometric and the photometric row of every matched pair → (sums (30,) f64 in
+    gicp_terms' layout, corr_idx (ns,) int32 torch cuda or None).  tgt_gradient: the target's
+    colour gradients (nt×3), or None = color_gradients(tgt, tgt_colors, 2·max_dist, 30).  kernel:
+    a robust kernel weighting each row on its own; None or L2 is unit weights."""
+    method = _nn_method(nn)
+    if not max_dist > 0.0:
+        raise ValueError("max_dist must be > 0")
+    torch = _torch()
+    cs, ct = _colors_device(src_colors, src.n, "source"), _colors_device(tgt_colors, tgt.n, "target")
+    tg = _gradient_device(tgt_gradient, tgt.n)
+    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    sums = (C.c_double * 32)()
+    rk = _colored_kernel(kernel)
+    src.ctx.check(src.ctx.lib.m3d_colored_terms(
+        src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), ptr(tg), _T16(np.eye(4) if T is None else T), float(max_dist),
+        method, float(lambda_geometric), None if rk is None else C.byref(rk), sums, ptr(idx), stream_handle()),
+        "colored_terms")
+    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
+
+
+def colored_icp(src: Cloud, tgt: Cloud, src_colors, tgt_colors, max_dist: float, init=None,
+                lambda_geometric: float = 0.968, tgt_gradient=None, relative_fitness=1e-6, relative_rmse=1e-6,
+                max_iteration=30, with_correspondences=True, nn: str = "grid", kernel=None):
+    """registration_colored_icp on the device (m3d_colored_icp_run) → IcpOutcome.  The target needs
+    normals, both clouds colours (n×3 f64 in [0, 1]); tgt_gradient as colored_terms takes it."""
+    method = _nn_method(nn)
+    if not max_dist > 0.0:
+        raise ValueError("Invalid max_correspondence_distance.")
+    torch = _torch()
+    cs, ct = _colors_device(src_colors, src.n, "source"), _colors_device(tgt_colors, tgt.n, "target")
+    tg = _gradient_device(tgt_gradient, tgt.n)
+    p = _lib.ColoredParams(float(lambda_geometric), float(relative_fitness), float(relative_rmse),
+                           int(max_iteration), method)
+    res = _lib.IcpResult()
+    corr = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
+    rk = _colored_kernel(kernel)
+    src.ctx.check(src.ctx.lib.m3d_colored_icp_run(
+        src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), ptr(tg), _T16(np.eye(4) if init is None else init),
+        float(max_dist), C.byref(p), None if rk is None else C.byref(rk), C.byref(res), ptr(corr), stream_handle()),
+        "colored_icp_run")
+    pairs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
+    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
+                      res.num_correspondences, res.iterations, bool(res.converged), pairs,
+                      np.array(res.update[:]).reshape(4, 4))
+
+
 class IcpLoop:
     """Step-wise device ICP (benchmarks, multi-GPU).  Every call only enqueues work."""
 

@@ -89,8 +89,36 @@ def _skip_binary_element(f, count, props, endian):
                 f.seek(np.dtype(t).itemsize, 1)
 
 
+def _colors_of(cols, props):
+    """``red green blue`` of the parsed vertex columns → N×3 f64 in [0, 1], or None: ``uchar`` values
+    are divided by 255 (``ushort`` by 65535), float and double values are taken as they are."""
+    types = dict(props)
+    if not all(k in types for k in ("red", "green", "blue")):
+        return None
+    out = np.empty((len(cols["red"]), 3), np.float64)
+    for a, k in enumerate(("red", "green", "blue")):
+        v = np.asarray(cols[k], np.float64)
+        out[:, a] = v / {"u1": 255.0, "u2": 65535.0}.get(types[k], 1.0)
+    return out
+
+
 def read_ply(path):
     """Read vertices of a PLY file → ``(points N×3 f64, normals N×3 f64 or None)``."""
+    return _read_vertices(path)[:2]
+
+
+def read_point_cloud(path):
+    """Open3D ``io.read_point_cloud`` for ``.ply``: a ``PointCloud`` with the file's points, its
+    normals and its colours (``red green blue``: ``uchar`` divided by 255, float / double as is)
+    where it has them."""
+    from .types import PointCloud
+
+    pts, nrm, col = _read_vertices(path)
+    return PointCloud(pts, nrm, colors=col)
+
+
+def _read_vertices(path):
+    """→ (points, normals or None, colours or None) of the vertex element."""
     path = Path(path)
     with open(path, "rb") as f:
         fmt, elements = _parse_header(f)
@@ -110,7 +138,7 @@ def read_ply(path):
                         nrm = None
                         if all(k in names for k in ("nx", "ny", "nz")):
                             nrm = np.stack([cols["nx"], cols["ny"], cols["nz"]], axis=1)
-                        return pts, nrm
+                        return pts, nrm, _colors_of(cols, props)
                 else:
                     if any(isinstance(t, tuple) for _, t in props):
                         raise PlyError("list properties in the vertex element are not supported")
@@ -124,7 +152,7 @@ def read_ply(path):
                 nrm = None
                 if all(k in names for k in ("nx", "ny", "nz")):
                     nrm = np.stack([cols["nx"], cols["ny"], cols["nz"]], axis=1).astype(np.float64)
-                return pts, nrm
+                return pts, nrm, _colors_of(cols, props)
             # an element before the vertices: skip it
             if fmt == "ascii":
                 for _ in range(count):
@@ -179,9 +207,38 @@ def _read_ascii_vertices(f, count, props):
     return {p: data[:, k] for k, (p, _) in enumerate(props)}
 
 
-def write_ply(path, points, normals=None, binary: bool = False, dtype="double"):
-    """Write a PLY point cloud (x y z [nx ny nz]); ``dtype`` "double" or "float"."""
+def _write_ply_colored(path, pts, normals, colors, binary, dtype):
+    """x y z [nx ny nz] as ``dtype`` plus ``uchar red green blue`` = round(c·255) clipped to [0, 255]."""
+    np_t = {"double": "f8", "float": "f4"}[dtype]
+    rgb = np.clip(np.rint(np.asarray(colors, np.float64).reshape(-1, 3) * 255.0), 0, 255).astype(np.uint8)
+    if len(rgb) != len(pts):
+        raise ValueError("colors must match points")
+    names = ["x", "y", "z"] + (["nx", "ny", "nz"] if normals is not None else [])
+    real = pts if normals is None else np.concatenate([pts, np.asarray(normals, np.float64).reshape(-1, 3)], axis=1)
+    head = (["ply", f"format {'binary_little_endian' if binary else 'ascii'} 1.0", f"element vertex {len(pts)}"]
+            + [f"property {dtype} {n}" for n in names] + [f"property uchar {c}" for c in ("red", "green", "blue")]
+            + ["end_header"])
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        if binary:
+            rec = np.empty(len(pts), np.dtype([(n, "<" + np_t) for n in names] + [(c, "u1") for c in "rgb"]))
+            for k, n in enumerate(names):
+                rec[n] = real[:, k]
+            for k, c in enumerate("rgb"):
+                rec[c] = rgb[:, k]
+            f.write(rec.tobytes())
+        else:
+            fmt = repr if dtype == "double" else (lambda v: "%.9g" % np.float32(v))
+            f.write("".join(" ".join(map(fmt, row)) + " " + " ".join(map(str, c)) + "\n"
+                            for row, c in zip(real.tolist(), rgb.tolist())).encode("ascii"))
+
+
+def write_ply(path, points, normals=None, binary: bool = False, dtype="double", colors=None):
+    """Write a PLY point cloud (x y z [nx ny nz] [red green blue]); ``dtype`` "double" or "float";
+    ``colors`` (N×3 in [0, 1]) are written as ``uchar``, c·255 rounded to nearest and clipped."""
     pts = np.asarray(points, np.float64).reshape(-1, 3)
+    if colors is not None:
+        return _write_ply_colored(path, pts, normals, colors, binary, dtype)
     cols = [pts]
     names = ["x", "y", "z"]
     if normals is not None:

@@ -6,8 +6,8 @@
 * ``FastGlobalRegistrationOption`` — Open3D ``pipelines.registration.FastGlobalRegistrationOption``:
   the same names and defaults.
 * ``PointCloud`` — the two attributes the path reads from ``o3d.geometry.PointCloud``:
-  ``points`` (N×3 f64) and ``normals`` (N×3 f64 or empty), and ``covariances`` (N×3×3 f64 or
-  empty) for Generalized ICP.
+  ``points`` (N×3 f64) and ``normals`` (N×3 f64 or empty), ``covariances`` (N×3×3 f64 or
+  empty) for Generalized ICP and ``colors`` (N×3 f64 in [0, 1] or empty) for Colored ICP.
 """
 
 from __future__ import annotations
@@ -63,12 +63,14 @@ class Feature:
 
 
 class PointCloud:
-    def __init__(self, points=None, normals=None, covariances=None):
+    def __init__(self, points=None, normals=None, covariances=None, colors=None):
         self.points = np.zeros((0, 3)) if points is None else np.asarray(points, np.float64).reshape(-1, 3)
         self.normals = np.zeros((0, 3)) if normals is None else np.asarray(normals, np.float64).reshape(-1, 3)
         # per-point 3×3 covariances (Open3D ``PointCloud.covariances``, Generalized ICP), or none
         self.covariances = (np.zeros((0, 3, 3)) if covariances is None
                             else np.asarray(covariances, np.float64).reshape(-1, 3, 3))
+        # per-point RGB in [0, 1] (Open3D ``PointCloud.colors``, Colored ICP), or none
+        self.colors = np.zeros((0, 3)) if colors is None else np.asarray(colors, np.float64).reshape(-1, 3)
 
     def has_points(self) -> bool:
         return len(self.points) > 0
@@ -79,6 +81,9 @@ class PointCloud:
     def has_covariances(self) -> bool:
         return len(self.covariances) == len(self.points) and len(self.points) > 0
 
+    def has_colors(self) -> bool:
+        return len(self.colors) == len(self.points) and len(self.points) > 0
+
     def compute_point_cloud_distance(self, target) -> np.ndarray:
         """Open3D ``PointCloud.compute_point_cloud_distance``: for each point the distance to its
         nearest point of ``target``, on the device (matcher.evaluate)."""
@@ -87,7 +92,7 @@ class PointCloud:
         return compute_point_cloud_distance(self, target)
 
     def select_by_index(self, indices, invert: bool = False) -> "PointCloud":
-        """Open3D ``PointCloud.select_by_index``: the points (and normals, covariances) at
+        """Open3D ``PointCloud.select_by_index``: the points (and normals, covariances, colours) at
         ``indices`` in index order; ``invert`` selects every other point."""
         n = len(self.points)
         mask = np.zeros(n, bool)
@@ -95,7 +100,18 @@ class PointCloud:
         if invert:
             mask = ~mask
         return PointCloud(self.points[mask], self.normals[mask] if self.has_normals() else None,
-                          self.covariances[mask] if self.has_covariances() else None)
+                          self.covariances[mask] if self.has_covariances() else None,
+                          self.colors[mask] if self.has_colors() else None)
+
+    def voxel_down_sample(self, voxel_size: float) -> "PointCloud":
+        """Open3D ``PointCloud.voxel_down_sample`` on the device (m3d.prep): points, normals and
+        colours are each the plain per-voxel mean, voxels in ascending (ix, iy, iz) order.  The
+        colours go through the same mean kernel in a second pass over the same voxels."""
+        from .prep import voxel_down_sample
+
+        pts, nrm = voxel_down_sample(self.points, voxel_size, normals=self.normals if self.has_normals() else None)
+        col = voxel_down_sample(self.points, voxel_size, normals=self.colors)[1] if self.has_colors() else None
+        return PointCloud(pts, nrm, colors=col)
 
     def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
         """Open3D ``PointCloud.remove_statistical_outlier`` on the device (m3d.prep) →

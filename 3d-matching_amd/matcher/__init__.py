@@ -9,6 +9,7 @@ façade the reference's ``main()`` intends (`src/main.py:34-38`).
 
 from __future__ import annotations
 
+from .colored import registration_colored_icp
 from .evaluate import (
     compute_point_cloud_distance,
     evaluate_registration,
@@ -52,6 +53,7 @@ __all__ = [
     "registration_fgr_based_on_feature_matching",
     "run_ransac",
     "refine_registration",
+    "registration_colored_icp",
     "registration_generalized_icp",
     "registration_icp",
     "register",

@@ -16,8 +16,9 @@ by the device path of ``m3d.prep``:
    cluster of Open3D's ``cluster_dbscan`` (the object, without the clamp, the hand and the plane's
    leftover rim) after 1b; ``cluster_label``, ``cluster_size`` and ``num_clusters`` keep what was
    found; no cluster at all is a ``ValueError``
-2. ``pcd_down`` = voxel down-sample (voxel_size); file normals, when present, are averaged
-   per voxel like Open3D's VoxelDownSample                                           ply.py:106
+2. ``pcd_down`` = voxel down-sample (voxel_size); file normals and colours (``red green blue``,
+   kept in ``pcd.colors``), when present, are averaged per voxel like Open3D's VoxelDownSample
+                                                                                     ply.py:106
 3. ``pcd_down`` normals: hybrid search (2·v, 30), oriented by those averaged normals ply.py:110-112
 4. ``pcd_fpfh`` = FPFH on ``pcd_down`` (hybrid 5·v, 100) — an Open3D-style ``Feature``
    (``.data`` 33×N)                                                                  ply.py:117-120
@@ -58,11 +59,11 @@ class Ply:
         from m3d import plyio
 
         t0 = time.perf_counter()
-        pts, nrm = plyio.read_ply(self.path)
+        pcd = plyio.read_point_cloud(self.path)  # points, normals and colours where the file has them
         self.stage_ms = {"read": (time.perf_counter() - t0) * 1e3}
-        if len(pts) == 0:
+        if len(pcd.points) == 0:
             raise ValueError(f"Point cloud is empty: {self.path}")          # ply.py:81-84
-        self.pcd = PointCloud(pts, nrm)
+        self.pcd = pcd
         self._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster, keypoints)
 
     def _remove_outliers(self, params: dict) -> None:
@@ -159,11 +160,13 @@ class Ply:
         # VoxelDownSample carries the file's normals (their plain per-voxel mean) into pcd_down,
         # and EstimateNormals then orients each new normal by that mean (ply.py:106-112)
         down, down_prev = prep.voxel_down_sample(p_dev, v, normals=prev)
+        # ... and the file's colours, the same way (Colored ICP reads them from pcd_down)
+        down_col = prep.voxel_down_sample(p_dev, v, normals=self.pcd.colors)[1] if self.pcd.has_colors() else None
         lap("voxel_down_sample")
         c_down = Cloud(down, down_prev)
         down_n = prep.estimate_normals(c_down, 2 * v, 30)
         lap("normals_down")
-        self.pcd_down = PointCloud(down, down_n)
+        self.pcd_down = PointCloud(down, down_n, colors=down_col)
         self.pcd_fpfh = Feature(prep.compute_fpfh(c_down, down_n, 5 * v, 100).T)
         lap("fpfh")
         if keypoints is not None:

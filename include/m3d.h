@@ -521,6 +521,69 @@ int m3d_gicp_run_robust(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt
                         const m3d_gicp_params* params, const m3d_robust_kernel* kernel, m3d_icp_result* out,
                         int32_t* corr_idx, void* stream);
 
+/* ------------------------------------------------------------------ Colored ICP (colored.hip)
+ * Open3D 0.19 registration_colored_icp (ColoredICP.cpp; Park, Zhou, Koltun 2017), restated in
+ * tests/colored_restatement.py; added within ABI 13, the version number is unchanged.  It is
+ * RegistrationICP with another ComputeTransformation: the NN search, the loop's transformed copy
+ * of the source, fitness, the geometric inlier_rmse = sqrt(sum d^2 / count) and the convergence
+ * rule are m3d_icp_run's.  Colours are n x 3 f64 in [0, 1] in the cloud's point order; the
+ * intensity of a point is I = (r + g + b) / 3.
+ *
+ * Gradient of a target point (vt, unit normal nt, intensity it): its hybrid neighbour list (the
+ * max_nn nearest with d^2 < radius^2, itself included, ordered by (d^2, index): m3d_hybrid_search's
+ * list) of length nn; nn < 4 gives 0.  Else entry 0 is skipped whatever it is (Open3D's loop
+ * starts at 1; among exact duplicates of the query FLANN's order is unpinned, here the lowest index
+ * leads), every other entry p, ip gives the row A = (p - ((p - vt) . nt) nt) - vt, b = ip - it,
+ * one more row is A = (nn - 1) nt, b = 0, and the gradient solves (A^T A) x = A^T b by LDLT.
+ * Departure: a pivot that is not positive and finite, or a non-finite solution, gives 0.
+ *
+ * Terms of a matched pair (moved source vs, intensity is; target vt, nt, it, gradient dit), sg =
+ * sqrt(lambda_geometric), sp = sqrt(1 - lambda_geometric):
+ *   r0 = sg (vs - vt) . nt,            J0 = sg [vs x nt | nt]
+ *   proj = vs - ((vs - vt) . nt) nt,   is0 = dit . (proj - vt) + it,   ditM = -(I - nt nt^T) dit
+ *   r1 = sp (is - is0),                J1 = sp [vs x ditM | ditM]
+ * each row weighted on its own by the robust kernel (NULL or L2: 1) and added as the robust
+ * point-to-plane row is: w J J^T, w J r, r^2 unweighted.  All sums are fp64 and added in a fixed
+ * order: both nn_methods, and repeated calls, return the same bits. */
+
+/* out[i] = the colour gradient of point i.  cloud must carry normals; colors [device] n x 3 f64,
+ * out [device] n x 3 f64.  M3D_ERR_INVALID for radius <= 0, max_nn outside [1, 64] (one list entry
+ * per lane of a wave), a cloud without normals or null colours.  An empty cloud launches nothing.
+ * Synchronous. */
+int m3d_color_gradients(m3d_ctx* ctx, const m3d_cloud* cloud, const double* colors, double radius,
+                        int32_t max_nn, double* out, void* stream);
+
+/* One evaluation, as m3d_gicp_terms: T_host applied unless isIdentity(), the exact radius 1-NN,
+ * then sums_out [host] 32 f64 in the point-to-plane slot layout.  src_colors / tgt_colors [device]
+ * n x 3 f64; tgt_gradient [device] nt x 3 f64 or NULL = computed with radius 2 max_dist, max_nn 30
+ * (KDTreeSearchParamHybrid).  kernel NULL or kind L2: unit weights.  corr_idx [device] ns int32 or
+ * NULL.  An empty source or target gives zeros.  M3D_ERR_INVALID for max_dist <= 0,
+ * lambda_geometric outside [0, 1], an unknown nn_method, a target without normals, null colours
+ * of a non-empty cloud, or a bad kernel; M3D_ERR_HIP when the grid NN's deferral list overflowed.
+ * Synchronous. */
+int m3d_colored_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                      const double* tgt_colors, const double* tgt_gradient, const double* T_host,
+                      double max_dist, int32_t nn_method, double lambda_geometric,
+                      const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx, void* stream);
+
+typedef struct {
+  double lambda_geometric; /* 0.968 */
+  double relative_fitness; /* ICPConvergenceCriteria defaults 1e-6 */
+  double relative_rmse;    /* 1e-6 */
+  int32_t max_iteration;   /* 30 */
+  int32_t nn_method;       /* M3D_NN_* */
+} m3d_colored_params;
+
+/* registration_colored_icp.  The target's gradients are built once (or taken from tgt_gradient),
+ * then the loop runs as m3d_gicp_run does: three launches per iteration, enqueued in growing
+ * chunks with a look at the state's `done` in between.  out and corr_idx as m3d_icp_run fills
+ * them.  M3D_ERR_INVALID as m3d_colored_terms, and for max_iteration < 0; M3D_ERR_HIP for a
+ * deferral-list overflow, as m3d_icp_result_get reports it.  Synchronous. */
+int m3d_colored_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
+                        const double* tgt_colors, const double* tgt_gradient, const double* init,
+                        double max_dist, const m3d_colored_params* params, const m3d_robust_kernel* kernel,
+                        m3d_icp_result* out, int32_t* corr_idx, void* stream);
+
 /* ------------------------------------------------------------------ preprocessing
  * Open3D 0.19 semantics restated (oracle/prep_oracle.py); all fp64. */
 
