@@ -3146,6 +3146,102 @@ int m3d_fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, dou
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- point-to-mesh distance
+// mesh.hip; a query call's scratch from the context's preprocessing buffer (the calls synchronise
+// before returning), the mesh's arrays and its grid from the block cache
+int m3d_mesh_create(m3d_ctx* ctx, const double* vertices, int64_t nv, const int32_t* triangles, int64_t nf,
+                    m3d_mesh** out) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, out != nullptr, "null output");
+  *out = nullptr;
+  CHECK_ARG(ctx, nv >= 0 && nv < ((int64_t)1 << 31) && nf >= 0 && nf < ((int64_t)1 << 26), "mesh size out of range");
+  CHECK_ARG(ctx, (nv == 0 || vertices) && (nf == 0 || triangles), "null device pointer");
+  hipSetDevice(ctx->device);
+  hipStream_t st = nullptr;
+  Touch tch{ctx, st};
+  m3d_mesh* m = new m3d_mesh();
+  m->ctx = ctx;
+  m->ctx_id = ctx->id;
+  m->nv = nv;
+  m->nf = nf;
+  Carve cv;
+  cv.add(&m->v64, 3 * (size_t)nv);
+  cv.add(&m->tri, 3 * (size_t)nf);
+  cv.add(&m->tri9, 9 * (size_t)nf);
+  cv.add(&m->ok, (size_t)nf);
+  if (cv.alloc(&m->block, &m->block_bytes, st) != hipSuccess) {
+    m3d_mesh_destroy(m);
+    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (mesh)");
+  }
+  hipError_t e = hipSuccess;
+  if (nv > 0) e = hipMemcpyAsync(m->v64, vertices, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && nf > 0)
+    e = hipMemcpyAsync(m->tri, triangles, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyDeviceToDevice, st);
+  int bad = 0;
+  if (e == hipSuccess) e = mesh_upload(m, st, &bad);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess || bad != 0) {
+    m3d_mesh_destroy(m);
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh upload: ") + hipGetErrorString(e));
+    return m3d_fail(ctx, M3D_ERR_INVALID, "triangle index outside [0, number of vertices)");
+  }
+  *out = m;
+  return M3D_OK;
+}
+
+void m3d_mesh_destroy(m3d_mesh* m) {
+  if (!m) return;
+  ReleaseScope rs(m->ctx, m->ctx_id);
+  if (m->gblock) block_release(m->gblock);
+  if (m->block) block_release(m->block);
+  delete m;
+}
+
+int64_t m3d_mesh_size(const m3d_mesh* m) { return m ? m->nf : -1; }
+
+int m3d_mesh_closest(m3d_ctx* ctx, m3d_mesh* mesh, const double* xyz, int64_t n, const double* T, int32_t path,
+                     double r0, double* d2_out, int32_t* tri_out, double* point_out, double* uv_out,
+                     uint8_t* region_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, mesh && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || xyz), "invalid arguments");
+  CHECK_ARG(ctx, path >= 0 && path <= 2, "path: 0 automatic, 1 brute force, 2 grid");
+  CHECK_ARG(ctx, mesh->usable > 0, "the mesh has no usable triangle (none, or every one degenerate or not finite)");
+  mesh->last_rounds = 0;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  double T12[12];
+  if (T != nullptr)
+    for (int k = 0; k < 12; ++k) T12[k] = T[k];
+  const double* Tp = T != nullptr ? T12 : nullptr;
+  const bool brute = path == 1 || (path == 0 && mesh->nf <= kMeshAutoBruteMax);
+  if (brute) {
+    HIPX(ctx, mesh_closest_brute(mesh, xyz, n, Tp, d2_out, tri_out, point_out, uv_out, region_out, st));
+    return M3D_OK;
+  }
+  char* scratch = nullptr;
+  int rc = prep_buffer(ctx, mesh_scratch_bytes(n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  hipError_t e = mesh_closest_grid(ctx, mesh, xyz, n, Tp, r0, d2_out, tri_out, point_out, uv_out, region_out,
+                                   scratch, st, &why);
+  if (e != hipSuccess) return clean_fail(ctx, "mesh_closest", e, why);
+  return M3D_OK;
+}
+
+int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4) {
+  if (!mesh || !out4) return M3D_ERR_INVALID;
+  out4[0] = mesh->grid_built ? mesh->grid.ncells : 0;
+  out4[1] = mesh->grid_built ? mesh->nrefs : 0;
+  out4[2] = mesh->grid_built ? mesh->doublings : 0;
+  out4[3] = mesh->last_rounds;
+  return M3D_OK;
+}
+
+int32_t m3d_mesh_brute_tile(void) { return kMeshBruteTile; }
+int32_t m3d_mesh_auto_brute_max(void) { return kMeshAutoBruteMax; }
+
 // ------------------------------------------------------------------------------- test hooks
 int m3d_debug_kabsch3_host(const double* src9, const double* tgt9, double* T16) {
   if (!src9 || !tgt9 || !T16) return M3D_ERR_INVALID;

@@ -143,6 +143,25 @@ struct Grid {
   size_t block_bytes = 0;
 };
 
+// Uniform grid of triangle references over a mesh's box (mesh.hip): cell c holds
+// refs[start[c] .. start[c + 1]), the usable triangles whose widened fp32 box overlaps it.
+struct TriGridDev {
+  float o[3];
+  float inv_h;
+  int n[3];
+  int64_t ncells = 0;
+  const int32_t* start = nullptr;  // ncells + 1 offsets
+  const int32_t* refs = nullptr;   // triangle indices, cell by cell
+  float margin = 0.0f;             // what every triangle's box is widened by (mesh.hip, covering argument)
+};
+// triangles per LDS tile of the brute-force point-to-mesh kernel (m3d_mesh_brute_tile)
+constexpr int kMeshBruteTile = 256;
+// m3d_mesh_closest path 0: brute force up to this many triangles, the grid above.  Measured with
+// 180k queries (tools/mesh_timing.py): brute force 1.7× faster at F = 576, the grid
+// 4 % faster at F = 1024; brute force grows by 0.63 µs per triangle and meets the grid's flat
+// 0.62 ms at F ≈ 980
+constexpr int kMeshAutoBruteMax = 960;
+
 // Device scratch for the temporaries of setup work (grid sorts, Morton copies, cloud packing):
 // grown on demand and owned by the context.  Setup work runs in stream order, so consecutive
 // users on one stream reuse it without a host sync; an outgrown buffer is retired (freed with the
@@ -344,6 +363,29 @@ struct m3d_cloud {
   // one allocation holding the point arrays (Carve; m3d_cloud_destroy frees it, not them)
   void* block = nullptr;
   size_t block_bytes = 0;
+};
+
+// A triangle mesh on the device (mesh.hip): what m3d_mesh_closest searches.
+struct m3d_mesh {
+  m3d_ctx* ctx = nullptr;
+  uint64_t ctx_id = 0;  // ctx->id at creation
+  int64_t nv = 0, nf = 0;
+  int64_t usable = 0;       // triangles the search considers (mesh.hip, contract)
+  double* v64 = nullptr;    // nv×3 vertices
+  int32_t* tri = nullptr;   // nf×3 vertex indices, validated on upload
+  double* tri9 = nullptr;   // nf×9: each triangle's a, b, c gathered (what both kernels read)
+  uint8_t* ok = nullptr;    // nf usable flags
+  void* block = nullptr;    // one allocation holding the four arrays above
+  size_t block_bytes = 0;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // box of the usable triangles
+  // the triangle grid, built by the first grid query
+  bool grid_built = false;
+  m3d::TriGridDev grid{};
+  void* gblock = nullptr;  // grid.start and grid.refs
+  size_t gblock_bytes = 0;
+  int64_t nrefs = 0;
+  int32_t doublings = 0;    // cell-size doublings of the build
+  int32_t last_rounds = 0;  // ladder rounds of the last call (0: brute force)
 };
 
 struct m3d_icp {
@@ -720,6 +762,19 @@ hipError_t fgr_rows(m3d_ctx* ctx, const double* src, int64_t ns, const double* t
 // the loop over the row set fgr_rows left in the same scratch: out->T_norm, out->par_final.  Synchronous.
 hipError_t fgr_optimise(m3d_ctx* ctx, int64_t ns, int64_t nt, int64_t nc, const m3d_fgr_params* p,
                         m3d_fgr_result* out, void* scratch, hipStream_t st);
+// point-to-mesh distance (mesh.hip).  mesh_upload: m->v64 / m->tri hold the caller's arrays; checks
+// the indices (*bad_index: one lies outside [0, nv), nothing else is filled), packs tri9 / ok and
+// reads back the usable count and box.  The two paths of a query call (synchronous; T: 12 host
+// doubles or null; every output [device] or null): brute force, and the grid with its radius
+// ladder (r0 ≤ 0: one cell; scratch: mesh_scratch_bytes(n); m->last_rounds; why: the message of a
+// failure that is not a HIP error, hipErrorUnknown).
+hipError_t mesh_upload(m3d_mesh* m, hipStream_t st, int* bad_index);
+size_t mesh_scratch_bytes(int64_t n);
+hipError_t mesh_closest_brute(const m3d_mesh* m, const double* xyz, int64_t n, const double* T, double* d2,
+                              int32_t* tri, double* point, double* uv, uint8_t* region, hipStream_t st);
+hipError_t mesh_closest_grid(m3d_ctx* ctx, m3d_mesh* m, const double* xyz, int64_t n, const double* T, double r0,
+                             double* d2, int32_t* tri, double* point, double* uv, uint8_t* region, void* scratch,
+                             hipStream_t st, std::string* why);
 size_t fgr_terms_scratch_bytes(int64_t n);
 // one iteration's sums over n ≥ 1 given rows (path as m3d_fgr_params.path) → sums27 [host].  Synchronous.
 hipError_t fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, int path,

@@ -36,6 +36,8 @@ ABI_VERSION = 13
 PLANE_CHUNK = 512  # plane.hip kPlaneChunk (m3d_plane_chunk): points per chunk of the score kernel's partial sums
 FGR_TRIAL_BATCH = 16384  # fgr.hip kFgrTrialBatch (m3d_fgr_trial_batch): trials per batch of the tuple test
 FGR_ONE_WG_ROWS = 3072   # fgr.hip kFgrOneWgRows (m3d_fgr_one_wg_rows): rows the one-workgroup loop holds
+MESH_AUTO, MESH_BRUTE, MESH_GRID = 0, 1, 2  # m3d_mesh_closest path
+MESH_BRUTE_TILE = 256  # mesh.hip kMeshBruteTile (m3d_mesh_brute_tile): triangles per LDS tile of the brute kernel
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -230,6 +232,13 @@ SIGNATURES = {
     "m3d_fgr_terms": (C.c_int, [vp, vp, vp, i64, dbl, C.POINTER(dbl), vp]),
     "m3d_fgr_trial_batch": (i32, []),
     "m3d_fgr_one_wg_rows": (i32, []),
+    "m3d_mesh_create": (C.c_int, [vp, vp, i64, vp, i64, C.POINTER(vp)]),
+    "m3d_mesh_destroy": (None, [vp]),
+    "m3d_mesh_size": (i64, [vp]),
+    "m3d_mesh_closest": (C.c_int, [vp, vp, vp, i64, C.POINTER(dbl), i32, dbl, vp, vp, vp, vp, vp, vp]),
+    "m3d_mesh_grid_info": (C.c_int, [vp, C.POINTER(i64)]),
+    "m3d_mesh_brute_tile": (i32, []),
+    "m3d_mesh_auto_brute_max": (i32, []),
     "m3d_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "m3d_comm_init": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(vp)]),
     "m3d_comm_destroy": (None, [vp]),

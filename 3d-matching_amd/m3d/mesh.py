@@ -1,0 +1,245 @@
+"""Triangle meshes and the point-to-mesh distance (mesh.hip through the C ABI).
+
+What an Open3D user runs after registering a CAD model against a scan and its replacement here:
+
+| Open3D                                                        | here                                   |
+|---------------------------------------------------------------|----------------------------------------|
+| ``o3d.io.read_triangle_mesh(path)`` (STL)                      | ``read_triangle_mesh``                 |
+| ``t.geometry.RaycastingScene.add_triangles``                   | ``RaycastingScene.add_triangles``      |
+| ``RaycastingScene.compute_closest_points`` / ``compute_distance`` | the same methods, ``closest_points`` |
+
+The contract is mesh.hip's (restated in numpy by tests/mesh_restatement.py): Ericson's closest point
+on a triangle in fp64 in one fixed operation order, the winner the smallest (d², triangle index)
+over every usable triangle.  Queries are float64 (n, 3); the arithmetic runs on the GPU, the brute
+force path and the grid path return the same bits.  Parity with Open3D itself is unpinned (Embree
+works in float32).  Ray casting, occupancy and signed distance (ray parity in Open3D) are not here.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from pathlib import Path
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["TriangleMesh", "RaycastingScene", "read_triangle_mesh", "closest_points"]
+
+INVALID_ID = np.uint32(0xFFFFFFFF)  # Open3D RaycastingScene.INVALID_ID
+
+
+class TriangleMesh:
+    """Vertices (V, 3) float64 and triangles (F, 3) int32 on the host; the device object
+    (m3d_mesh: the arrays, later the triangle grid) is made by the first query and owned here."""
+
+    def __init__(self, vertices=None, triangles=None):
+        v = np.zeros((0, 3)) if vertices is None else np.asarray(vertices, np.float64)
+        t = np.zeros((0, 3), np.int64) if triangles is None else np.asarray(triangles)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("vertices must be (V, 3)")
+        if t.size and (t.ndim != 2 or t.shape[1] != 3):
+            raise ValueError("triangles must be (F, 3)")
+        t = t.reshape(-1, 3)
+        if t.size and not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("triangles must be integers")
+        if t.size and (int(t.min()) < 0 or int(t.max()) >= len(v)):
+            raise ValueError(f"triangle index outside [0, {len(v)})")
+        self.vertices = np.ascontiguousarray(v)
+        self.triangles = np.ascontiguousarray(t, np.int32)
+        self._h = None
+        self._ctx = None
+
+    def has_vertices(self) -> bool:
+        return len(self.vertices) > 0
+
+    def has_triangles(self) -> bool:
+        return len(self.vertices) > 0 and len(self.triangles) > 0
+
+    def triangle_normals(self) -> np.ndarray:
+        """(F, 3) unit face normals (b − a) × (c − a) / |·| (zeros for a zero-area triangle)."""
+        a, b, c = (self.vertices[self.triangles[:, k]] for k in range(3))
+        n = np.cross(b - a, c - a)
+        ln = np.linalg.norm(n, axis=1, keepdims=True)
+        return np.divide(n, ln, out=np.zeros_like(n), where=ln > 0)
+
+    def transform(self, T) -> "TriangleMesh":
+        """Open3D ``TriangleMesh.transform``: the vertices moved by the 4×4 ``T`` in place; the
+        device object is dropped and made again by the next query."""
+        T = np.asarray(T, np.float64).reshape(4, 4)
+        self.vertices = np.ascontiguousarray(self.vertices @ T[:3, :3].T + T[:3, 3])
+        self._release()
+        return self
+
+    # ---- device object
+    def _handle(self):
+        if self._h is None:
+            from .core import context, ptr, to_device
+
+            ctx = context()
+            v = to_device(self.vertices)
+            t = to_device(self.triangles, "int32", (3,))
+            h = C.c_void_p()
+            ctx.check(ctx.lib.m3d_mesh_create(ctx.h, ptr(v), len(self.vertices), ptr(t), len(self.triangles),
+                                              C.byref(h)), "mesh_create")
+            self._h, self._ctx = h, ctx
+        return self._ctx, self._h
+
+    def _release(self):
+        h, self._h = self._h, None
+        if h:
+            self._ctx.lib.m3d_mesh_destroy(h)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:  # interpreter teardown
+            pass
+
+    def grid_info(self) -> dict:
+        """m3d_mesh_grid_info: the triangle grid's cells and references, the cell-size doublings of
+        its build and the ladder rounds of the last query (0: it ran brute force)."""
+        ctx, h = self._handle()
+        out = (C.c_int64 * 4)()
+        ctx.check(ctx.lib.m3d_mesh_grid_info(h, out), "mesh_grid_info")
+        return {"cells": out[0], "references": out[1], "doublings": out[2], "rounds": out[3]}
+
+    def __repr__(self):
+        return f"TriangleMesh with {len(self.vertices)} points and {len(self.triangles)} triangles."
+
+
+def read_triangle_mesh(path) -> TriangleMesh:
+    """``o3d.io.read_triangle_mesh`` for STL (binary or ASCII, ``m3d.plyio.read_stl``: vertices
+    merged by exact equality).  PLY face lists are not read: a ``.ply`` raises."""
+    from .plyio import read_stl
+
+    ext = Path(path).suffix.lower()
+    if ext == ".ply":
+        raise ValueError(f"{path}: PLY face lists are not supported; read_triangle_mesh reads STL "
+                         "(m3d.plyio.read_point_cloud reads a PLY's vertices)")
+    if ext != ".stl":
+        raise ValueError(f"{path}: unsupported mesh format {ext or '(none)'}; read_triangle_mesh reads STL")
+    v, f = read_stl(path)
+    return TriangleMesh(v, f)
+
+
+_PATHS = {None: _lib.MESH_AUTO, "auto": _lib.MESH_AUTO, "brute": _lib.MESH_BRUTE, "grid": _lib.MESH_GRID}
+
+
+def _queries(points) -> np.ndarray:
+    q = np.asarray(points)
+    if q.dtype != np.float64:
+        raise ValueError("queries must be float64 (n, 3)")
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("queries must be float64 (n, 3)")
+    return np.ascontiguousarray(q)
+
+
+def closest_points(mesh: TriangleMesh, points, transformation=None, path=None, r0: float = 0.0) -> dict:
+    """m3d_mesh_closest: for every query (moved by ``transformation`` when given) the closest
+    triangle of ``mesh``.  → ``d2`` (n,), ``triangle`` (n,) int32, ``point`` (n, 3), ``uv`` (n, 2)
+    (v, w: point ≈ (1−v−w)·a + v·b + w·c), ``region`` (n,) uint8 (0 1 2 vertex a b c, 3 4 5 edge
+    ab ac bc, 6 face).  ``path``: "auto" | "brute" | "grid"; ``r0``: the grid path's first radius
+    (<= 0: one cell) — neither changes a bit of the result.  ValueError for a mesh without a usable
+    triangle."""
+    from .core import _torch, device_empty, ptr, stream_handle, to_device
+
+    q = _queries(points)
+    n = len(q)
+    ctx, h = mesh._handle()
+    torch = _torch()
+    qd = to_device(q)
+    m = max(n, 1)
+    d2 = device_empty((m,), torch.float64)
+    tri = device_empty((m,), torch.int32)
+    pt = device_empty((m, 3), torch.float64)
+    uv = device_empty((m, 2), torch.float64)
+    reg = device_empty((m,), torch.uint8)
+    Tc = None
+    if transformation is not None:
+        Tc = (C.c_double * 16)(*np.asarray(transformation, np.float64).reshape(16).tolist())
+    ctx.check(ctx.lib.m3d_mesh_closest(ctx.h, h, ptr(qd), n, Tc, _PATHS[path], float(r0), ptr(d2), ptr(tri),
+                                       ptr(pt), ptr(uv), ptr(reg), stream_handle()), "mesh_closest")
+    return {"d2": d2[:n].cpu().numpy(), "triangle": tri[:n].cpu().numpy(), "point": pt[:n].cpu().numpy(),
+            "uv": uv[:n].cpu().numpy(), "region": reg[:n].cpu().numpy()}
+
+
+class RaycastingScene:
+    """Open3D ``t.geometry.RaycastingScene`` as far as closest-point queries go.  Meshes added
+    with ``add_triangles`` are concatenated (vertex indices offset) into one mesh at the first
+    query; a query's winner is mapped back to (geometry id, triangle of that geometry)."""
+
+    INVALID_ID = INVALID_ID
+
+    def __init__(self):
+        self._meshes: list[TriangleMesh] = []
+        self._joined: TriangleMesh | None = None
+        self._first = np.zeros(1, np.int64)  # first global triangle of each geometry, then the total
+
+    def add_triangles(self, mesh, triangles=None) -> int:
+        """``add_triangles(mesh)`` or ``add_triangles(vertices, triangles)`` → the geometry id."""
+        m = mesh if isinstance(mesh, TriangleMesh) else TriangleMesh(mesh, triangles)
+        if not m.has_triangles():
+            raise ValueError("add_triangles: the mesh has no triangles")
+        self._meshes.append(m)
+        self._joined = None
+        return len(self._meshes) - 1
+
+    def _scene(self) -> TriangleMesh:
+        if not self._meshes:
+            raise ValueError("RaycastingScene: no geometry added")
+        if self._joined is None:
+            voff = np.cumsum([0] + [len(m.vertices) for m in self._meshes])
+            self._first = np.cumsum([0] + [len(m.triangles) for m in self._meshes]).astype(np.int64)
+            if len(self._meshes) == 1:
+                self._joined = self._meshes[0]
+            else:
+                v = np.vstack([m.vertices for m in self._meshes])
+                t = np.vstack([m.triangles.astype(np.int64) + o for m, o in zip(self._meshes, voff)])
+                self._joined = TriangleMesh(v, t)
+        return self._joined
+
+    def compute_closest_points(self, query_points) -> dict:
+        """→ ``points`` (n, 3), ``geometry_ids`` and ``primitive_ids`` (n,) uint32 (the triangle's
+        index within its geometry), ``primitive_uvs`` (n, 2), ``primitive_normals`` (n, 3): the unit
+        face normal of the winning triangle."""
+        scene = self._scene()
+        out = closest_points(scene, _queries(query_points))
+        tri = np.asarray(out["triangle"], np.int64)
+        hit = tri >= 0
+        safe = np.where(hit, tri, 0)
+        geo = np.searchsorted(self._first, safe, side="right") - 1
+        local = safe - self._first[geo]
+        a, b, c = (scene.vertices[scene.triangles[safe, k]] for k in range(3))
+        nrm = np.cross(b - a, c - a)
+        ln = np.linalg.norm(nrm, axis=1, keepdims=True)
+        nrm = np.divide(nrm, ln, out=np.zeros_like(nrm), where=ln > 0)
+        nrm[~hit] = 0.0
+        return {"points": out["point"],
+                "geometry_ids": np.where(hit, geo, int(INVALID_ID)).astype(np.uint32),
+                "primitive_ids": np.where(hit, local, int(INVALID_ID)).astype(np.uint32),
+                "primitive_uvs": out["uv"], "primitive_normals": nrm}
+
+    def compute_distance(self, query_points) -> np.ndarray:
+        """(n,) float64: the distance to the closest triangle, sqrt of the contract's d²."""
+        return np.sqrt(closest_points(self._scene(), _queries(query_points))["d2"])
+
+    # Open3D methods that need a ray caster, which this project does not have yet
+    def cast_rays(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.cast_rays: ray casting is not implemented")
+
+    def test_occlusions(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.test_occlusions: ray casting is not implemented")
+
+    def count_intersections(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.count_intersections: ray casting is not implemented")
+
+    def list_intersections(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.list_intersections: ray casting is not implemented")
+
+    def compute_signed_distance(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.compute_signed_distance: the sign is ray parity in "
+                                  "Open3D and needs a ray caster")
+
+    def compute_occupancy(self, *args, **kwargs):
+        raise NotImplementedError("RaycastingScene.compute_occupancy: needs a ray caster")

@@ -12,6 +12,7 @@ from __future__ import annotations
 from .colored import registration_colored_icp
 from .evaluate import (
     compute_point_cloud_distance,
+    compute_point_cloud_to_mesh_distance,
     evaluate_registration,
     get_information_matrix_from_point_clouds,
 )
@@ -42,6 +43,7 @@ __all__ = [
     "TukeyLoss",
     "compute_feature_correspondences",
     "compute_point_cloud_distance",
+    "compute_point_cloud_to_mesh_distance",
     "compute_step_transformation",
     "evaluate_inlier_ratio",
     "evaluate_inlier_ratio_fast",

@@ -1,5 +1,7 @@
 """Judging a given transform on the device: Open3D's ``evaluate_registration``,
-``get_information_matrix_from_point_clouds`` and ``PointCloud.compute_point_cloud_distance``.
+``get_information_matrix_from_point_clouds`` and ``PointCloud.compute_point_cloud_distance``, and
+the distance to a triangle mesh's SURFACE (``compute_point_cloud_to_mesh_distance``: Open3D's
+``RaycastingScene.compute_distance``) where the target is a CAD model.
 
 The three functions take what ``matcher.icp.registration_icp`` takes (Ply-likes with ``.pcd``,
 objects with ``.points``, (N, 3) arrays), pack the clouds through the drop-in cache and run
@@ -22,7 +24,7 @@ from m3d.types import RegistrationResult
 from .icp import _full_cloud
 
 __all__ = ["evaluate_registration", "get_information_matrix_from_point_clouds",
-           "compute_point_cloud_distance"]
+           "compute_point_cloud_distance", "compute_point_cloud_to_mesh_distance"]
 
 
 def _T(transformation):
@@ -90,3 +92,23 @@ def compute_point_cloud_distance(source, target, transformation=None) -> np.ndar
     out = _evaluate(src, tgt, T, _reach(sp, tp, T), nn="brute", with_correspondences=False,
                     with_distances=True)
     return np.sqrt(out.d2.cpu().numpy())
+
+
+def compute_point_cloud_to_mesh_distance(source, mesh, transformation=None) -> np.ndarray:
+    """For every point of ``source`` (moved by ``transformation`` when given) the distance to the
+    closest point on the SURFACE of ``mesh`` (an ``m3d.mesh.TriangleMesh``, or a ``(vertices,
+    triangles)`` pair) — Open3D's ``RaycastingScene.compute_distance`` on the transformed points.
+    (ns,) float64, the square root of the fp64 d² of ``m3d.mesh.closest_points``.
+
+    ``compute_point_cloud_distance`` against the mesh's vertices answers another question: on a
+    flat face made of two large triangles the nearest vertex can be far where the surface is
+    touched.  ``source`` is resolved as there (a Ply-like, an object with ``.points``, an array)."""
+    from m3d.mesh import TriangleMesh, closest_points
+
+    if not isinstance(mesh, TriangleMesh):
+        mesh = TriangleMesh(*mesh)
+    sp, _ = _full_cloud(source)
+    if len(sp) == 0:
+        return np.zeros(0)
+    T = None if transformation is None else _T(transformation)
+    return np.sqrt(closest_points(mesh, np.ascontiguousarray(sp, np.float64), T)["d2"])

@@ -62,6 +62,7 @@ typedef struct m3d_ctx m3d_ctx;
 typedef struct m3d_corrset m3d_corrset; /* packed correspondence set (RANSAC) */
 typedef struct m3d_cloud m3d_cloud;     /* packed point cloud (ICP / NN)      */
 typedef struct m3d_icp m3d_icp;         /* device-resident ICP loop state     */
+typedef struct m3d_mesh m3d_mesh;       /* triangle mesh (point-to-mesh distance) */
 
 /* ------------------------------------------------------------------ context */
 int m3d_abi_version(void);
@@ -914,6 +915,39 @@ int m3d_fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, dou
  * loop holds (the sum order's segment is a fixed fraction of it) */
 int32_t m3d_fgr_trial_batch(void);
 int32_t m3d_fgr_one_wg_rows(void);
+
+/* ------------------------------------------------------------------ point-to-mesh distance
+ * (added within ABI 13)  Open3D t.geometry.RaycastingScene.compute_closest_points /
+ * compute_distance: for every query the closest triangle of a mesh.  The contract (mesh.hip):
+ * Ericson's closest point on a triangle in fp64 in one fixed operation order, d² = the fp64
+ * squared distance to it, the winner the smallest (d², triangle index) over every usable triangle
+ * (nine finite coordinates, ab × ac not three exact zeros) whose d² is not NaN.  The brute-force
+ * path and the grid path return the same bits.
+ *
+ * m3d_mesh_create: vertices [device] nv×3 f64, triangles [device] nf×3 int32 (both copied).
+ * M3D_ERR_INVALID: an index outside [0, nv) (found on the device before a vertex is read through
+ * it), nf >= 2^26.  Synchronous. */
+int m3d_mesh_create(m3d_ctx* ctx, const double* vertices, int64_t nv, const int32_t* triangles, int64_t nf,
+                    m3d_mesh** out);
+void m3d_mesh_destroy(m3d_mesh* mesh);
+int64_t m3d_mesh_size(const m3d_mesh* mesh); /* triangles (−1: null) */
+/* xyz [device] n×3 f64 queries; T [host] 16 doubles (row-major 4×4: the query is
+ * ((T00·x + T01·y) + T02·z) + T03, …) or NULL.  path: 0 automatic, 1 brute force, 2 grid.  r0: the
+ * grid path's first radius (<= 0: one cell); it changes the rounds, never the result.  Outputs
+ * [device], each may be NULL: d2_out n f64, tri_out n int32, point_out n×3 f64, uv_out n×2 f64
+ * (v, w: point ≈ (1−v−w)·a + v·b + w·c), region_out n uint8 (0 1 2: vertex a b c; 3 4 5: edge ab ac
+ * bc; 6: face).  A query no triangle answers (a NaN query): d² +inf, triangle −1, NaN point and uv,
+ * region 255.  M3D_ERR_INVALID: the mesh has no usable triangle.  Synchronous. */
+int m3d_mesh_closest(m3d_ctx* ctx, m3d_mesh* mesh, const double* xyz, int64_t n, const double* T, int32_t path,
+                     double r0, double* d2_out, int32_t* tri_out, double* point_out, double* uv_out,
+                     uint8_t* region_out, void* stream);
+/* out4 [host]: the grid's cells and references (0 0 before the first grid query), the cell-size
+ * doublings of its build, the ladder rounds of the last call (0: it ran brute force). */
+int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4);
+/* constants of the library: triangles per LDS tile of the brute-force kernel; the triangle count up
+ * to which path 0 takes it */
+int32_t m3d_mesh_brute_tile(void);
+int32_t m3d_mesh_auto_brute_max(void);
 
 /* ------------------------------------------------------------------ test hooks
  * Host-compiled copy of the device 3×3 linear algebra (same source), for CPU-side unit tests
