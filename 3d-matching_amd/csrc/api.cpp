@@ -1983,127 +1983,75 @@ int m3d_evaluate_registration(m3d_ctx* ctx, const m3d_cloud* src, const m3d_clou
   return M3D_OK;
 }
 
-// ------------------------------------------------------------------------------- Generalized ICP
-// gicp.hip.  The loop object is the point-to-plane loop's (state, NN scan, solve); the
-// covariances and the terms pass's partials live in one block of their own beside it.
-int m3d_covariances_from_normals(m3d_ctx* ctx, const double* normals, int64_t n, double epsilon,
-                                 double* cov_out, void* stream) {
-  if (!ctx) return M3D_ERR_INVALID;
-  CHECK_ARG(ctx, n >= 0 && (n == 0 || (normals && cov_out)), "invalid arguments");
-  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
-  hipSetDevice(ctx->device);
-  HIPX(ctx, launch_cov_from_normals(normals, n, epsilon, cov_out, 9, S(stream)));
-  return M3D_OK;
-}
-
+// ------------------------------------------------------------------------------- side terms calls
+// The entry points whose loop runs a terms pass of its own (terms_pass.h): Generalized ICP, the
+// robust kernels, Colored ICP.  Two shapes — one evaluation (side_terms_once) and the whole
+// registration (side_terms_run) — around what an estimator adds: a call object with
+//   before(ctx, src, tgt, max_dist, st)   work enqueued before the loop object exists
+//   setup(loop, st)                       its arrays allocated and filled
+//   pass(loop, sums, with_defer, st)      its terms pass and the reduce
+extern "C++" {
 namespace {
-// the covariance arrays of one Generalized-ICP call: the source's in the loop's Morton slot order
-// (rotated in place by every evaluation), the target's in target index order, 6 doubles per point
-struct GicpArrays {
+// The arrays of one side-terms call beside its loop object, one block from the block cache: the
+// estimator's own (its call object adds them to the Carve) and the terms pass's block partials
+struct TermArrays {
   void* block = nullptr;
-  double* cov_s = nullptr;
-  double* cov_t = nullptr;
-  double* partials = nullptr;
+  double* partials = nullptr;  // side_terms_blocks(ns) × kTermSlots
   m3d_ctx* ctx = nullptr;
   hipStream_t st = nullptr;
   // back to the block cache, marked after the work this call enqueued on its stream
-  ~GicpArrays() {
+  ~TermArrays() {
     if (block == nullptr) return;
     ctx_touch(ctx, st);
     ReleaseScope rs(ctx, ctx->id);
     block_release(block);
   }
+  int alloc(m3d_ctx* c, hipStream_t s, Carve& cc, int64_t ns, const char* what) {
+    ctx = c;
+    st = s;
+    cc.add(&partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(side_terms_blocks(ns), 1));
+    size_t bytes = 0;
+    if (cc.alloc(&block, &bytes, st) != hipSuccess)
+      return m3d_fail(ctx, M3D_ERR_OOM, std::string("device allocation failed (") + what + ")");
+    return M3D_OK;
+  }
+  int before(m3d_ctx*, const m3d_cloud*, const m3d_cloud*, double, hipStream_t) { return M3D_OK; }
 };
 
-int gicp_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
-               const double* tgt_cov, double max_dist, int32_t nn_method, double epsilon) {
-  CHECK_ARG(ctx, src && tgt, "invalid arguments");
-  CHECK_ARG(ctx, max_dist > 0.0, "Invalid max_correspondence_distance.");
-  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
-  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
-  CHECK_ARG(ctx, src_cov != nullptr || src->nrm64 != nullptr || src->n == 0,
-            "Generalized ICP: the source has neither covariances nor normals");
-  CHECK_ARG(ctx, tgt_cov != nullptr || tgt->nrm64 != nullptr || tgt->n == 0,
-            "Generalized ICP: the target has neither covariances nor normals");
-  return M3D_OK;
-}
-
-// allocate the arrays and (re-)initialise the covariances: the caller's (its order → slot order
-// for the source), else from the normals — the Morton copy's are in slot order already
-int gicp_setup(m3d_icp* s, const double* src_cov, const double* tgt_cov, double epsilon, hipStream_t st,
-               GicpArrays* ga) {
-  m3d_ctx* ctx = s->ctx;
-  const int64_t ns = s->src->n, nt = s->tgt->n;
-  ga->ctx = ctx;
-  ga->st = st;
-  Carve cc;
-  cc.add(&ga->cov_s, 6 * (size_t)ns);
-  cc.add(&ga->cov_t, 6 * (size_t)nt);
-  cc.add(&ga->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(gicp_blocks(ns), 1));
-  size_t bytes = 0;
-  if (cc.alloc(&ga->block, &bytes, st) != hipSuccess)
-    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (Generalized ICP covariances)");
-  HIPX(ctx, src_cov != nullptr ? launch_cov_pack(src_cov, s->src->slot, ns, ga->cov_s, st)
-                               : launch_cov_from_normals(s->src->nrm64, ns, epsilon, ga->cov_s, 6, st));
-  HIPX(ctx, tgt_cov != nullptr ? launch_cov_pack(tgt_cov, nullptr, nt, ga->cov_t, st)
-                               : launch_cov_from_normals(s->tgt->nrm64, nt, epsilon, ga->cov_t, 6, st));
-  return M3D_OK;
-}
-
-// the loop object of a Generalized-ICP call: created as a point-to-point loop (no demand on the
-// target's normals — the covariances may be the caller's), then switched to the point-to-plane
-// estimator, whose state and solve the plane-to-plane sums feed (same slot layout)
-int gicp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist, double rel_fit,
-                double rel_rmse, int32_t max_iteration, int32_t nn_method, m3d_icp** out) {
-  m3d_icp_params p{rel_fit, rel_rmse, max_iteration, M3D_EST_POINT_TO_POINT, nn_method, 0};
+// the loop object of a side-terms call: created with p's estimation, then switched to the
+// point-to-plane estimator, whose state and solve the pass's sums feed (same slot layout)
+int side_loop_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist,
+                     const m3d_icp_params& p, m3d_icp** out) {
   const int rc = icp_create(ctx, src, tgt, max_dist, &p, out, true);
   if (!rc) (*out)->params.estimation = M3D_EST_POINT_TO_PLANE;
   return rc;
 }
-}  // namespace
 
-extern "C++" {
-namespace {
-// a caller's robust kernel: a known kind, and a finite k > 0 for the kinds that read it
-int robust_check(m3d_ctx* ctx, const m3d_robust_kernel* kernel) {
-  CHECK_ARG(ctx, kernel != nullptr, "null robust kernel");
-  CHECK_ARG(ctx, kernel->kind >= M3D_KERNEL_L2 && kernel->kind <= M3D_KERNEL_TUKEY, "unknown robust kernel");
-  CHECK_ARG(ctx, kernel->kind == M3D_KERNEL_L2 || kernel->kind == M3D_KERNEL_L1 ||
-                     (std::isfinite(kernel->k) && kernel->k > 0.0),
-            "robust kernel: k must be finite and > 0");
-  return M3D_OK;
-}
-
-// One Generalized-ICP evaluation; kernel null: the plane-to-plane terms of gicp.hip, else
-// robust.hip's with that (checked) kernel
-int gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
-               const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method, double epsilon,
-               const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx, hipStream_t st) {
-  CHECK_ARG(ctx, sums_out != nullptr, "null output");
-  int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, nn_method, epsilon);
-  if (rc) return rc;
+// One evaluation at T_host: sums_out[0 .. 30) (non-null: the entry point's check) and the
+// correspondences.  pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and whatever
+// the estimator moves with them
+template <class Call>
+int side_terms_once(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* T_host, double max_dist,
+                    int32_t estimation, int32_t nn_method, Call& call, double* sums_out, int32_t* corr_idx,
+                    hipStream_t st) {
   for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
-  const int64_t ns = src->n, nt = tgt->n;
-  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
+  if (src->n == 0 || tgt->n == 0) {  // nothing to search: every source (if any) is unmatched, no sums
     hipSetDevice(ctx->device);
-    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
+    hipError_t e = launch_eval_fill(src->n, corr_idx, nullptr, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
     return M3D_OK;
   }
-  ScopedLoop s;
-  rc = gicp_create(ctx, src, tgt, max_dist, 1e-6, 1e-6, 0, nn_method, &s.s);
+  int rc = call.before(ctx, src, tgt, max_dist, st);
   if (rc) return rc;
-  GicpArrays ga;
-  rc = gicp_setup(s, src_cov, tgt_cov, epsilon, st, &ga);
+  ScopedLoop s;
+  rc = side_loop_create(ctx, src, tgt, max_dist, m3d_icp_params{1e-6, 1e-6, 0, estimation, nn_method, 0}, &s.s);
+  if (!rc) rc = call.setup(s, st);
   if (rc) return rc;
   double sums[kTermSlots] = {};
-  // pcd = source; if (!T.isIdentity()) pcd.Transform(T) — points and covariances
   rc = one_evaluation(s, T_host, true, [&](double* pin) {
     KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-    return kernel == nullptr
-               ? launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, pin, true, st)
-               : launch_robust_gicp_terms(s, kernel->kind, kernel->k, ga.cov_s, ga.cov_t, ga.partials, pin, true, st);
+    return call.pass(s, pin, true, st);
   }, corr_idx, kTermSlots, sums, st);
   if (rc) return rc;
   for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
@@ -2136,39 +2084,31 @@ int run_terms_loop(m3d_icp* s, int32_t max_iteration, Terms terms, m3d_icp_resul
   return rc;
 }
 
-int gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
-             const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
-             const m3d_robust_kernel* kernel, m3d_icp_result* out, int32_t* corr_idx, void* stream) {
-  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
-  int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, params->nn_method, params->epsilon);
+// The whole registration from init: p = the loop's parameters (its estimation: side_loop_create)
+template <class Call>
+int side_terms_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* init, double max_dist,
+                   const m3d_icp_params& p, Call& call, m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  hipStream_t st = S(stream);
+  int rc = call.before(ctx, src, tgt, max_dist, st);
   if (rc) return rc;
   ScopedLoop s;
-  rc = gicp_create(ctx, src, tgt, max_dist, params->relative_fitness, params->relative_rmse,
-                   params->max_iteration, params->nn_method, &s.s);
-  if (rc) return rc;
-  hipStream_t st = S(stream);
-  GicpArrays ga;
-  rc = gicp_setup(s, src_cov, tgt_cov, params->epsilon, st, &ga);
+  rc = side_loop_create(ctx, src, tgt, max_dist, p, &s.s);
+  if (!rc) rc = call.setup(s, st);
   if (!rc) rc = m3d_icp_reset(s, init, stream);
   if (!rc)
-    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
-      return kernel == nullptr
-                 ? launch_gicp_terms(s, ga.cov_s, ga.cov_t, ga.partials, sums, false, st)
-                 : launch_robust_gicp_terms(s, kernel->kind, kernel->k, ga.cov_s, ga.cov_t, ga.partials, sums, false, st);
-    }, out, corr_idx, st);
+    rc = run_terms_loop(s, p.max_iteration, [&](double* sums) { return call.pass(s, sums, false, st); }, out,
+                        corr_idx, st);
   if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
   return rc;
 }
 
-// the block partials of a robust point-to-plane pass (GicpArrays without covariances)
-int robust_plane_setup(m3d_icp* s, hipStream_t st, GicpArrays* ga) {
-  ga->ctx = s->ctx;
-  ga->st = st;
-  Carve cc;
-  cc.add(&ga->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(robust_blocks(s->src->n), 1));
-  size_t bytes = 0;
-  if (cc.alloc(&ga->block, &bytes, st) != hipSuccess)
-    return m3d_fail(s->ctx, M3D_ERR_OOM, "device allocation failed (robust point-to-plane partials)");
+// a caller's robust kernel: a known kind, and a finite k > 0 for the kinds that read it
+int robust_check(m3d_ctx* ctx, const m3d_robust_kernel* kernel) {
+  CHECK_ARG(ctx, kernel != nullptr, "null robust kernel");
+  CHECK_ARG(ctx, kernel->kind >= M3D_KERNEL_L2 && kernel->kind <= M3D_KERNEL_TUKEY, "unknown robust kernel");
+  CHECK_ARG(ctx, kernel->kind == M3D_KERNEL_L2 || kernel->kind == M3D_KERNEL_L1 ||
+                     (std::isfinite(kernel->k) && kernel->k > 0.0),
+            "robust kernel: k must be finite and > 0");
   return M3D_OK;
 }
 
@@ -2176,8 +2116,104 @@ int robust_plane_setup(m3d_icp* s, hipStream_t st, GicpArrays* ga) {
 const m3d_robust_kernel* non_l2(const m3d_robust_kernel* kernel) {
   return kernel != nullptr && kernel->kind != M3D_KERNEL_L2 ? kernel : nullptr;
 }
+
+// ------------------------------------------------------------------------------- Generalized ICP
+// gicp.hip.  The loop object is created as a point-to-point loop: no demand on the target's
+// normals — the covariances may be the caller's.
+int gicp_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+               const double* tgt_cov, double max_dist, int32_t nn_method, double epsilon) {
+  CHECK_ARG(ctx, src && tgt, "invalid arguments");
+  CHECK_ARG(ctx, max_dist > 0.0, "Invalid max_correspondence_distance.");
+  CHECK_ARG(ctx, nn_method == M3D_NN_BRUTE || nn_method == M3D_NN_GRID, "unknown nn_method");
+  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
+  CHECK_ARG(ctx, src_cov != nullptr || src->nrm64 != nullptr || src->n == 0,
+            "Generalized ICP: the source has neither covariances nor normals");
+  CHECK_ARG(ctx, tgt_cov != nullptr || tgt->nrm64 != nullptr || tgt->n == 0,
+            "Generalized ICP: the target has neither covariances nor normals");
+  return M3D_OK;
+}
+
+// The covariance arrays of one Generalized-ICP call, 6 doubles per point: the source's in the
+// loop's Morton slot order (rotated in place by every evaluation), the target's in target index
+// order.  kernel null: the plane-to-plane terms of gicp.hip, else robust.hip's with that (checked)
+// kernel
+struct GicpCall : TermArrays {
+  const double *src_cov, *tgt_cov;
+  double epsilon;
+  const m3d_robust_kernel* kernel;
+  double* cov_s = nullptr;
+  double* cov_t = nullptr;
+  GicpCall(const double* sc, const double* tc, double eps, const m3d_robust_kernel* k)
+      : src_cov(sc), tgt_cov(tc), epsilon(eps), kernel(k) {}
+  // allocate the arrays and initialise the covariances: the caller's (its order → slot order for
+  // the source), else from the normals — the Morton copy's are in slot order already
+  int setup(m3d_icp* s, hipStream_t st) {
+    const int64_t ns = s->src->n, nt = s->tgt->n;
+    Carve cc;
+    cc.add(&cov_s, 6 * (size_t)ns);
+    cc.add(&cov_t, 6 * (size_t)nt);
+    const int rc = alloc(s->ctx, st, cc, ns, "Generalized ICP covariances");
+    if (rc) return rc;
+    HIPX(ctx, src_cov != nullptr ? launch_cov_pack(src_cov, s->src->slot, ns, cov_s, st)
+                                 : launch_cov_from_normals(s->src->nrm64, ns, epsilon, cov_s, 6, st));
+    HIPX(ctx, tgt_cov != nullptr ? launch_cov_pack(tgt_cov, nullptr, nt, cov_t, st)
+                                 : launch_cov_from_normals(s->tgt->nrm64, nt, epsilon, cov_t, 6, st));
+    return M3D_OK;
+  }
+  hipError_t pass(const m3d_icp* s, double* sums, bool with_defer, hipStream_t st) const {
+    return kernel == nullptr
+               ? launch_gicp_terms(s, cov_s, cov_t, partials, sums, with_defer, st)
+               : launch_robust_terms(s, kernel->kind, kernel->k, cov_s, cov_t, partials, sums, with_defer, st);
+  }
+};
+
+int gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+               const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method, double epsilon,
+               const m3d_robust_kernel* kernel, double* sums_out, int32_t* corr_idx, hipStream_t st) {
+  CHECK_ARG(ctx, sums_out != nullptr, "null output");
+  const int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, nn_method, epsilon);
+  if (rc) return rc;
+  GicpCall call(src_cov, tgt_cov, epsilon, kernel);
+  return side_terms_once(ctx, src, tgt, T_host, max_dist, M3D_EST_POINT_TO_POINT, nn_method, call, sums_out,
+                         corr_idx, st);
+}
+
+int gicp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
+             const double* tgt_cov, const double* init, double max_dist, const m3d_gicp_params* params,
+             const m3d_robust_kernel* kernel, m3d_icp_result* out, int32_t* corr_idx, void* stream) {
+  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
+  const int rc = gicp_check(ctx, src, tgt, src_cov, tgt_cov, max_dist, params->nn_method, params->epsilon);
+  if (rc) return rc;
+  GicpCall call(src_cov, tgt_cov, params->epsilon, kernel);
+  const m3d_icp_params p{params->relative_fitness, params->relative_rmse, params->max_iteration,
+                         M3D_EST_POINT_TO_POINT,   params->nn_method,     0};
+  return side_terms_run(ctx, src, tgt, init, max_dist, p, call, out, corr_idx, stream);
+}
+
+// robust point-to-plane (robust.hip): the block partials are all it needs
+struct RobustPlaneCall : TermArrays {
+  const m3d_robust_kernel* kernel;
+  explicit RobustPlaneCall(const m3d_robust_kernel* k) : kernel(k) {}
+  int setup(m3d_icp* s, hipStream_t st) {
+    Carve cc;
+    return alloc(s->ctx, st, cc, s->src->n, "robust point-to-plane partials");
+  }
+  hipError_t pass(const m3d_icp* s, double* sums, bool with_defer, hipStream_t st) const {
+    return launch_robust_terms(s, kernel->kind, kernel->k, nullptr, nullptr, partials, sums, with_defer, st);
+  }
+};
 }  // namespace
 }  // extern "C++"
+
+int m3d_covariances_from_normals(m3d_ctx* ctx, const double* normals, int64_t n, double epsilon,
+                                 double* cov_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, n >= 0 && (n == 0 || (normals && cov_out)), "invalid arguments");
+  CHECK_ARG(ctx, epsilon > 0.0, "epsilon must be > 0");
+  hipSetDevice(ctx->device);
+  HIPX(ctx, launch_cov_from_normals(normals, n, epsilon, cov_out, 9, S(stream)));
+  return M3D_OK;
+}
 
 int m3d_gicp_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_cov,
                    const double* tgt_cov, const double* T_host, double max_dist, int32_t nn_method,
@@ -2239,31 +2275,9 @@ int m3d_robust_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, c
   CHECK_ARG(ctx, tgt->nrm64 != nullptr || tgt->n == 0,
             "TransformationEstimationPointToPlane requires pre-computed normal vectors for target "
             "PointCloud.");
-  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
-  hipStream_t st = S(stream);
-  const int64_t ns = src->n, nt = tgt->n;
-  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
-    hipSetDevice(ctx->device);
-    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-    return M3D_OK;
-  }
-  m3d_icp_params p{1e-6, 1e-6, 0, M3D_EST_POINT_TO_PLANE, nn_method, 0};
-  ScopedLoop s;
-  rc = icp_create(ctx, src, tgt, max_dist, &p, &s.s, true);
-  if (rc) return rc;
-  GicpArrays ga;
-  rc = robust_plane_setup(s, st, &ga);
-  if (rc) return rc;
-  double sums[kTermSlots] = {};
-  rc = one_evaluation(s, T_host, true, [&](double* pin) {
-    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-    return launch_robust_plane_terms(s, kernel->kind, kernel->k, ga.partials, pin, true, st);
-  }, corr_idx, kTermSlots, sums, st);
-  if (rc) return rc;
-  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
-  return M3D_OK;
+  RobustPlaneCall call(kernel);
+  return side_terms_once(ctx, src, tgt, T_host, max_dist, M3D_EST_POINT_TO_PLANE, nn_method, call, sums_out,
+                         corr_idx, S(stream));
 }
 
 int m3d_robust_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* init,
@@ -2276,19 +2290,8 @@ int m3d_robust_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt,
   if (rc) return rc;
   CHECK_ARG(ctx, params->estimation == M3D_EST_POINT_TO_PLANE,
             "a robust kernel needs the point-to-plane estimation (TransformationEstimationPointToPoint takes none)");
-  ScopedLoop s;
-  rc = icp_create(ctx, src, tgt, max_dist, params, &s.s, true);
-  if (rc) return rc;
-  hipStream_t st = S(stream);
-  GicpArrays ga;
-  rc = robust_plane_setup(s, st, &ga);
-  if (!rc) rc = m3d_icp_reset(s, init, stream);
-  if (!rc)
-    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
-      return launch_robust_plane_terms(s, kernel->kind, kernel->k, ga.partials, sums, false, st);
-    }, out, corr_idx, st);
-  if (rc) (void)hipStreamSynchronize(st);  // the partials go back to the block cache idle
-  return rc;
+  RobustPlaneCall call(kernel);
+  return side_terms_run(ctx, src, tgt, init, max_dist, *params, call, out, corr_idx, stream);
 }
 
 // ------------------------------------------------------------------------------- preprocessing
@@ -2416,22 +2419,6 @@ int m3d_hybrid_search(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, int32
 // one block of their own beside it, as Generalized ICP's covariances do.
 extern "C++" {
 namespace {
-struct ColoredArrays {
-  void* block = nullptr;
-  double* rec_t = nullptr;  // nt × 4: gradient, intensity
-  double* is_s = nullptr;   // ns, slot order
-  double* partials = nullptr;
-  m3d_ctx* ctx = nullptr;
-  hipStream_t st = nullptr;
-  // back to the block cache, marked after the work this call enqueued on its stream
-  ~ColoredArrays() {
-    if (block == nullptr) return;
-    ctx_touch(ctx, st);
-    ReleaseScope rs(ctx, ctx->id);
-    block_release(block);
-  }
-};
-
 constexpr int kColoredMaxNn = 30;  // KDTreeSearchParamHybrid(2·max_dist, 30)
 
 // the gradients of cloud c with the given normals and colours: rec (n × 4) and / or out3 (n × 3)
@@ -2460,36 +2447,39 @@ int colored_check(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, cons
   return kernel != nullptr ? robust_check(ctx, kernel) : M3D_OK;
 }
 
-// allocate the arrays; the target's records from the caller's gradients, else computed
-int colored_setup_target(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* tgt_colors,
-                         const double* tgt_gradient, double max_dist, hipStream_t st, ColoredArrays* ca) {
-  ca->ctx = ctx;
-  ca->st = st;
-  Carve cc;
-  cc.add(&ca->rec_t, 4 * (size_t)tgt->n);
-  cc.add(&ca->is_s, (size_t)src->n);
-  cc.add(&ca->partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(colored_blocks(src->n), 1));
-  size_t bytes = 0;
-  if (cc.alloc(&ca->block, &bytes, st) != hipSuccess)
-    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (Colored ICP arrays)");
-  if (tgt_gradient != nullptr) {
-    HIPX(ctx, launch_color_rec_pack(tgt_gradient, tgt_colors, tgt->n, ca->rec_t, st));
+// The arrays of one Colored-ICP call: the target's records (from the caller's gradients, else
+// computed) are allocated and filled before the loop object exists, the source's intensities
+// gathered into the loop's slot order once it does.  kernel null: L2 through the same pass
+struct ColoredCall : TermArrays {
+  const double *src_colors, *tgt_colors, *tgt_gradient;
+  double lambda;
+  const m3d_robust_kernel* kernel;
+  double* rec_t = nullptr;  // nt × 4: gradient, intensity
+  double* is_s = nullptr;   // ns, slot order
+  ColoredCall(const double* sc, const double* tc, const double* tg, double l, const m3d_robust_kernel* k)
+      : src_colors(sc), tgt_colors(tc), tgt_gradient(tg), lambda(l), kernel(k) {}
+  int before(m3d_ctx* c, const m3d_cloud* src, const m3d_cloud* tgt, double max_dist, hipStream_t st) {
+    hipSetDevice(c->device);
+    Carve cc;
+    cc.add(&rec_t, 4 * (size_t)tgt->n);
+    cc.add(&is_s, (size_t)src->n);
+    const int rc = alloc(c, st, cc, src->n, "Colored ICP arrays");
+    if (rc) return rc;
+    if (tgt_gradient != nullptr) {
+      HIPX(ctx, launch_color_rec_pack(tgt_gradient, tgt_colors, tgt->n, rec_t, st));
+      return M3D_OK;
+    }
+    return color_gradients(ctx, tgt, tgt_colors, 2.0 * max_dist, kColoredMaxNn, rec_t, nullptr, st);
+  }
+  int setup(m3d_icp* s, hipStream_t st) {
+    HIPX(ctx, launch_intensity_pack(src_colors, s->src->slot, s->src->n, is_s, st));
     return M3D_OK;
   }
-  return color_gradients(ctx, tgt, tgt_colors, 2.0 * max_dist, kColoredMaxNn, ca->rec_t, nullptr, st);
-}
-
-// the loop object of a Colored-ICP call (the point-to-plane loop's) and the source's intensities
-// gathered into its slot order
-int colored_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
-                   double max_dist, double rel_fit, double rel_rmse, int32_t max_iteration, int32_t nn_method,
-                   hipStream_t st, ColoredArrays* ca, m3d_icp** out) {
-  m3d_icp_params p{rel_fit, rel_rmse, max_iteration, M3D_EST_POINT_TO_PLANE, nn_method, 0};
-  const int rc = icp_create(ctx, src, tgt, max_dist, &p, out, true);
-  if (rc) return rc;
-  HIPX(ctx, launch_intensity_pack(src_colors, (*out)->src->slot, (*out)->src->n, ca->is_s, st));
-  return M3D_OK;
-}
+  hipError_t pass(const m3d_icp* s, double* sums, bool with_defer, hipStream_t st) const {
+    return launch_colored_terms(s, rec_t, is_s, lambda, kernel != nullptr ? kernel->kind : M3D_KERNEL_L2,
+                                kernel != nullptr ? kernel->k : 0.0, partials, sums, with_defer, st);
+  }
+};
 }  // namespace
 }  // extern "C++"
 
@@ -2519,32 +2509,9 @@ int m3d_colored_terms(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, 
   CHECK_ARG(ctx, sums_out != nullptr, "null output");
   int rc = colored_check(ctx, src, tgt, src_colors, tgt_colors, max_dist, nn_method, lambda_geometric, kernel);
   if (rc) return rc;
-  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
-  const int64_t ns = src->n, nt = tgt->n;
-  if (ns == 0 || nt == 0) {  // nothing to search: every source (if any) is unmatched, no sums
-    hipSetDevice(ctx->device);
-    hipError_t e = launch_eval_fill(ns, corr_idx, nullptr, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
-    return M3D_OK;
-  }
-  hipSetDevice(ctx->device);
-  ColoredArrays ca;
-  rc = colored_setup_target(ctx, src, tgt, tgt_colors, tgt_gradient, max_dist, st, &ca);
-  if (rc) return rc;
-  ScopedLoop s;
-  rc = colored_create(ctx, src, tgt, src_colors, max_dist, 1e-6, 1e-6, 0, nn_method, st, &ca, &s.s);
-  if (rc) return rc;
-  const int32_t kind = kernel != nullptr ? kernel->kind : M3D_KERNEL_L2;
-  const double kk = kernel != nullptr ? kernel->k : 0.0;
-  double sums[kTermSlots] = {};
-  rc = one_evaluation(s, T_host, true, [&](double* pin) {
-    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
-    return launch_colored_terms(s, ca.rec_t, ca.is_s, lambda_geometric, kind, kk, ca.partials, pin, true, st);
-  }, corr_idx, kTermSlots, sums, st);
-  if (rc) return rc;
-  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
-  return M3D_OK;
+  ColoredCall call(src_colors, tgt_colors, tgt_gradient, lambda_geometric, kernel);
+  return side_terms_once(ctx, src, tgt, T_host, max_dist, M3D_EST_POINT_TO_PLANE, nn_method, call, sums_out,
+                         corr_idx, st);
 }
 
 int m3d_colored_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, const double* src_colors,
@@ -2559,27 +2526,10 @@ int m3d_colored_icp_run(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt
                          params->lambda_geometric, kernel);
   if (rc) return rc;
   CHECK_ARG(ctx, params->max_iteration >= 0, "max_iteration must be >= 0");
-  hipSetDevice(ctx->device);
-  ColoredArrays ca;
-  rc = colored_setup_target(ctx, src, tgt, tgt_colors, tgt_gradient, max_dist, st, &ca);
-  if (rc) return rc;
-  ScopedLoop s;
-  rc = colored_create(ctx, src, tgt, src_colors, max_dist, params->relative_fitness, params->relative_rmse,
-                      params->max_iteration, params->nn_method, st, &ca, &s.s);
-  if (rc) {
-    (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
-    return rc;
-  }
-  const int32_t kind = kernel != nullptr ? kernel->kind : M3D_KERNEL_L2;
-  const double kk = kernel != nullptr ? kernel->k : 0.0;
-  const double lambda = params->lambda_geometric;
-  rc = m3d_icp_reset(s, init, stream);
-  if (!rc)
-    rc = run_terms_loop(s, params->max_iteration, [&](double* sums) {
-      return launch_colored_terms(s, ca.rec_t, ca.is_s, lambda, kind, kk, ca.partials, sums, false, st);
-    }, out, corr_idx, st);
-  if (rc) (void)hipStreamSynchronize(st);  // the arrays go back to the block cache idle
-  return rc;
+  ColoredCall call(src_colors, tgt_colors, tgt_gradient, params->lambda_geometric, kernel);
+  const m3d_icp_params p{params->relative_fitness, params->relative_rmse, params->max_iteration,
+                         M3D_EST_POINT_TO_PLANE,   params->nn_method,     0};
+  return side_terms_run(ctx, src, tgt, init, max_dist, p, call, out, corr_idx, stream);
 }
 
 int m3d_estimate_normals(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, int32_t max_nn,

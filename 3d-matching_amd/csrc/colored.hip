@@ -1,9 +1,9 @@
 // colored.hip — Colored ICP (Open3D 0.19 ColoredICP.cpp; Park, Zhou, Koltun 2017): the colour
-// gradient of every target point, built once per call, and the two-row terms pass that replaces
-// icp.hip's point-to-plane terms in the RegistrationICP loop.  The NN scan before it, the solve
-// after it (icp.hip solve_state, the point-to-plane slot layout), fitness, the geometric
-// inlier_rmse and the convergence rule are the loop's own — three launches per iteration (scan,
-// terms + reduce, solve), as gicp.hip's and robust.hip's.
+// gradient of every target point, built once per call, and the two-row estimator (ColoredEst) of
+// the side terms pass (terms_pass.h) that replaces icp.hip's point-to-plane terms in the
+// RegistrationICP loop.  The NN scan before it, the solve after it (icp.hip solve_state, the
+// point-to-plane slot layout), fitness, the geometric inlier_rmse and the convergence rule are
+// the loop's own, as for gicp.hip and robust.hip.
 //
 // Intensity of a colour (r, g, b):  I = ((r + g) + b) / 3.0.
 //
@@ -34,14 +34,10 @@
 //           M = I − nt·ntᵀ (M_aa = 1.0 − n_a·n_a, M_ac = −(n_a·n_c)),
 //           m_c = −((g0·M_0c + g1·M_1c) + g2·M_2c)   (ditM = −ditᵀ·M),
 //           r1 = sp·(is − is0),  J1 = [sp·(vs × m) | sp·m]
-//   each row added by robust_rows.h add_row with its own weight w(r) (robust.hip's table; no
-//   kernel or L2: 1): (w·J_a)·J_c, (w·J_a)·r and the unweighted r·r into slot 27; slot 28 += 1,
-//   slot 29 += d² (the loop's).  Slots: 0..20 JᵀJ (upper, row-major), 21..26 Jᵀr, 27 Σr², 28
-//   count, 29 Σd² — the point-to-plane layout, so launch_icp_solve consumes the sums unchanged.
-//
-// Order of summation: the loop's fixed order (nnkey.h block_partial per block of 256 consecutive
-// slots, launch_reduce over the block partials) — two runs, and the brute-force and grid scans,
-// give the same bits.  No floating-point atomics anywhere in this file.
+//   each row added by terms_pass.h add_row with its own weight w(r) (robust.hip's table; no
+//   kernel or L2: 1): (w·J_a)·J_c, (w·J_a)·r and the unweighted r·r into slot 27.  Count, Σd², the
+//   slots and the order of summation: terms_pass.h.  No floating-point atomics anywhere in this
+//   file.
 //
 // Bytes per source the terms pass must move: its point read and written (24 + 24), key,
 // runner-up and correspondence (8 + 4 + 4), its intensity (8), and the gathered winner's point,
@@ -50,13 +46,11 @@
 #include "knn_wave.h"
 #include "m3d_internal.h"
 #include "nnkey.h"
-#include "robust_rows.h"
+#include "terms_pass.h"
 
 namespace m3d {
 
 namespace {
-
-constexpr int kColoredBlock = 256;
 
 __device__ __forceinline__ double intensity_of(const double* __restrict__ c) { return ((c[0] + c[1]) + c[2]) / 3.0; }
 
@@ -171,27 +165,16 @@ __global__ __launch_bounds__(256) void intensity_pack_kernel(const double* __res
   out[k] = intensity_of(colors + 3 * (slot != nullptr ? (int64_t)slot[k] : k));
 }
 
-// ns > 0 and nt > 0 (the launcher keeps the empty cases away: no slot 0, no target 0 to load)
+// the two weighted rows of a matched pair (the file header's formulas); sg = sqrt(λ), sp = sqrt(1 − λ)
 template <int K>
-__global__ __launch_bounds__(kColoredBlock) void colored_terms_kernel(
-    double* __restrict__ pcd64, const float4* __restrict__ src32, int64_t ns, const double* __restrict__ tgt64,
-    const double* __restrict__ nrm_t, const double* __restrict__ rec_t, const double* __restrict__ is_s, int64_t nt,
-    GridDev g, const IcpState* __restrict__ s, const int64_t* __restrict__ keys, const uint32_t* __restrict__ near2,
-    int32_t* __restrict__ corr, double sg, double sp, double kk, double* __restrict__ partials) {
-  if (s->done) return;
-  const SlotWinner sw = slot_winner((int64_t)blockIdx.x * kColoredBlock + threadIdx.x, pcd64, src32, ns, tgt64, nt,
-                                    g, s, keys, near2);
-  const double(&Q)[3] = sw.Q;
-  if (sw.valid) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) pcd64[3 * sw.i + k] = Q[k];
-    corr[sw.i] = sw.hit ? (int32_t)sw.gj : -1;
-  }
-  double v[kRobustUsed];
-#pragma unroll
-  for (int k = 0; k < kRobustUsed; ++k) v[k] = 0.0;
-  if (sw.hit) {
-    const double* tq = tgt64 + 3 * sw.gj;
+struct ColoredEst : NoSlotState {
+  const double* __restrict__ nrm_t;
+  const double* __restrict__ rec_t;
+  const double* __restrict__ is_s;
+  double sg, sp, kk;
+  __device__ __forceinline__ void rows(double (&v)[kTermsUsed], const SlotWinner& sw, const double* __restrict__ tq,
+                                       const Slot&) const {
+    const double(&Q)[3] = sw.Q;
     const double* tn = nrm_t + 3 * sw.gj;
     const double* tr = rec_t + 4 * sw.gj;
     const double is = is_s[sw.i];
@@ -219,15 +202,10 @@ __global__ __launch_bounds__(kColoredBlock) void colored_terms_kernel(
                            sp * m0,                sp * m1,                sp * m2};
       add_row(v, J, r1, robust_weight<K>(r1, kk));
     }
-    v[28] = 1.0;
-    v[29] = sw.d;
   }
-  block_partial<kTermSlots, kRobustUsed, kColoredBlock>(v, partials);
-}
+};
 
 }  // namespace
-
-int64_t colored_blocks(int64_t ns) { return ns > 0 ? (ns + kColoredBlock - 1) / kColoredBlock : 0; }
 
 // The colour gradients of every point of c (its normals nrm, colours n × 3): g / gf / hfine as
 // hybrid_search takes them, 1 ≤ k ≤ 64.  rec (n × 4: gradient, intensity) and out3 (n × 3): either
@@ -264,23 +242,19 @@ hipError_t launch_intensity_pack(const double* colors, const int32_t* slot, int6
   return hipGetLastError();
 }
 
-// The colored terms of the loop's current evaluation (its NN scan must have been enqueued on st)
-// and their reduction into sums, as launch_robust_plane_terms.  rec_t: the target's records in
-// index order; is_s: the source's intensities in slot order; kind: a checked M3D_KERNEL_* (L2: unit
-// weights); partials: colored_blocks(ns) × kTermSlots doubles; the target has normals.
+// The colored terms of the loop's current evaluation and their reduction into sums (terms_pass.h
+// launch_side_terms).  rec_t: the target's records in index order; is_s: the source's intensities
+// in slot order; kind: a checked M3D_KERNEL_* (L2: unit weights); the target has normals.
 hipError_t launch_colored_terms(const m3d_icp* s, const double* rec_t, const double* is_s, double lambda,
                                 int32_t kind, double k, double* partials, double* sums, bool with_defer,
                                 hipStream_t st) {
-  const int64_t ns = s->src->n, nt = s->tgt->n;
-  const int64_t nb = (ns == 0 || nt == 0) ? 0 : colored_blocks(ns);
   const double sg = std::sqrt(lambda), sp = std::sqrt(1.0 - lambda);
-  if (nb > 0)
-    with_kind(kind, [&](auto K) {
-      colored_terms_kernel<decltype(K)::value><<<(unsigned)nb, kColoredBlock, 0, st>>>(
-          s->pcd64, s->src->xyz32, ns, s->tgt->xyz64, s->tgt->nrm64, rec_t, is_s, nt, s->tgrid->dev, s->state,
-          s->keys, s->near2, s->corr, sg, sp, k, partials);
-    });
-  return launch_reduce(partials, nb, kTermSlots, sums, s->state, with_defer ? s->hcnt : nullptr, st);
+  hipError_t e = hipSuccess;
+  with_kind(kind, [&](auto K) {
+    e = launch_side_terms(s, ColoredEst<decltype(K)::value>{{}, s->tgt->nrm64, rec_t, is_s, sg, sp, k}, partials, sums,
+                          with_defer, st);
+  });
+  return e;
 }
 
 }  // namespace m3d

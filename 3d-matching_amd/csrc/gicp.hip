@@ -1,7 +1,9 @@
 // gicp.hip — Generalized ICP (Open3D 0.19 GeneralizedICP.cpp, plane-to-plane): per-point
-// covariances from normals, and the terms pass that replaces icp.hip's point-to-plane terms in the
-// RegistrationICP loop.  The NN scan before it, the solve after it (icp.hip solve_state, the
-// point-to-plane slot layout) and the convergence rule are the loop's own.
+// covariances from normals, and the estimator (GicpEst) of the side terms pass that replaces
+// icp.hip's point-to-plane terms in the RegistrationICP loop.  The pass itself — winner,
+// write-back, the 30 slots, the fixed-order sum — is terms_pass.h's; the NN scan before it, the
+// solve after it (icp.hip solve_state, the point-to-plane slot layout) and the convergence rule
+// are the loop's own.
 //
 // Covariance of a point with unit normal n (InitializePointCloudForGeneralizedICP):
 //   C = Rx·diag(ε, 1, 1)·Rxᵀ,  Rx = GetRotationFromE1ToX(n):  v = e1 × n = (0, −nz, ny), c = nx,
@@ -11,28 +13,22 @@
 //
 // One evaluation, source slot i (its point p, covariance Cs; dT = the transform the evaluation
 // applies, IcpState::dT — the init, then each update):
-//   vs = dT·p (nnkey.h q64_of), Cs ← R·Cs·Rᵀ (R = dT's rotation), both written back
-//   (pcd.Transform(update) moves points and covariances); winner t = nnkey.h winner_fp64;
+//   vs = dT·p (nnkey.h q64_of), Cs ← R·Cs·Rᵀ (R = dT's rotation; terms_pass.h rotate_cov6, shared
+//   with robust.hip), both written back (pcd.Transform(update) moves points and covariances);
+//   winner t = nnkey.h winner_fp64;
 //   d = vs − vt, M = Ct + Cs, B = M⁻¹ (closed form: cofactors over the determinant),
 //   J₀ = [−[vs]× | I] (3×6):  JᵀJ += J₀ᵀ·B·J₀, Jᵀr += J₀ᵀ·B·d, Σr² += dᵀ·B·d, count += 1, Σd² += d².
 // With unit weights this equals Open3D's rows W·d, W·J₀ with W = M^(−1/2): no square root needed.
-// Slots: 0..20 JᵀJ (upper, row-major), 21..26 Jᵀr, 27 Σr², 28 count, 29 Σd² — icp.hip's
-// point-to-plane layout, so launch_icp_solve consumes the sums unchanged.
-//
-// Order of summation: the loop's fixed order (icp.hip, "reduce"; nnkey.h block_partial per block
-// of 256 consecutive slots, launch_reduce over the block partials) — two runs, and the brute-force
-// and grid scans, give the same bits.
+// Slots and order of summation: terms_pass.h.
 //
 // Bytes per source the terms pass must move: its point read and written (24 + 24), its
 // covariance read and written (48 + 48), key, runner-up and correspondence (8 + 4 + 4), and the
 // gathered winner's point and covariance (24 + 48): 232 B.
 #include "m3d_internal.h"
 #include "nnkey.h"
+#include "terms_pass.h"
 
 namespace m3d {
-
-constexpr int kGicpBlock = 256;
-constexpr int kGicpUsed = 30;
 
 // upper triangle of Rx·diag(ε, 1, 1)·Rxᵀ for the normal (nx, ny, nz)
 __device__ __forceinline__ void cov6_of_normal(double nx, double ny, double nz, double eps, double (&C)[6]) {
@@ -107,7 +103,7 @@ __device__ __forceinline__ double j0_dot(double x, double y, double z, const dou
 constexpr int jtj_slot(int a, int c) { return a * 6 - a * (a - 1) / 2 + (c - a); }
 
 template <int a, int c>
-__device__ __forceinline__ void jtj_row(double (&v)[kGicpUsed], double x, double y, double z,
+__device__ __forceinline__ void jtj_row(double (&v)[kTermsUsed], double x, double y, double z,
                                         const double (&G)[6][3]) {
   if constexpr (c < 6) {
     v[jtj_slot(a, c)] = j0_dot<a>(x, y, z, G[c]);
@@ -115,7 +111,7 @@ __device__ __forceinline__ void jtj_row(double (&v)[kGicpUsed], double x, double
   }
 }
 template <int a>
-__device__ __forceinline__ void jtj_rows(double (&v)[kGicpUsed], double x, double y, double z,
+__device__ __forceinline__ void jtj_rows(double (&v)[kTermsUsed], double x, double y, double z,
                                          const double (&G)[6][3], const double (&w)[3]) {
   if constexpr (a < 6) {
     jtj_row<a, a>(v, x, y, z, G);
@@ -124,50 +120,13 @@ __device__ __forceinline__ void jtj_rows(double (&v)[kGicpUsed], double x, doubl
   }
 }
 
-// ns > 0 and nt > 0 (launch_gicp_terms keeps the empty cases away: no slot 0, no target 0 to load)
-__global__ __launch_bounds__(kGicpBlock) void gicp_terms_kernel(
-    double* __restrict__ pcd64, double* __restrict__ cov_s, const float4* __restrict__ src32, int64_t ns,
-    const double* __restrict__ tgt64, const double* __restrict__ cov_t, int64_t nt, GridDev g,
-    const IcpState* __restrict__ s, const int64_t* __restrict__ keys, const uint32_t* __restrict__ near2,
-    int32_t* __restrict__ corr, double* __restrict__ partials) {
-  if (s->done) return;
-  const SlotWinner sw = slot_winner((int64_t)blockIdx.x * kGicpBlock + threadIdx.x, pcd64, src32, ns, tgt64, nt, g, s,
-                                    keys, near2);
-  const bool valid = sw.valid, hit = sw.hit;
-  const int64_t i = sw.i, gj = sw.gj;
-  const double(&Q)[3] = sw.Q;
-  // Cs ← R·Cs·Rᵀ: A = R·Cs, then the upper triangle of A·Rᵀ
-  double cs[6], Cs[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) cs[k] = cov_s[6 * i + k];
-  {
-    const double* T = s->dT;
-    const double R[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
-    const double C[3][3] = {{cs[0], cs[1], cs[2]}, {cs[1], cs[3], cs[4]}, {cs[2], cs[4], cs[5]}};
-    double A[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) A[a][b] = (R[a][0] * C[0][b] + R[a][1] * C[1][b]) + R[a][2] * C[2][b];
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = a; b < 3; ++b) Cs[k++] = (A[a][0] * R[b][0] + A[a][1] * R[b][1]) + A[a][2] * R[b][2];
-  }
-  if (valid) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) pcd64[3 * i + k] = Q[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) cov_s[6 * i + k] = Cs[k];
-  }
-  if (valid) corr[i] = hit ? (int32_t)gj : -1;
-  double v[kGicpUsed];
-#pragma unroll
-  for (int k = 0; k < kGicpUsed; ++k) v[k] = 0.0;
-  if (hit) {
-    const double* tq = tgt64 + 3 * gj;
-    const double* ct = cov_t + 6 * gj;
+// The plane-to-plane terms of a matched pair (the file header's formulas, expression for expression)
+struct GicpEst : CovState {
+  __device__ __forceinline__ void rows(double (&v)[kTermsUsed], const SlotWinner& sw, const double* __restrict__ tq,
+                                       const Slot& own) const {
+    const double(&Q)[3] = sw.Q;
+    const double(&Cs)[6] = own.Cs;
+    const double* ct = cov_t + 6 * sw.gj;
     const double d[3] = {Q[0] - tq[0], Q[1] - tq[1], Q[2] - tq[2]};
     const double ma = ct[0] + Cs[0], mb = ct[1] + Cs[1], mc = ct[2] + Cs[2];
     const double md = ct[3] + Cs[3], me = ct[4] + Cs[4], mf = ct[5] + Cs[5];
@@ -189,13 +148,8 @@ __global__ __launch_bounds__(kGicpBlock) void gicp_terms_kernel(
                          (b02 * d[0] + b12 * d[1]) + b22 * d[2]};
     jtj_rows<0>(v, x, y, z, G, w);
     v[27] = (d[0] * w[0] + d[1] * w[1]) + d[2] * w[2];
-    v[28] = 1.0;
-    v[29] = sw.d;
   }
-  block_partial<kTermSlots, kGicpUsed, kGicpBlock>(v, partials);
-}
-
-int64_t gicp_blocks(int64_t ns) { return ns > 0 ? (ns + kGicpBlock - 1) / kGicpBlock : 0; }
+};
 
 hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, double* out, int width,
                                    hipStream_t st) {
@@ -210,22 +164,11 @@ hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, d
   return hipGetLastError();
 }
 
-// The plane-to-plane terms of the loop's current evaluation (its NN scan must have been enqueued
-// on st) and their reduction into sums (kTermSlots doubles).  cov_s: the loop's source covariances
-// in slot order, 6 per point, rotated in place; cov_t: the target's in index order; partials:
-// gicp_blocks(ns) × kTermSlots doubles.  sums[0 .. 30) = the sums over the partials (no blocks:
-// zeros), all the solve reads; with_defer: the last two words carry the grid scan's deferral count
-// and fault word (else, and for brute force, zeros), so that a one-evaluation call gets its result
-// and the fault word in one read.
+// The plane-to-plane terms of the loop's current evaluation and their reduction into sums
+// (terms_pass.h launch_side_terms)
 hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
                              double* sums, bool with_defer, hipStream_t st) {
-  const int64_t ns = s->src->n, nt = s->tgt->n;
-  const int64_t nb = (ns == 0 || nt == 0) ? 0 : gicp_blocks(ns);
-  if (nb > 0)
-    gicp_terms_kernel<<<(unsigned)nb, kGicpBlock, 0, st>>>(s->pcd64, cov_s, s->src->xyz32, ns, s->tgt->xyz64,
-                                                          cov_t, nt, s->tgrid->dev, s->state, s->keys,
-                                                          s->near2, s->corr, partials);
-  return launch_reduce(partials, nb, kTermSlots, sums, s->state, with_defer ? s->hcnt : nullptr, st);
+  return launch_side_terms(s, GicpEst{{cov_s, cov_t}}, partials, sums, with_defer, st);
 }
 
 }  // namespace m3d

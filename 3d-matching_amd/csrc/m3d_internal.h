@@ -276,6 +276,10 @@ inline bool in_block(const void* p, const void* block, size_t bytes) {
 constexpr int kDeferWords = 4;
 constexpr int kDeferFault = 2;
 constexpr int kTermSlots = 32;  // 21 JTJ + 6 JTr + r² + count + Σd² (+2 pad)
+// a side terms pass (terms_pass.h): one slot per thread, 256 per block as nnkey.h block_partial and
+// launch_reduce take them
+constexpr int kSideBlock = 256;
+inline int64_t side_terms_blocks(int64_t ns) { return ns > 0 ? (ns + kSideBlock - 1) / kSideBlock : 0; }
 constexpr int64_t kKeyNone = 0x7FFFFFFFFFFFFFFFll;
 
 }  // namespace m3d
@@ -579,28 +583,24 @@ size_t eval_scratch_bytes(int64_t ns);
 hipError_t launch_eval(const m3d_icp* s, int with_info, int32_t* idx, double* d2, double* partials,
                        double* out, hipStream_t st);
 hipError_t launch_eval_fill(int64_t ns, int32_t* idx, double* d2, hipStream_t st);
-// gicp.hip: covariances (6 doubles per point: the upper triangle) and the plane-to-plane terms pass
-// after a loop's NN scan; sums[0 .. 30) in the point-to-plane slot layout, the last two words the
-// deferral count / fault when with_defer
-int64_t gicp_blocks(int64_t ns);
+// The side terms passes after a loop's NN scan (terms_pass.h: one kernel skeleton and one launcher,
+// an estimator per translation unit): sums[0 .. 30) in the point-to-plane slot layout, the last
+// two words the deferral count / fault when with_defer; partials: side_terms_blocks(ns) ×
+// kTermSlots doubles.
+// gicp.hip: covariances (6 doubles per point: the upper triangle) and the plane-to-plane terms
 hipError_t launch_cov_from_normals(const double* nrm, int64_t n, double eps, double* out, int width,
                                    hipStream_t st);
 hipError_t launch_cov_pack(const double* cov9, const int32_t* slot, int64_t n, double* out6, hipStream_t st);
 hipError_t launch_gicp_terms(const m3d_icp* s, double* cov_s, const double* cov_t, double* partials,
                              double* sums, bool with_defer, hipStream_t st);
-// robust.hip: the same two passes with a robust kernel (kind: a checked M3D_KERNEL_*, k its scale);
-// partials: robust_blocks(ns) × kTermSlots doubles
-int64_t robust_blocks(int64_t ns);
-hipError_t launch_robust_plane_terms(const m3d_icp* s, int32_t kind, double k, double* partials, double* sums,
-                                     bool with_defer, hipStream_t st);
-hipError_t launch_robust_gicp_terms(const m3d_icp* s, int32_t kind, double k, double* cov_s, const double* cov_t,
-                                    double* partials, double* sums, bool with_defer, hipStream_t st);
+// robust.hip: the terms with a robust kernel (kind: a checked M3D_KERNEL_*, k its scale); cov_s
+// null: point-to-plane, else Generalized ICP
+hipError_t launch_robust_terms(const m3d_icp* s, int32_t kind, double k, double* cov_s, const double* cov_t,
+                               double* partials, double* sums, bool with_defer, hipStream_t st);
 // colored.hip: the colour gradients of a cloud (one wave per point on its hybrid list, g / gf /
 // hfine as hybrid_search; rec n × 4 = gradient and intensity, out3 n × 3, either may be null), a
 // caller's gradients packed into records, intensities gathered through slot, and the two-row terms
-// pass after a loop's NN scan (rec_t in target index order, is_s in slot order, partials:
-// colored_blocks(ns) × kTermSlots doubles)
-int64_t colored_blocks(int64_t ns);
+// (rec_t in target index order, is_s in slot order)
 hipError_t launch_color_gradients(const m3d_cloud* c, const double* nrm, const double* colors, const Grid* g,
                                   double radius, int k, double* rec, double* out3, hipStream_t st,
                                   const Grid* gf = nullptr, double hfine = 0.0);

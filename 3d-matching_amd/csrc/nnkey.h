@@ -399,8 +399,9 @@ __device__ __forceinline__ void winner_fp64(bool valid, uint64_t k1, float near2
 }
 
 // The winner of a loop's source slot after its NN scan, as every pass that consumes a whole scan
-// on one device opens (icp.hip nn_finalize_kernel, eval.hip eval_kernel, gicp.hip
-// gicp_terms_kernel): the same expressions in the same order, hence the same bits in all three.
+// on one device opens (icp.hip nn_finalize_kernel, eval.hip eval_kernel, terms_pass.h
+// side_terms_kernel for every side terms estimator): the same expressions in the same order,
+// hence the same bits in all of them.
 // i0 = the thread's slot; every lane of the wave calls it, a lane past ns (valid false) with
 // slot 0's loads.  Q = dT·pcd64[i], gj / d = winner_fp64's winner and its fp64 d², hit = the slot
 // has a target inside the radius.  ns > 0.

@@ -489,13 +489,35 @@ def corr_pairs(ctx: Context, corr, n: int) -> np.ndarray:
     return out[: m.value]
 
 
+def _outcome(ctx: Context, res, corr, n: int, with_correspondences: bool) -> IcpOutcome:
+    """The IcpOutcome of a library IcpResult; corr: the run's per-source indices (corr_pairs)."""
+    pairs = corr_pairs(ctx, corr, n) if with_correspondences else np.zeros((0, 2), np.int32)
+    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
+                      res.num_correspondences, res.iterations, bool(res.converged), pairs,
+                      np.array(res.update[:]).reshape(4, 4))
+
+
+def _terms_call(src: Cloud, with_correspondences: bool, call, what: str):
+    """One evaluation's outputs: call(sums, idx) runs the library call on a 32-double sums array
+    and the per-source index tensor (or None) → (sums (30,) f64, corr_idx (ns,) or None)."""
+    idx = device_empty((max(src.n, 1),), _torch().int32) if with_correspondences else None
+    sums = (C.c_double * 32)()
+    src.ctx.check(call(sums, ptr(idx)), what)
+    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
+
+
 def _robust_kernel(kernel):
     """A robust kernel (matcher.robust: an object with ``kind`` = _lib.ROBUST_* and, where the
     kernel has a scale, ``k``) as the library's struct; None for no kernel or L2 — the call is then
-    the one without a kernel."""
+    the one without a kernel (the fused point-to-plane tail, gicp.hip's plane-to-plane terms).
+    Colored ICP has no pass without weights, so _colored_kernel hands L2 on."""
     if kernel is None or int(kernel.kind) == _lib.ROBUST_L2:
         return None
-    return _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
+    return _colored_kernel(kernel)
+
+
+def _colored_kernel(kernel):
+    return None if kernel is None else _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
 
 
 def icp(src: Cloud, tgt: Cloud, max_dist: float, init=None, estimation=_lib.EST_POINT_TO_PLANE,
@@ -517,10 +539,7 @@ def icp(src: Cloud, tgt: Cloud, max_dist: float, init=None, estimation=_lib.EST_
         src.ctx.check(src.ctx.lib.m3d_robust_icp_run(src.ctx.h, src.h, tgt.h, init16, float(max_dist), C.byref(p),
                                                      C.byref(rk), C.byref(res), ptr(corr), stream_handle()),
                       "robust_icp_run")
-    cs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
-    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
-                      res.num_correspondences, res.iterations, bool(res.converged), cs,
-                      np.array(res.update[:]).reshape(4, 4))
+    return _outcome(src.ctx, res, corr, src.n, with_correspondences)
 
 
 def robust_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, kernel=None, nn: str = "grid",
@@ -529,16 +548,12 @@ def robust_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, kernel=N
     (sums (30,) f64 in gicp_terms' layout, corr_idx (ns,) int32 torch cuda or None).  Every kind,
     L2 too, runs through the robust pass here."""
     method = _nn_method(nn)
-    torch = _torch()
     if kernel is None:
         raise ValueError("robust_terms needs a kernel")
-    rk = _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
-    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
-    sums = (C.c_double * 32)()
-    src.ctx.check(src.ctx.lib.m3d_robust_terms(
+    rk = _colored_kernel(kernel)  # L2 handed on
+    return _terms_call(src, with_correspondences, lambda sums, idx: src.ctx.lib.m3d_robust_terms(
         src.ctx.h, src.h, tgt.h, _T16(np.eye(4) if T is None else T), float(max_dist), method, C.byref(rk), sums,
-        ptr(idx), stream_handle()), "robust_terms")
-    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
+        idx, stream_handle()), "robust_terms")
 
 
 def _cov_device(cov, n: int, what: str):
@@ -564,21 +579,16 @@ def gicp_terms(src: Cloud, tgt: Cloud, T=None, max_dist: float = 0.0, src_cov=No
         raise ValueError("max_dist must be > 0")
     if not epsilon > 0.0:
         raise ValueError("epsilon must be > 0")
-    torch = _torch()
     cs, ct = _cov_device(src_cov, src.n, "source"), _cov_device(tgt_cov, tgt.n, "target")
-    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
-    sums = (C.c_double * 32)()
     rk = _robust_kernel(kernel)
     T16 = _T16(np.eye(4) if T is None else T)
     if rk is None:
-        src.ctx.check(src.ctx.lib.m3d_gicp_terms(
+        return _terms_call(src, with_correspondences, lambda sums, idx: src.ctx.lib.m3d_gicp_terms(
             src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), T16, float(max_dist),
-            method, float(epsilon), sums, ptr(idx), stream_handle()), "gicp_terms")
-    else:
-        src.ctx.check(src.ctx.lib.m3d_gicp_terms_robust(
-            src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), T16, float(max_dist),
-            method, float(epsilon), C.byref(rk), sums, ptr(idx), stream_handle()), "gicp_terms_robust")
-    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
+            method, float(epsilon), sums, idx, stream_handle()), "gicp_terms")
+    return _terms_call(src, with_correspondences, lambda sums, idx: src.ctx.lib.m3d_gicp_terms_robust(
+        src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), T16, float(max_dist),
+        method, float(epsilon), C.byref(rk), sums, idx, stream_handle()), "gicp_terms_robust")
 
 
 def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_cov=None,
@@ -608,10 +618,7 @@ def gicp(src: Cloud, tgt: Cloud, max_dist: float, init=None, src_cov=None, tgt_c
         src.ctx.check(src.ctx.lib.m3d_gicp_run_robust(src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), init16,
                                                       float(max_dist), C.byref(p), C.byref(rk), C.byref(res),
                                                       ptr(corr), stream_handle()), "gicp_run_robust")
-    pairs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
-    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
-                      res.num_correspondences, res.iterations, bool(res.converged), pairs,
-                      np.array(res.update[:]).reshape(4, 4))
+    return _outcome(src.ctx, res, corr, src.n, with_correspondences)
 
 
 def _colors_device(colors, n: int, what: str):
@@ -632,10 +639,6 @@ def _gradient_device(grad, n: int):
     if t.shape[0] != n:
         raise ValueError(f"target gradients must be {n}×3")
     return t
-
-
-def _colored_kernel(kernel):
-    return None if kernel is None else _lib.RobustKernel(int(kernel.kind), float(getattr(kernel, "k", 0.0)))
 
 
 def color_gradients(cloud: Cloud, colors, radius: float, max_nn: int = 30) -> np.ndarray:
@@ -666,17 +669,13 @@ def colored_terms(src: Cloud, tgt: Cloud, src_colors, tgt_colors, T=None, max_di
     method = _nn_method(nn)
     if not max_dist > 0.0:
         raise ValueError("max_dist must be > 0")
-    torch = _torch()
     cs, ct = _colors_device(src_colors, src.n, "source"), _colors_device(tgt_colors, tgt.n, "target")
     tg = _gradient_device(tgt_gradient, tgt.n)
-    idx = device_empty((max(src.n, 1),), torch.int32) if with_correspondences else None
-    sums = (C.c_double * 32)()
     rk = _colored_kernel(kernel)
-    src.ctx.check(src.ctx.lib.m3d_colored_terms(
+    return _terms_call(src, with_correspondences, lambda sums, idx: src.ctx.lib.m3d_colored_terms(
         src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), ptr(tg), _T16(np.eye(4) if T is None else T), float(max_dist),
-        method, float(lambda_geometric), None if rk is None else C.byref(rk), sums, ptr(idx), stream_handle()),
+        method, float(lambda_geometric), None if rk is None else C.byref(rk), sums, idx, stream_handle()),
         "colored_terms")
-    return np.array(sums[:30]), (None if idx is None else idx[: src.n])
 
 
 def colored_icp(src: Cloud, tgt: Cloud, src_colors, tgt_colors, max_dist: float, init=None,
@@ -699,10 +698,7 @@ def colored_icp(src: Cloud, tgt: Cloud, src_colors, tgt_colors, max_dist: float,
         src.ctx.h, src.h, tgt.h, ptr(cs), ptr(ct), ptr(tg), _T16(np.eye(4) if init is None else init),
         float(max_dist), C.byref(p), None if rk is None else C.byref(rk), C.byref(res), ptr(corr), stream_handle()),
         "colored_icp_run")
-    pairs = corr_pairs(src.ctx, corr, src.n) if with_correspondences else np.zeros((0, 2), np.int32)
-    return IcpOutcome(np.array(res.T[:]).reshape(4, 4), res.fitness, res.inlier_rmse,
-                      res.num_correspondences, res.iterations, bool(res.converged), pairs,
-                      np.array(res.update[:]).reshape(4, 4))
+    return _outcome(src.ctx, res, corr, src.n, with_correspondences)
 
 
 class IcpLoop:
@@ -790,9 +786,7 @@ class IcpLoop:
     def result(self) -> IcpOutcome:
         r = _lib.IcpResult()
         self.ctx.check(self.ctx.lib.m3d_icp_result_get(self.h, C.byref(r), stream_handle()), "icp_result")
-        return IcpOutcome(np.array(r.T[:]).reshape(4, 4), r.fitness, r.inlier_rmse,
-                          r.num_correspondences, r.iterations, bool(r.converged),
-                          update=np.array(r.update[:]).reshape(4, 4))
+        return _outcome(self.ctx, r, None, 0, False)
 
     def points(self):
         """The loop's fp64 points of the last evaluation (ns×3 f64 torch cuda, source order):

@@ -26,7 +26,7 @@ import icp_oracle as I
 import matcher
 import robust_restatement as R
 from m3d import _lib
-from m3d.core import Cloud, gicp, gicp_terms, icp, robust_terms
+from m3d.core import Cloud, colored_terms, gicp, gicp_terms, icp, robust_terms
 from m3d.types import FastGlobalRegistrationOption, PointCloud
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The given NumPy array is not writable")]
@@ -98,6 +98,33 @@ def test_l2_or_null_through_the_c_entry_points_is_the_call_without_a_kernel():
                                             C.byref(res), None, stream_handle()), "gicp_run_robust")
         np.testing.assert_array_equal(np.array(res.T[:]).reshape(4, 4), run.transformation)
         assert (res.fitness, res.inlier_rmse, res.iterations) == (run.fitness, run.inlier_rmse, run.iterations)
+
+
+@pytest.mark.parametrize("ns", [257, 256])
+def test_every_side_terms_pass_shares_the_skeleton(ns):
+    """What terms_pass.h does for every estimator — the winner, corr, the count and Σd² — is the
+    same bits whichever estimator rides on it: plain Generalized ICP, robust point-to-plane L2,
+    robust Generalized ICP Huber and Colored ICP (a constant colour on both clouds), grid and brute
+    force.  257 sources: two blocks, the second with one live lane; 256 (the same case sliced; a
+    source's winner does not depend on the other sources): exactly one full block."""
+    c = R.eval_case(257)
+    j = c["j"][:ns]
+    assert (j < 0).any() and (j >= 0).any()  # some sources unmatched
+    s, t = Cloud(c["src"][:ns], c["sn"][:ns]), Cloud(c["tgt"], c["tn"])
+    sc, tc = np.full((ns, 3), 0.5), np.full((len(c["tgt"]), 3), 0.5)
+    calls = {"gicp": lambda nn: gicp_terms(s, t, c["T"], G.RADIUS, epsilon=G.EPS, nn=nn),
+             "plane l2": lambda nn: robust_terms(s, t, c["T"], G.RADIUS, matcher.L2Loss(), nn=nn),
+             "gicp huber": lambda nn: gicp_terms(s, t, c["T"], G.RADIUS, epsilon=G.EPS, nn=nn,
+                                                 kernel=matcher.HuberLoss(c["k_gicp"])),
+             "colored": lambda nn: colored_terms(s, t, sc, tc, c["T"], G.RADIUS, nn=nn)}
+    first = None
+    for name, call in calls.items():
+        for nn in ("grid", "brute"):
+            sums, idx = call(nn)
+            np.testing.assert_array_equal(idx.cpu().numpy(), j, err_msg=f"{name} {nn}")
+            assert sums[28] == (j >= 0).sum(), (name, nn)
+            first = sums if first is None else first
+            assert (sums[28].tobytes(), sums[29].tobytes()) == (first[28].tobytes(), first[29].tobytes()), (name, nn)
 
 
 # ---------------------------------------------------------------------------------------- loops

@@ -16,10 +16,12 @@ position in the target's frame, r != g != b).
    point-to-plane) per source the passes must move.  The difference is the second row and 40 more
    bytes.
 
+AB_LIB=<libm3d.so of another build> times that build instead.
 Needs the GPU; prints readable lines and one JSON line.
 Usage: python tools/colored_timing.py [--ns 100000] [--iters 30] [--repeats 15] [--warmup 3]"""
 import argparse
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -28,6 +30,9 @@ import numpy as np
 import torch
 
 from m3d import _lib, synth
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 from m3d.core import Cloud, color_gradients, colored_icp, context, device_empty, icp, ptr, stream_handle, to_device
 from matcher.robust import TukeyLoss
 from robust_timing import spread, timed

@@ -11,11 +11,15 @@ with the grid NN.
 * Kernel events of the library (m3d_profile_*), in a pass of their own: the NN scan and the terms
   launch(es) per evaluation — for Generalized ICP the plane-to-plane pass plus its reduce — and
   the achieved bytes/s of that pass against the 232 B per source it must move (gicp.hip).
+* The one-evaluation call (m3d_gicp_terms) at 1,000 sources of the same pair, host-bound at that
+  size: whole warm calls, median and min..max over 20 x --repeats.
 
+AB_LIB=<libm3d.so of another build> times that build instead.
 Needs the GPU; prints readable lines and one JSON line.
 Usage: python tools/gicp_timing.py [--ns 100000] [--iters 30] [--repeats 15] [--warmup 3]"""
 import argparse
 import json
+import os
 import statistics
 import sys
 from pathlib import Path
@@ -25,7 +29,10 @@ import numpy as np
 import torch
 
 from m3d import _lib, synth
-from m3d.core import Cloud, IcpLoop, context, gicp, icp
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
+from m3d.core import Cloud, IcpLoop, context, gicp, gicp_terms, icp
 
 BYTES_PER_SOURCE = 232  # gicp.hip: point and covariance read + written, key, runner-up, corr, gathered target
 
@@ -83,6 +90,14 @@ def main():
         if rep >= args.warmup:
             steps.append(us / N)
     res["point_to_plane_step_loop"] = spread(steps)
+    # the one-evaluation call at a size where the host's part of it dominates
+    s1k, t1k = Cloud(src[:1000], sn[:1000]), Cloud(tgt[:1000], tn[:1000])
+    one = []
+    for rep in range(20 * (args.warmup + args.repeats)):
+        us, _ = timed(lambda: gicp_terms(s1k, t1k, np.eye(4), r, with_correspondences=False))
+        if rep >= 20 * args.warmup:
+            one.append(us)
+    res["gicp_terms_call_ns1000"] = spread(one)
     # kernel events, in a pass of their own
     kern = {}
     for name, fn in calls.items():
@@ -106,6 +121,9 @@ def main():
     v = res["point_to_plane_step_loop"]
     print(f"step-wise point-to-plane loop: {v['median_us']:.1f} us per iteration (min {v['min_us']:.1f}, "
           f"max {v['max_us']:.1f})")
+    v = res["gicp_terms_call_ns1000"]
+    print(f"m3d_gicp_terms at ns = 1000: {v['median_us']:.1f} us per call (min {v['min_us']:.1f}, max {v['max_us']:.1f}, "
+          f"n {v['n']})")
     print(f"ratio gicp / point-to-plane per evaluation: {res['ratio_gicp_over_point_to_plane']:.2f}")
     for k, v in kern.items():
         print(f"{k:>15} kernel events: NN scan {v['nn_us']:.1f} us, terms launch {v['terms_us']:.1f} us "

@@ -12,10 +12,12 @@ the benchmark's seeded 100k <-> 100k pair (m3d.synth.icp_pair, seed 0, r = 0.12)
   and gicp.hip's move the same bytes, so (robust - unweighted) / robust is what W = M^(-1/2)
   (Jacobi sweeps, three 1/sqrt) and three weighted rows instead of one M^-1 system cost together.
 
+AB_LIB=<libm3d.so of another build> times that build instead.
 Needs the GPU; prints readable lines and one JSON line.
 Usage: python tools/robust_timing.py [--ns 100000] [--iters 30] [--repeats 15] [--warmup 3]"""
 import argparse
 import json
+import os
 import statistics
 import sys
 from pathlib import Path
@@ -25,6 +27,9 @@ import numpy as np
 import torch
 
 from m3d import _lib, synth
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 from m3d.core import Cloud, context, gicp, icp
 from matcher.robust import TukeyLoss
 
