@@ -1841,7 +1841,7 @@ struct ScopedLoop {
 // read `done` and return.  The evaluations that run are the same; only the early-exit launches
 // are skipped.
 template <class Step>
-int run_chunked(m3d_icp* s, int32_t total, Step step, hipStream_t st) {
+int run_chunked(m3d_ctx* ctx, const IcpState* state, int32_t total, Step step, hipStream_t st) {
   int32_t left = total, chunk = 4;
   while (left > 0) {
     const int32_t k = std::min(chunk, left);
@@ -1850,12 +1850,16 @@ int run_chunked(m3d_icp* s, int32_t total, Step step, hipStream_t st) {
     chunk *= 2;
     if (rc || left == 0) return rc;
     int32_t done = 0;
-    hipError_t e = hipMemcpyAsync(&done, &s->state->done, sizeof(done), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(&done, &state->done, sizeof(done), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return m3d_fail(s->ctx, M3D_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, hipGetErrorString(e));
     if (done) break;
   }
   return M3D_OK;
+}
+template <class Step>
+int run_chunked(m3d_icp* s, int32_t total, Step step, hipStream_t st) {
+  return run_chunked(s->ctx, s->state, total, step, st);
 }
 
 // after the evaluations: the result, and the correspondences in the caller's source order
@@ -2075,7 +2079,10 @@ int run_terms_loop(m3d_icp* s, int32_t max_iteration, Terms terms, m3d_icp_resul
         KTimer kt(ctx, M3D_KERNEL_TERMS, st);
         e = terms(s->sums);
       }
-      if (e == hipSuccess) e = launch_icp_solve(s, s->sums, st);
+      if (e == hipSuccess) {
+        KTimer kt(ctx, M3D_KERNEL_LOOP, st);
+        e = launch_icp_solve(s, s->sums, st);
+      }
     }
     return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("terms loop step: ") + hipGetErrorString(e));
   };
@@ -3186,6 +3193,168 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4) {
   out4[1] = mesh->grid_built ? mesh->nrefs : 0;
   out4[2] = mesh->grid_built ? mesh->doublings : 0;
   out4[3] = mesh->last_rounds;
+  return M3D_OK;
+}
+
+// ------------------------------------------------------------------------------- ICP against a mesh
+// mesh_icp.hip.  A loop of its own around the mesh (m3d_icp is bound to a target cloud's NN): the
+// arrays from the context's run arena (the calls synchronise before returning), the source in the
+// Morton slot order of its cloud, the mesh's grid built on first use.  Profiling (m3d_profile_*): the
+// scan under M3D_KERNEL_NN, terms + reduce under M3D_KERNEL_TERMS, the solve under M3D_KERNEL_LOOP.
+extern "C++" {
+namespace {
+struct MeshIcpCall {
+  MeshIcpLoop L;
+  const m3d_cloud* ms = nullptr;  // the source's Morton copy
+  bool brute = false;
+  int32_t kind = M3D_KERNEL_L2;
+  double k = 1.0;
+};
+
+// the checks both entry points share, the path, the loop's arrays and its state at `init`
+int mesh_icp_setup(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const double* init, double max_dist,
+                   const m3d_robust_kernel* kernel, int32_t path, MeshIcpCall* c, hipStream_t st) {
+  CHECK_ARG(ctx, src != nullptr, "invalid arguments");
+  CHECK_ARG(ctx, std::isfinite(max_dist) && max_dist > 0.0, "Invalid max_correspondence_distance.");
+  CHECK_ARG(ctx, path >= 0 && path <= 2, "path: 0 automatic, 1 brute force, 2 grid");
+  if (kernel != nullptr) {
+    const int rc = robust_check(ctx, kernel);
+    if (rc) return rc;
+    c->kind = kernel->kind;
+    c->k = kernel->k;
+  }
+  CHECK_ARG(ctx, mesh->usable > 0, "the mesh has no usable triangle (none, or every one degenerate or not finite)");
+  hipSetDevice(ctx->device);
+  c->brute = path == 1 || (path == 0 && mesh->nf <= kMeshIcpAutoBruteMax);
+  MeshIcpLoop& L = c->L;
+  L.ns = src->n;
+  L.max_dist = max_dist;
+  if (!c->brute) {
+    std::string why;
+    const hipError_t e = mesh_grid_build(ctx, mesh, st, &why);
+    if (e != hipSuccess) return clean_fail(ctx, "mesh_icp", e, why);
+  }
+  if (L.ns > 0) {
+    const Grid* sg = nullptr;
+    const int rc = ensure_morton_source(ctx, src, max_dist * 1.001, &c->ms, &sg);
+    if (rc) return rc;
+    HIPX(ctx, hipStreamSynchronize(nullptr));  // the copy is made on the null stream
+  }
+  const size_t n1 = (size_t)std::max<int64_t>(L.ns, 1);
+  Carve cv;
+  cv.add(&L.state, 1);
+  cv.add(&L.sums, kTermSlots);
+  cv.add(&L.partials, (size_t)kTermSlots * (size_t)std::max<int64_t>(side_terms_blocks(L.ns), 1));
+  cv.add(&L.pcd64, 3 * n1);
+  cv.add(&L.tri, n1);
+  cv.add(&L.d2, n1);
+  cv.add(&L.pt, 3 * n1);
+  if (ctx->run.reserve(cv.bytes()) != hipSuccess)
+    return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (mesh ICP loop arrays)");
+  cv.place(ctx->run.base);
+  // RegistrationICP: pcd = source; if (!init.isIdentity()) pcd.Transform(init) — by the first query
+  IcpState h;
+  memset(&h, 0, sizeof h);
+  for (int k = 0; k < 16; ++k) {
+    const double I = (k % 5 == 0) ? 1.0 : 0.0;
+    h.T[k] = init != nullptr ? init[k] : I;
+    h.dT[k] = init != nullptr && !eigen_is_identity(init) ? init[k] : I;
+    h.last_upd[k] = I;
+  }
+  h.r2 = max_dist * max_dist;
+  HIPX(ctx, hipMemcpyAsync(L.state, &h, sizeof h, hipMemcpyHostToDevice, st));
+  if (L.ns > 0) {
+    HIPX(ctx, hipMemcpyAsync(L.pcd64, c->ms->xyz64, sizeof(double) * 3 * (size_t)L.ns, hipMemcpyDeviceToDevice, st));
+    HIPX(ctx, hipMemsetAsync(L.tri, 0xFF, sizeof(int32_t) * (size_t)L.ns, st));  // no seed, no match: −1
+  }
+  HIPX(ctx, hipStreamSynchronize(st));  // h leaves scope
+  return M3D_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int m3d_mesh_icp_terms(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const double* T_host, double max_dist,
+                       const m3d_robust_kernel* kernel, int32_t path, const int32_t* seed_tri, double* sums_out,
+                       int32_t* tri_idx, double* d2_out, void* stream) {
+  if (!ctx || !mesh) return M3D_ERR_INVALID;
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  CHECK_ARG(ctx, sums_out != nullptr, "null output");
+  for (int k = 0; k < kTermSlots; ++k) sums_out[k] = 0.0;
+  MeshIcpCall c;
+  const int rc = mesh_icp_setup(ctx, mesh, src, T_host, max_dist, kernel, path, &c, st);
+  if (rc) return rc;
+  const MeshIcpLoop& L = c.L;
+  if (L.ns == 0) return M3D_OK;
+  hipError_t e = hipSuccess;
+  if (seed_tri != nullptr) e = launch_gather_i32(seed_tri, c.ms->slot, L.ns, L.tri, st);
+  if (e == hipSuccess) e = launch_mesh_icp_scan(mesh, L, c.brute, seed_tri != nullptr, st);
+  if (e == hipSuccess) e = launch_mesh_icp_terms(mesh, L, c.kind, c.k, L.sums, st);
+  if (e == hipSuccess && tri_idx != nullptr) e = launch_scatter_i32(L.tri, c.ms->slot, L.ns, tri_idx, st);
+  if (e == hipSuccess && d2_out != nullptr) e = launch_scatter_f64(L.d2, c.ms->slot, L.ns, d2_out, st);
+  double sums[kTermSlots];
+  if (e == hipSuccess) e = hipMemcpyAsync(sums, L.sums, sizeof sums, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh_icp_terms: ") + hipGetErrorString(e));
+  }
+  for (int k = 0; k < 30; ++k) sums_out[k] = sums[k];
+  return M3D_OK;
+}
+
+int m3d_mesh_icp_run(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const double* init, double max_dist,
+                     const m3d_icp_params* params, const m3d_robust_kernel* kernel, int32_t path, int32_t seed,
+                     m3d_icp_result* out, int32_t* tri_idx, void* stream) {
+  if (!ctx || !mesh) return M3D_ERR_INVALID;
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  CHECK_ARG(ctx, out != nullptr && params != nullptr, "null output or parameters");
+  CHECK_ARG(ctx, params->estimation == M3D_EST_POINT_TO_PLANE,
+            "ICP against a mesh is point-to-plane (the face normal); point-to-point is not implemented");
+  CHECK_ARG(ctx, params->max_iteration >= 0, "max_iteration must be >= 0");
+  MeshIcpCall c;
+  int rc = mesh_icp_setup(ctx, mesh, src, init, max_dist, kernel, path, &c, st);
+  if (rc) return rc;
+  const MeshIcpLoop& L = c.L;
+  auto step = [&](int32_t n) {
+    hipError_t e = hipSuccess;
+    for (int32_t it = 0; it < n && e == hipSuccess; ++it) {
+      {
+        KTimer kt(ctx, M3D_KERNEL_NN, st);
+        e = launch_mesh_icp_scan(mesh, L, c.brute, seed != 0, st);
+      }
+      if (e == hipSuccess) {
+        KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+        e = launch_mesh_icp_terms(mesh, L, c.kind, c.k, L.sums, st);
+      }
+      if (e == hipSuccess) {
+        KTimer kt(ctx, M3D_KERNEL_LOOP, st);
+        e = launch_mesh_icp_solve(L, L.sums, *params, st);
+      }
+    }
+    return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh ICP step: ") + hipGetErrorString(e));
+  };
+  rc = run_chunked(ctx, L.state, params->max_iteration + 1, step, st);
+  IcpState h;
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpyAsync(&h, L.state, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && tri_idx != nullptr) e = launch_scatter_i32(L.tri, L.ns > 0 ? c.ms->slot : nullptr, L.ns, tri_idx, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);  // the arena is idle when the call returns
+  if (rc) return rc;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh_icp_run: ") + hipGetErrorString(e));
+  for (int k = 0; k < 16; ++k) {
+    out->T[k] = h.T[k];
+    out->update[k] = h.last_upd[k];
+  }
+  out->fitness = h.fitness;
+  out->inlier_rmse = h.rmse;
+  out->num_correspondences = h.count;
+  out->iterations = h.iters;
+  out->converged = h.converged;
   return M3D_OK;
 }
 

@@ -21,6 +21,7 @@
 
 #include <cmath>
 
+#include "linalg.h"
 #include "m3d_internal.h"
 #include "nnkey.h"
 
@@ -93,12 +94,7 @@ __device__ __forceinline__ double wave_shr1(double old, double v) {
   const uint32_t hi = (uint32_t)wave_shr1((int32_t)(uint32_t)(o >> 32), (int32_t)(uint32_t)(x >> 32));
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const uint64_t x = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)x, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(x >> 32), l);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
+// (readlane_f64: linalg.h)
 
 // LDS written by some lanes of a wave is read by others of the same wave
 __device__ __forceinline__ void wave_lds_sync() {

@@ -14,12 +14,15 @@
 //  * sym3_eigenvalues: the three eigenvalues of a symmetric 3×3 by cyclic Jacobi (the covariance
 //      of an ISS neighbourhood, iss.hip): a few ulps of the norm, exact zeros for a zero block.
 //      sym3_eigen: the same with the eigenvectors; sym3_inv_sqrt: M^(−1/2) from them (robust.hip).
-//  * vec6_to_matrix: Open3D TransformVector6dToMatrix4d, R = Rz(x2)·Ry(x1)·Rx(x0).
+//  * vec6_to_matrix: Open3D TransformVector6dToMatrix4d, R = Rz(x2)·Ry(x1)·Rx(x0);
+//      vec6_to_matrix_wave: the same for a device solve, one wave, the three sincos in lanes 0..2.
 #pragma once
 
 #include <math.h>
+#include <stdint.h>
 
 #ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define M3D_HD __host__ __device__ inline
 #else
 #define M3D_HD inline
@@ -472,6 +475,57 @@ M3D_HD void matmul4(const double A[16], const double B[16], double C[16]) {
                      A[i * 4 + 2] * B[2 * 4 + j] + A[i * 4 + 3] * B[3 * 4 + j];
   for (int k = 0; k < 16; ++k) C[k] = t[k];
 }
+
+#ifdef __HIPCC__
+// (device only: one wave calls it, every lane with the same x — the solve kernels of icp.hip and
+// mesh_icp.hip)
+// vec6_to_matrix with the three sincos evaluated in lanes 0..2 at once (whole wave calls it)
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)b, l);
+  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// sin / cos of |a| ≤ 0.5 by their Taylor series in z = a² (Horner, sine to a¹⁷, cosine to a¹⁸: the
+// first dropped terms are < 2e-20 relative), ≈ 2 ulp; an ICP update's angles are far inside this
+__device__ __forceinline__ void sincos_small(double a, double* sn, double* cs) {
+  const double z = a * a;
+  double ps = 1.0 / 355687428096000.0;  // 1/17!
+  ps = fma(ps, z, -1.0 / 1307674368000.0);
+  ps = fma(ps, z, 1.0 / 6227020800.0);
+  ps = fma(ps, z, -1.0 / 39916800.0);
+  ps = fma(ps, z, 1.0 / 362880.0);
+  ps = fma(ps, z, -1.0 / 5040.0);
+  ps = fma(ps, z, 1.0 / 120.0);
+  ps = fma(ps, z, -1.0 / 6.0);
+  double pc = 1.0 / 6402373705728000.0;  // 1/18!
+  pc = fma(pc, z, -1.0 / 20922789888000.0);
+  pc = fma(pc, z, 1.0 / 87178291200.0);
+  pc = fma(pc, z, -1.0 / 479001600.0);
+  pc = fma(pc, z, 1.0 / 3628800.0);
+  pc = fma(pc, z, -1.0 / 40320.0);
+  pc = fma(pc, z, 1.0 / 720.0);
+  pc = fma(pc, z, -1.0 / 24.0);
+  pc = fma(pc, z, 0.5);
+  *sn = fma(a * z, ps, a);
+  *cs = fma(-z, pc, 1.0);
+}
+
+__device__ __forceinline__ void vec6_to_matrix_wave(const double x[6], double T[16]) {
+  const int lane = threadIdx.x & 63;
+  double sn, cs;
+  const double ang = lane == 0 ? x[0] : (lane == 1 ? x[1] : x[2]);
+  // x is the same in every lane: the branch is uniform
+  if (fmax(fabs(x[0]), fmax(fabs(x[1]), fabs(x[2]))) <= 0.5)
+    sincos_small(ang, &sn, &cs);
+  else
+    sincos(ang, &sn, &cs);
+  // lanes 0..2 hold the results: v_readlane into SGPRs (a ds_bpermute per half costs an LDS trip)
+  vec6_to_matrix_sc(x, readlane_f64(cs, 0), readlane_f64(sn, 0), readlane_f64(cs, 1),
+                    readlane_f64(sn, 1), readlane_f64(cs, 2), readlane_f64(sn, 2), T);
+}
+#endif
 
 // C = A · B for row-major affine 4×4 (bottom rows 0 0 0 1): matmul4's sums in its order, without
 // the terms that multiply by the bottom row's exact 0 / 1 (equal values; the sign of an exact zero

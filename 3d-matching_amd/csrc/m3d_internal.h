@@ -161,6 +161,12 @@ constexpr int kMeshBruteTile = 256;
 // 4 % faster at F = 1024; brute force grows by 0.63 µs per triangle and meets the grid's flat
 // 0.62 ms at F ≈ 980
 constexpr int kMeshAutoBruteMax = 960;
+// m3d_mesh_icp_* path 0: the same choice for the radius-bounded scan of ICP against a mesh, which is
+// cheaper on the grid than the unbounded query.  Measured with 180k points at r = 0.12
+// (tools/mesh_icp_timing.py): brute force 169 µs against the grid's 225–256 µs at
+// F = 256, 355 µs against 248–281 µs at F = 576; brute force grows by 0.58 µs per triangle and meets
+// the grid between F ≈ 370 (unseeded) and 420 (seeded)
+constexpr int kMeshIcpAutoBruteMax = 400;
 
 // Device scratch for the temporaries of setup work (grid sorts, Morton copies, cloud packing):
 // grown on demand and owned by the context.  Setup work runs in stream order, so consecutive
@@ -775,6 +781,33 @@ hipError_t mesh_closest_brute(const m3d_mesh* m, const double* xyz, int64_t n, c
 hipError_t mesh_closest_grid(m3d_ctx* ctx, m3d_mesh* m, const double* xyz, int64_t n, const double* T, double r0,
                              double* d2, int32_t* tri, double* point, double* uv, uint8_t* region, void* scratch,
                              hipStream_t st, std::string* why);
+// the triangle grid of a mesh with usable triangles, built once (mesh.hip; synchronous)
+hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why);
+// ICP against a mesh (mesh_icp.hip): the device arrays of one loop, every per-point array in the
+// source's Morton slot order.  state: an IcpState of the loop's own (T, dT, last_upd, fitness, rmse,
+// the previous pair, count, evals, iters, done, converged and r2 are used: the struct launch_reduce
+// reads `done` from); tri / d2 / pt: the scan's records (tri doubles as the next scan's seed).
+struct MeshIcpLoop {
+  IcpState* state = nullptr;
+  double* pcd64 = nullptr;     // ns×3, the loop's points
+  int32_t* tri = nullptr;      // ns
+  double* d2 = nullptr;        // ns
+  double* pt = nullptr;        // ns×3
+  double* partials = nullptr;  // side_terms_blocks(ns) × kTermSlots
+  double* sums = nullptr;      // kTermSlots
+  int64_t ns = 0;
+  double max_dist = 0.0;
+};
+// enqueue only.  scan: brute force, or the one-box grid scan (the mesh's grid is built; seed: L.tri
+// holds each point's seed triangle); terms: the rows of kind / k and their reduce → sums; solve:
+// the RegistrationICP rule on sums
+hipError_t launch_mesh_icp_scan(const m3d_mesh* m, const MeshIcpLoop& L, bool brute, bool seed, hipStream_t st);
+hipError_t launch_mesh_icp_terms(const m3d_mesh* m, const MeshIcpLoop& L, int32_t kind, double k, double* sums,
+                                 hipStream_t st);
+hipError_t launch_mesh_icp_solve(const MeshIcpLoop& L, const double* sums, const m3d_icp_params& p, hipStream_t st);
+// dst[k] = v[slot[k]] / dst[slot[k]] = v[k], k < n
+hipError_t launch_gather_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst, hipStream_t st);
+hipError_t launch_scatter_f64(const double* v, const int32_t* slot, int64_t n, double* dst, hipStream_t st);
 size_t fgr_terms_scratch_bytes(int64_t n);
 // one iteration's sums over n ≥ 1 given rows (path as m3d_fgr_params.path) → sums27 [host].  Synchronous.
 hipError_t fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, int path,

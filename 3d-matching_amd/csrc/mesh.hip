@@ -7,7 +7,7 @@
 // The query is p, or q64_of(T, p) (nnkey.h) when a transform is given.  A triangle is (a, b, c),
 // the fp64 vertices its three indices name.  closest(p, tri) is Ericson's closest point on a
 // triangle (Real-Time Collision Detection §5.1.5), the seven Voronoi regions tested in this order —
-// tri_closest below is the ONE function both kernels call:
+// tri_closest (mesh_tri.h) is the ONE function every kernel calls:
 //   ab = b−a, ac = c−a, ap = p−a; d1 = ab·ap, d2 = ac·ap.
 //     region 0 (A)  if d1 ≤ 0 && d2 ≤ 0:                       point a,            (v, w) = (0, 0)
 //   bp = p−b; d3 = ab·bp, d4 = ac·bp.
@@ -93,6 +93,7 @@
 
 #include "m3d_internal.h"
 #include "knn_wave.h"
+#include "mesh_tri.h"
 
 namespace m3d {
 namespace {
@@ -102,63 +103,6 @@ constexpr int kMaxRounds = 64;               // host bound of the ladder
 constexpr int64_t kMaxCellsAxis = 1024;      // cells per axis
 constexpr int64_t kMaxCells = (int64_t)1 << 24;
 constexpr int kRefsPerTri = 16;              // the count pass's condition: references ≤ 16·F
-
-struct TriHit {
-  double d2, pt[3], v, w;
-  int region;
-};
-
-__device__ __forceinline__ double dot3(const double* x, const double* y) {
-  return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
-}
-
-// closest(p, (a, b, c)) of the contract
-__device__ __forceinline__ void tri_closest(const double* a, const double* b, const double* c, const double* p,
-                                            TriHit& h) {
-  const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-  const double ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-  const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-  auto done = [&](int region, double x, double y, double z, double v, double w) {
-    h.pt[0] = x, h.pt[1] = y, h.pt[2] = z;
-    h.v = v, h.w = w, h.region = region;
-    h.d2 = d2_exact(h.pt, p);
-  };
-  if (d1 <= 0.0 && d2 <= 0.0) return done(0, a[0], a[1], a[2], 0.0, 0.0);
-  const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
-  const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-  if (d3 >= 0.0 && d4 <= d3) return done(1, b[0], b[1], b[2], 1.0, 0.0);
-  const double vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-    const double v = d1 / (d1 - d3);
-    return done(3, a[0] + ab[0] * v, a[1] + ab[1] * v, a[2] + ab[2] * v, v, 0.0);
-  }
-  const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-  const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-  if (d6 >= 0.0 && d5 <= d6) return done(2, c[0], c[1], c[2], 0.0, 1.0);
-  const double vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-    const double w = d2 / (d2 - d6);
-    return done(4, a[0] + ac[0] * w, a[1] + ac[1] * w, a[2] + ac[2] * w, 0.0, w);
-  }
-  const double va = d3 * d6 - d5 * d4;
-  if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-    const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-    return done(5, b[0] + (c[0] - b[0]) * w, b[1] + (c[1] - b[1]) * w, b[2] + (c[2] - b[2]) * w, 1.0 - w, w);
-  }
-  const double s = (va + vb) + vc;
-  const double v = vb / s, w = vc / s;
-  return done(6, (a[0] + ab[0] * v) + ac[0] * w, (a[1] + ab[1] * v) + ac[1] * w, (a[2] + ab[2] * v) + ac[2] * w, v,
-              w);
-}
-
-// a running (d², index) minimum: a NaN d² never enters, the first candidate always does
-__device__ __forceinline__ void take_min(double& bd, int32_t& bt, double d, int32_t t) {
-  if (t >= 0 && d == d && (bt < 0 || key_less(d, t, bd, bt))) {
-    bd = d;
-    bt = t;
-  }
-}
 
 // the optional query transform, by value (12 doubles: the rows of [R | t])
 struct MeshXf {
@@ -293,25 +237,6 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_pack_kernel(const double* __r
 }
 
 // ------------------------------------------------------------------------------- the grid
-// an fp32 at or below the real x − w / at or above the real x + w (w ≥ 0; header, (1))
-__device__ __forceinline__ float below(double x, float w) {
-  return nextafterf(__double2float_rd(x - (double)w), -INFINITY);
-}
-__device__ __forceinline__ float above(double x, float w) {
-  return nextafterf(__double2float_ru(x + (double)w), INFINITY);
-}
-
-// a triangle's cell range: its box's fp32 ends rounded outward and widened by the margin (header, (1))
-__device__ __forceinline__ void tri_cells(const double* __restrict__ t9, const TriGridDev& g, int lo[3], int hi[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double mn = fmin(fmin(t9[k], t9[3 + k]), t9[6 + k]);
-    const double mx = fmax(fmax(t9[k], t9[3 + k]), t9[6 + k]);
-    lo[k] = grid_coord(below(mn, g.margin), g.o[k], g.inv_h, g.n[k]);
-    hi[k] = grid_coord(above(mx, g.margin), g.o[k], g.inv_h, g.n[k]);
-  }
-}
-
 // the references a grid would hold (no per-cell work): Σ over usable triangles of their cell count
 __global__ __launch_bounds__(kMeshBlock) void tri_refs_total_kernel(const double* __restrict__ tri9,
                                                                     const uint8_t* __restrict__ ok, int64_t nf,
@@ -467,18 +392,6 @@ struct MeshScratch {
   }
 };
 
-// (float)x rounded toward −inf / +inf on the host
-float float_down(double x) {
-  float f = (float)x;
-  if ((double)f > x) f = std::nextafterf(f, -INFINITY);
-  return f;
-}
-float float_up(double x) {
-  float f = (float)x;
-  if ((double)f < x) f = std::nextafterf(f, INFINITY);
-  return f;
-}
-
 // the grid of cell h over the mesh's box: origin below every widened triangle end, dimensions
 // clamped to ≥ 1; false when it would hold more cells than the budget
 bool grid_shape(const m3d_mesh* m, double h, TriGridDev* g) {
@@ -535,7 +448,7 @@ hipError_t mesh_upload(m3d_mesh* m, hipStream_t st, int* bad_index) {
 }
 
 // the triangle grid of a mesh with usable triangles, built once (synchronous)
-static hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why) {
+hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why) {
   if (m->grid_built) return hipSuccess;
   if (m->gblock != nullptr) {  // a build that failed half way
     block_release(m->gblock);

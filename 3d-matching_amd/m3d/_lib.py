@@ -236,6 +236,10 @@ SIGNATURES = {
     "m3d_mesh_destroy": (None, [vp]),
     "m3d_mesh_size": (i64, [vp]),
     "m3d_mesh_closest": (C.c_int, [vp, vp, vp, i64, C.POINTER(dbl), i32, dbl, vp, vp, vp, vp, vp, vp]),
+    "m3d_mesh_icp_terms": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(RobustKernel), i32, vp,
+                                     C.POINTER(dbl), vp, vp, vp]),
+    "m3d_mesh_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams), C.POINTER(RobustKernel),
+                                   i32, i32, C.POINTER(IcpResult), vp, vp]),
     "m3d_mesh_grid_info": (C.c_int, [vp, C.POINTER(i64)]),
     "m3d_mesh_brute_tile": (i32, []),
     "m3d_mesh_auto_brute_max": (i32, []),

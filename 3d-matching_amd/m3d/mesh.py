@@ -7,12 +7,17 @@ What an Open3D user runs after registering a CAD model against a scan and its re
 | ``o3d.io.read_triangle_mesh(path)`` (STL)                      | ``read_triangle_mesh``                 |
 | ``t.geometry.RaycastingScene.add_triangles``                   | ``RaycastingScene.add_triangles``      |
 | ``RaycastingScene.compute_closest_points`` / ``compute_distance`` | the same methods, ``closest_points`` |
+| ``registration_icp`` against points sampled from the model      | ``icp_to_mesh`` (``matcher.registration_icp_to_mesh``): the surface itself as target |
 
 The contract is mesh.hip's (restated in numpy by tests/mesh_restatement.py): Ericson's closest point
 on a triangle in fp64 in one fixed operation order, the winner the smallest (d², triangle index)
 over every usable triangle.  Queries are float64 (n, 3); the arithmetic runs on the GPU, the brute
 force path and the grid path return the same bits.  Parity with Open3D itself is unpinned (Embree
 works in float32).  Ray casting, occupancy and signed distance (ray parity in Open3D) are not here.
+
+``icp_to_mesh`` / ``icp_to_mesh_terms`` are mesh_icp.hip's loop and its one-evaluation hook
+(restated by tests/mesh_icp_restatement.py): point-to-plane ICP whose target is the closest point
+on the mesh's surface with the winning triangle's face normal.
 """
 
 from __future__ import annotations
@@ -24,7 +29,8 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["TriangleMesh", "RaycastingScene", "read_triangle_mesh", "closest_points"]
+__all__ = ["TriangleMesh", "RaycastingScene", "read_triangle_mesh", "closest_points", "icp_to_mesh",
+           "icp_to_mesh_terms"]
 
 INVALID_ID = np.uint32(0xFFFFFFFF)  # Open3D RaycastingScene.INVALID_ID
 
@@ -162,6 +168,60 @@ def closest_points(mesh: TriangleMesh, points, transformation=None, path=None, r
                                        ptr(pt), ptr(uv), ptr(reg), stream_handle()), "mesh_closest")
     return {"d2": d2[:n].cpu().numpy(), "triangle": tri[:n].cpu().numpy(), "point": pt[:n].cpu().numpy(),
             "uv": uv[:n].cpu().numpy(), "region": reg[:n].cpu().numpy()}
+
+
+# The seeded box of the grid scan (mesh_icp.hip) never changes a bit of the result; it is on by
+# default only where it measured faster than the unseeded scan (DESIGN §3.21, 180k points, r = 0.12):
+# slower by 4–14 % up to 2,304 triangles, equal at 4,096, faster from 16,384 on (2 × at 435,600).
+ICP_SEED_MIN_TRIANGLES = 4096
+
+
+def icp_to_mesh_terms(src, mesh: TriangleMesh, T=None, max_dist: float = 0.0, kernel=None, path=None,
+                      seed_triangles=None):
+    """m3d_mesh_icp_terms: ONE evaluation of ``src`` (an ``m3d.core.Cloud``) against ``mesh`` at the
+    transform ``T`` → (sums (30,) f64 in ``robust_terms``' layout, triangle (ns,) int32 with −1 for
+    an unmatched point, d2 (ns,) f64 with inf).  ``seed_triangles`` (ns,) int32 or None: the
+    triangles the grid scan tries first; they change the work, never the result."""
+    from .core import _T16, _colored_kernel, _torch, device_empty, ptr, stream_handle, to_device
+
+    ctx, h = mesh._handle()
+    torch = _torch()
+    n = src.n
+    tri = device_empty((max(n, 1),), torch.int32)
+    d2 = device_empty((max(n, 1),), torch.float64)
+    seed = None
+    if seed_triangles is not None:
+        seed = to_device(np.ascontiguousarray(seed_triangles, np.int32).reshape(-1), "int32", ())
+        if seed.shape[0] != n:
+            raise ValueError(f"seed_triangles must be ({n},)")
+    rk = _colored_kernel(kernel)  # L2 handed on: this loop has one terms pass for every kind
+    sums = (C.c_double * 32)()
+    ctx.check(ctx.lib.m3d_mesh_icp_terms(ctx.h, h, src.h, _T16(np.eye(4) if T is None else T), float(max_dist),
+                                         None if rk is None else C.byref(rk), _PATHS[path],
+                                         ptr(seed), sums, ptr(tri), ptr(d2), stream_handle()),
+              "mesh_icp_terms")
+    return np.array(sums[:30]), tri[:n].cpu().numpy(), d2[:n].cpu().numpy()
+
+
+def icp_to_mesh(src, mesh: TriangleMesh, max_dist: float, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
+                max_iteration=30, kernel=None, path=None, seed=None):
+    """m3d_mesh_icp_run: registration_icp of ``src`` (an ``m3d.core.Cloud``) against the surface of
+    ``mesh`` → ``m3d.core.IcpOutcome`` whose correspondence_set is (M, 2): source index, triangle
+    index.  ``seed``: the grid scan's seeded box (None: on from
+    ``ICP_SEED_MIN_TRIANGLES`` triangles)."""
+    from .core import _T16, _colored_kernel, _outcome, _torch, device_empty, ptr, stream_handle
+
+    ctx, h = mesh._handle()
+    p = _lib.IcpParams(float(relative_fitness), float(relative_rmse), int(max_iteration), _lib.EST_POINT_TO_PLANE,
+                       _lib.NN_GRID, 0)
+    rk = _colored_kernel(kernel)
+    res = _lib.IcpResult()
+    tri = device_empty((max(src.n, 1),), _torch().int32)
+    use_seed = len(mesh.triangles) >= ICP_SEED_MIN_TRIANGLES if seed is None else bool(seed)
+    ctx.check(ctx.lib.m3d_mesh_icp_run(ctx.h, h, src.h, _T16(np.eye(4) if init is None else init), float(max_dist),
+                                       C.byref(p), None if rk is None else C.byref(rk), _PATHS[path],
+                                       int(use_seed), C.byref(res), ptr(tri), stream_handle()), "mesh_icp_run")
+    return _outcome(ctx, res, tri, src.n, True)
 
 
 class RaycastingScene:

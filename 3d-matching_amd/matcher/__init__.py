@@ -23,6 +23,11 @@ from .fgr import (
 )
 from .gicp import registration_generalized_icp
 from .icp import refine_registration, registration_icp
+from .mesh_icp import (
+    evaluate_registration_to_mesh,
+    refine_registration_to_mesh,
+    registration_icp_to_mesh,
+)
 from .ransac import (
     compute_feature_correspondences,
     compute_step_transformation,
@@ -48,6 +53,7 @@ __all__ = [
     "evaluate_inlier_ratio",
     "evaluate_inlier_ratio_fast",
     "evaluate_registration",
+    "evaluate_registration_to_mesh",
     "get_information_matrix_from_point_clouds",
     "global_registration",
     "global_registration_fgr",
@@ -55,8 +61,10 @@ __all__ = [
     "registration_fgr_based_on_feature_matching",
     "run_ransac",
     "refine_registration",
+    "refine_registration_to_mesh",
     "registration_colored_icp",
     "registration_generalized_icp",
     "registration_icp",
+    "registration_icp_to_mesh",
     "register",
 ]

@@ -80,7 +80,8 @@ int m3d_get_stats(m3d_ctx* ctx, int64_t* out8 /* [host] 8 values */);
 #define M3D_KERNEL_SCORE 1  /* RANSAC fp32 scoring screen       */
 #define M3D_KERNEL_KABSCH 2 /* RANSAC batched 3-point Kabsch    */
 #define M3D_KERNEL_TERMS 3  /* ICP fp64 estimation terms        */
-#define M3D_KERNEL_LOOP 4   /* reserved (ABI 10-11: the persistent grid loop, removed in ABI 12) */
+#define M3D_KERNEL_LOOP 4   /* the solve launch of the side-terms loops (robust, Generalized, Colored, mesh ICP);
+                               also used by other calls' own stages (ABI 10-11: the persistent grid loop) */
 #define M3D_KERNEL_COMM 5   /* RCCL all-reduces issued by the library, on their streams (ABI 10) */
 int m3d_profile_enable(m3d_ctx* ctx, int enable);
 /* Synchronises, returns Σ launch durations (ms) and launch count since the last read, resets. */
@@ -948,6 +949,44 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4);
  * to which path 0 takes it */
 int32_t m3d_mesh_brute_tile(void);
 int32_t m3d_mesh_auto_brute_max(void);
+
+/* ------------------------------------------------------------------ ICP against a mesh (mesh_icp.hip)
+ * registration_icp with the SURFACE of a triangle mesh as target (added within ABI 13, the version
+ * number is unchanged): m3d_icp_run's loop — the transformed copy of the source, `init` applied
+ * unless isIdentity(), fitness / inlier_rmse, the convergence rule, the LDLT solve, the slot layout
+ * and the fixed summation order are its — with, for every point p of an evaluation,
+ *   the winner     m3d_mesh_closest's: the smallest (d², triangle index) over every usable
+ *                  triangle, q its closest point;
+ *   the match      d² < max_dist·max_dist in fp64, strictly (a NaN point never matches);
+ *   the row        n = the winning triangle's unit face normal (b − a) × (c − a) / |·|,
+ *                  r = (p − q) · n, J = [p × n | n], weighted by `kernel` as m3d_robust_terms' rows
+ *                  (NULL or kind L2: weight 1).
+ * Restated in numpy by tests/mesh_icp_restatement.py.  path: 0 automatic, 1 brute force, 2 the
+ * triangle grid (one box of half-width max_dist per point: a triangle outside it is farther than
+ * max_dist by m3d_mesh_closest's covering argument, so no radius ladder is needed).  Both paths,
+ * the seeded box on or off, and repeated calls return the same bits.  Not implemented: point-to-point
+ * estimation, Generalized and Colored ICP against a mesh, sharding over devices, a step-wise driver.
+ * M3D_ERR_INVALID: max_dist <= 0 or not finite, an unknown kernel kind, a k <= 0 or non-finite
+ * for a kind that reads k, a mesh without a usable triangle, an unknown path.  An empty source is
+ * not an error: fitness 0, T = init, no pairs.  Both calls are synchronous.
+ *
+ * m3d_mesh_icp_terms: ONE evaluation at T_host [host] 16 f64 (NULL = identity; applied unless
+ * isIdentity()) → sums_out [host] 32 f64 in m3d_robust_terms' layout (0..20 JtJ upper triangle,
+ * 21..26 Jtr, 27 sum r², 28 count, 29 sum d²).  seed_tri [device] ns int32 or NULL: per source point
+ * (caller's order) a triangle to try first — the grid path then cuts the point's box with that
+ * triangle's distance when it is below max_dist (−1, or an unusable triangle: no seed); it never
+ * changes a bit of the result.  tri_idx [device] ns int32 or NULL: the matched triangle per source
+ * point in the caller's order (−1 none); d2_out [device] ns f64 or NULL: its d² (+inf none). */
+int m3d_mesh_icp_terms(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const double* T_host, double max_dist,
+                       const m3d_robust_kernel* kernel, int32_t path, const int32_t* seed_tri, double* sums_out,
+                       int32_t* tri_idx, double* d2_out, void* stream);
+/* The whole registration from init [host] 16 f64 (NULL = identity).  params->estimation must be
+ * M3D_EST_POINT_TO_PLANE (else M3D_ERR_INVALID); params->nn_method and flags are not read.  seed:
+ * non-zero = from the second evaluation on every point's box is cut with the distance of the
+ * triangle it matched last.  tri_idx as above, of the last evaluation. */
+int m3d_mesh_icp_run(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const double* init, double max_dist,
+                     const m3d_icp_params* params, const m3d_robust_kernel* kernel, int32_t path, int32_t seed,
+                     m3d_icp_result* out, int32_t* tri_idx, void* stream);
 
 /* ------------------------------------------------------------------ test hooks
  * Host-compiled copy of the device 3×3 linear algebra (same source), for CPU-side unit tests
