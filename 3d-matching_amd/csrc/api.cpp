@@ -1517,12 +1517,18 @@ bool eigen_is_identity(const double* T) {
   return true;
 }
 
+// RegistrationICP (Registration.cpp): pcd = source; if (!init.isIdentity()) pcd.Transform(init) —
+// whether a loop's points start as init·p, decided here for the cloud loops and the mesh loop alike
+// (open3d_init false: always)
+bool apply_init_of(const double* T, bool open3d_init) { return !(open3d_init && eigen_is_identity(T)); }
+
+const double kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
 int icp_reset(m3d_icp* s, const double* init, bool open3d_init, void* stream) {
   if (!s) return M3D_ERR_INVALID;
   Touch tch{s->ctx, S(stream)};
   m3d_ctx* ctx = s->ctx;
-  double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  const double* T = init ? init : I;
+  const double* T = init ? init : kIdentity16;
   hipSetDevice(ctx->device);
   hipStream_t st = S(stream);
   HIPX(ctx, hipMemsetAsync(s->corr, 0xFF, sizeof(int32_t) * std::max<int64_t>(s->src->n, 1), st));
@@ -1531,8 +1537,7 @@ int icp_reset(m3d_icp* s, const double* init, bool open3d_init, void* stream) {
   // the deferral list's count, ticket and fault word start at zero on the caller's stream (the
   // heavy kernel re-zeroes count and ticket after each scan; a reset also clears a fault)
   if (s->hcnt != nullptr) HIPX(ctx, hipMemsetAsync(s->hcnt, 0, kDeferWords * sizeof(uint32_t), st));
-  // RegistrationICP (Registration.cpp): pcd = source; if (!init.isIdentity()) pcd.Transform(init)
-  HIPX(ctx, launch_icp_reset(s, T, !(open3d_init && eigen_is_identity(T)), st));
+  HIPX(ctx, launch_icp_reset(s, T, apply_init_of(T, open3d_init), st));
   s->keys_clean = false;
   return M3D_OK;
 }
@@ -1751,18 +1756,19 @@ int defer_fault(m3d_ctx* ctx, uint32_t count, bool fault) {
                   "grid NN deferral list overflow (count " + std::to_string(count) +
                       "): results since the last m3d_icp_reset are invalid");
 }
-}  // namespace
 
-int m3d_icp_result_get(m3d_icp* s, m3d_icp_result* out, void* stream) {
-  if (!s || !out) return M3D_ERR_INVALID;
-  Touch tch{s->ctx, S(stream)};
-  m3d_ctx* ctx = s->ctx;
+// The result of a loop: its state and — hcnt given — the grid scan's deferral header copied back on
+// st, one stream sync (on every path: the stream is idle when this returns), the deferral fault,
+// then the fields.  what: the caller's name in a HIP error's text.
+int read_result(m3d_ctx* ctx, const char* what, const IcpState* state, const uint32_t* hcnt, m3d_icp_result* out,
+                hipStream_t st) {
   IcpState h;
   uint32_t defer[kDeferWords] = {0, 0, 0, 0};
-  HIPX(ctx, hipMemcpyAsync(&h, s->state, sizeof(h), hipMemcpyDeviceToHost, S(stream)));
-  if (s->hcnt != nullptr)
-    HIPX(ctx, hipMemcpyAsync(defer, s->hcnt, sizeof(defer), hipMemcpyDeviceToHost, S(stream)));
-  HIPX(ctx, hipStreamSynchronize(S(stream)));
+  hipError_t e = hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && hcnt != nullptr) e = hipMemcpyAsync(defer, hcnt, sizeof(defer), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   if (const int rc = defer_fault(ctx, defer[0], defer[kDeferFault] != 0)) return rc;
   for (int k = 0; k < 16; ++k) {
     out->T[k] = h.T[k];
@@ -1774,6 +1780,13 @@ int m3d_icp_result_get(m3d_icp* s, m3d_icp_result* out, void* stream) {
   out->iterations = h.iters;
   out->converged = h.converged;
   return M3D_OK;
+}
+}  // namespace
+
+int m3d_icp_result_get(m3d_icp* s, m3d_icp_result* out, void* stream) {
+  if (!s || !out) return M3D_ERR_INVALID;
+  Touch tch{s->ctx, S(stream)};
+  return read_result(s->ctx, "m3d_icp_result_get", s->state, s->hcnt, out, S(stream));
 }
 
 int m3d_corr_pairs(m3d_ctx* ctx, const int32_t* corr_idx, int64_t n, int32_t* pairs_out, int64_t* count,
@@ -3197,10 +3210,14 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4) {
 }
 
 // ------------------------------------------------------------------------------- ICP against a mesh
-// mesh_icp.hip.  A loop of its own around the mesh (m3d_icp is bound to a target cloud's NN): the
-// arrays from the context's run arena (the calls synchronise before returning), the source in the
-// Morton slot order of its cloud, the mesh's grid built on first use.  Profiling (m3d_profile_*): the
-// scan under M3D_KERNEL_NN, terms + reduce under M3D_KERNEL_TERMS, the solve under M3D_KERNEL_LOOP.
+// mesh_icp.hip.  A loop of its own around the mesh only where m3d_icp is bound to a target cloud's
+// NN — the scan and its arrays.  The state's reset, the solve and the result read are the cloud
+// loops' (launch_icp_state_init, launch_icp_solve_state, read_result).  The arrays come from the
+// context's run arena (the calls synchronise before returning), the source is in the Morton slot
+// order of its cloud, the mesh's grid is built on first use.  `init` is affine, as every documented
+// input is and matmul4_affine assumes: the state starts with the bottom row (0, 0, 0, 1) whatever
+// the caller's last four values, m3d_icp_reset's rule.  Profiling (m3d_profile_*): the scan under
+// M3D_KERNEL_NN, terms + reduce under M3D_KERNEL_TERMS, the solve under M3D_KERNEL_LOOP.
 extern "C++" {
 namespace {
 struct MeshIcpCall {
@@ -3252,22 +3269,12 @@ int mesh_icp_setup(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const dou
   if (ctx->run.reserve(cv.bytes()) != hipSuccess)
     return m3d_fail(ctx, M3D_ERR_OOM, "device allocation failed (mesh ICP loop arrays)");
   cv.place(ctx->run.base);
-  // RegistrationICP: pcd = source; if (!init.isIdentity()) pcd.Transform(init) — by the first query
-  IcpState h;
-  memset(&h, 0, sizeof h);
-  for (int k = 0; k < 16; ++k) {
-    const double I = (k % 5 == 0) ? 1.0 : 0.0;
-    h.T[k] = init != nullptr ? init[k] : I;
-    h.dT[k] = init != nullptr && !eigen_is_identity(init) ? init[k] : I;
-    h.last_upd[k] = I;
-  }
-  h.r2 = max_dist * max_dist;
-  HIPX(ctx, hipMemcpyAsync(L.state, &h, sizeof h, hipMemcpyHostToDevice, st));
   if (L.ns > 0) {
     HIPX(ctx, hipMemcpyAsync(L.pcd64, c->ms->xyz64, sizeof(double) * 3 * (size_t)L.ns, hipMemcpyDeviceToDevice, st));
     HIPX(ctx, hipMemsetAsync(L.tri, 0xFF, sizeof(int32_t) * (size_t)L.ns, st));  // no seed, no match: −1
   }
-  HIPX(ctx, hipStreamSynchronize(st));  // h leaves scope
+  const double* T = init != nullptr ? init : kIdentity16;
+  HIPX(ctx, launch_icp_state_init(L.state, T, apply_init_of(T, true), max_dist * max_dist, mesh_icp_frame(), st));
   return M3D_OK;
 }
 }  // namespace
@@ -3285,8 +3292,11 @@ int m3d_mesh_icp_terms(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const
   const int rc = mesh_icp_setup(ctx, mesh, src, T_host, max_dist, kernel, path, &c, st);
   if (rc) return rc;
   const MeshIcpLoop& L = c.L;
-  if (L.ns == 0) return M3D_OK;
   hipError_t e = hipSuccess;
+  if (L.ns == 0) {  // nothing to scan; the state's reset is in flight on the arena
+    HIPX(ctx, hipStreamSynchronize(st));
+    return M3D_OK;
+  }
   if (seed_tri != nullptr) e = launch_gather_i32(seed_tri, c.ms->slot, L.ns, L.tri, st);
   if (e == hipSuccess) e = launch_mesh_icp_scan(mesh, L, c.brute, seed_tri != nullptr, st);
   if (e == hipSuccess) e = launch_mesh_icp_terms(mesh, L, c.kind, c.k, L.sums, st);
@@ -3330,32 +3340,19 @@ int m3d_mesh_icp_run(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const d
       }
       if (e == hipSuccess) {
         KTimer kt(ctx, M3D_KERNEL_LOOP, st);
-        e = launch_mesh_icp_solve(L, L.sums, *params, st);
+        e = launch_icp_solve_state(L.state, L.sums, params->relative_fitness, params->relative_rmse, params->max_iteration,
+                                   M3D_EST_POINT_TO_PLANE, L.ns, kIdentity16, mesh_icp_frame(), st);
       }
     }
     return e == hipSuccess ? M3D_OK : m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh ICP step: ") + hipGetErrorString(e));
   };
   rc = run_chunked(ctx, L.state, params->max_iteration + 1, step, st);
-  IcpState h;
   hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpyAsync(&h, L.state, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && tri_idx != nullptr) e = launch_scatter_i32(L.tri, L.ns > 0 ? c.ms->slot : nullptr, L.ns, tri_idx, st);
-  }
-  const hipError_t es = hipStreamSynchronize(st);  // the arena is idle when the call returns
-  if (rc) return rc;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh_icp_run: ") + hipGetErrorString(e));
-  for (int k = 0; k < 16; ++k) {
-    out->T[k] = h.T[k];
-    out->update[k] = h.last_upd[k];
-  }
-  out->fitness = h.fitness;
-  out->inlier_rmse = h.rmse;
-  out->num_correspondences = h.count;
-  out->iterations = h.iters;
-  out->converged = h.converged;
-  return M3D_OK;
+  if (!rc && tri_idx != nullptr) e = launch_scatter_i32(L.tri, L.ns > 0 ? c.ms->slot : nullptr, L.ns, tri_idx, st);
+  // the arena is idle when the call returns: read_result synchronises, a failed call here
+  if (!rc && e == hipSuccess) return read_result(ctx, "mesh_icp_run", L.state, nullptr, out, st);
+  (void)hipStreamSynchronize(st);
+  return rc ? rc : m3d_fail(ctx, M3D_ERR_HIP, std::string("mesh_icp_run: ") + hipGetErrorString(e));
 }
 
 int32_t m3d_mesh_brute_tile(void) { return kMeshBruteTile; }

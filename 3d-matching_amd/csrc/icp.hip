@@ -41,13 +41,7 @@ constexpr double kU64 = 1.1102230246251565e-16;
 
 
 // ------------------------------------------------------------------------------- state
-struct FrameParams {
-  double cs[3], ct[3];
-  double pinf, qinf;
-  double s16;  // the target cloud's fp16 operand scale (power of two)
-  int shared;  // the target's frame is shared by every shard (m3d_cloud_create_framed)
-};
-
+// FrameParams: m3d_internal.h
 // Refresh the fp32 search transform and radius bound for transform T (device side; T and
 // r2 = s->r2 passed in registers by the solve, which has them already).
 // fp64 → fp32 rounded toward +inf on the vector unit (the library's __double2float_ru bounces the
@@ -1050,10 +1044,17 @@ __global__ __launch_bounds__(256) void nn_finalize_kernel(const double* __restri
   if (d2out != nullptr) d2out[o] = w.gj >= 0 ? w.d : INFINITY;
 }
 
-__global__ void scatter_i32_kernel(const int32_t* __restrict__ v, const int32_t* __restrict__ slot,
-                                   int64_t n, int32_t* __restrict__ dst) {
+// An order change by a slot table: dst[slot[k]] = v[k] (slot order → the caller's order), or with
+// kGather dst[k] = v[slot[k]] (the caller's order → slot order)
+template <typename V, bool kGather>
+__global__ void permute_kernel(const V* __restrict__ v, const int32_t* __restrict__ slot, int64_t n,
+                               V* __restrict__ dst) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k < n) dst[slot[k]] = v[k];
+  if (k >= n) return;
+  if (kGather)
+    dst[k] = v[slot[k]];
+  else
+    dst[slot[k]] = v[k];
 }
 
 // ------------------------------------------------------------------------------- pairs
@@ -1197,14 +1198,18 @@ static hipError_t reset_plan_counts(const m3d_icp* s, hipStream_t st) {
   return hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t), st);
 }
 
+hipError_t launch_icp_state_init(IcpState* state, const double* T, bool apply_init, double r2, const FrameParams& f,
+                                 hipStream_t st) {
+  icp_init_kernel<<<1, 64, 0, st>>>(state, T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11],
+                                    r2, f, apply_init ? 1 : 0);
+  return hipGetLastError();
+}
+
 hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st) {
   hipError_t e = reset_points(s, st);
   if (e == hipSuccess) e = reset_plan_counts(s, st);
   if (e != hipSuccess) return e;
-  icp_init_kernel<<<1, 64, 0, st>>>(s->state, T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7],
-                                    T[8], T[9], T[10], T[11], s->max_dist * s->max_dist,
-                                    frame_of(s), apply_init ? 1 : 0);
-  return hipGetLastError();
+  return launch_icp_state_init(s->state, T, apply_init, s->max_dist * s->max_dist, frame_of(s), st);
 }
 
 hipError_t launch_icp_set_T(const m3d_icp* s, const double* T_dev, hipStream_t st) {
@@ -1435,10 +1440,24 @@ hipError_t launch_icp_terms_reduce(const m3d_icp* s, int64_t off, const int32_t*
   return hipGetLastError();
 }
 
+hipError_t launch_icp_solve_state(IcpState* state, const double* sums, double relative_fitness, double relative_rmse,
+                                  int32_t max_iteration, int32_t estimation, int64_t ns, const double* center,
+                                  const FrameParams& f, hipStream_t st) {
+  SolveParams sp;
+  sp.rel_fit = relative_fitness;
+  sp.rel_rmse = relative_rmse;
+  sp.max_iter = max_iteration;
+  sp.est = estimation;
+  sp.ns = ns;
+  for (int k = 0; k < 3; ++k) sp.c[k] = center[k];
+  sp.f = f;
+  with_est(sp.est, [&](auto e) { solve_kernel<decltype(e)::value><<<1, 64, 0, st>>>(sums, state, sp); });
+  return hipGetLastError();
+}
+
 hipError_t launch_icp_solve(const m3d_icp* s, const double* sums, hipStream_t st) {
   const SolveParams sp = solve_params(s);
-  with_est(sp.est, [&](auto e) { solve_kernel<decltype(e)::value><<<1, 64, 0, st>>>(sums, s->state, sp); });
-  return hipGetLastError();
+  return launch_icp_solve_state(s->state, sums, sp.rel_fit, sp.rel_rmse, sp.max_iter, sp.est, sp.ns, sp.c, sp.f, st);
 }
 
 hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st) {
@@ -1461,12 +1480,23 @@ hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStr
   return hipGetLastError();
 }
 
+template <typename V, bool kGather>
+static hipError_t launch_permute(const V* v, const int32_t* slot, int64_t n, V* dst, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  permute_kernel<V, kGather><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(v, slot, n, dst);
+  return hipGetLastError();
+}
+
 hipError_t launch_scatter_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst,
                               hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  if (slot == nullptr) return hipMemcpyAsync(dst, v, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st);
-  scatter_i32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(v, slot, n, dst);
-  return hipGetLastError();
+  if (n > 0 && slot == nullptr) return hipMemcpyAsync(dst, v, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st);
+  return launch_permute<int32_t, false>(v, slot, n, dst, st);
+}
+hipError_t launch_gather_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst, hipStream_t st) {
+  return launch_permute<int32_t, true>(v, slot, n, dst, st);
+}
+hipError_t launch_scatter_f64(const double* v, const int32_t* slot, int64_t n, double* dst, hipStream_t st) {
+  return launch_permute<double, false>(v, slot, n, dst, st);
 }
 
 hipError_t launch_corr_pairs(const int32_t* v, int64_t n, int32_t* cnt, int32_t* pairs, hipStream_t st) {

@@ -477,8 +477,7 @@ M3D_HD void matmul4(const double A[16], const double B[16], double C[16]) {
 }
 
 #ifdef __HIPCC__
-// (device only: one wave calls it, every lane with the same x — the solve kernels of icp.hip and
-// mesh_icp.hip)
+// (device only: one wave calls it, every lane with the same x — the solve kernels of icp.hip)
 // vec6_to_matrix with the three sincos evaluated in lanes 0..2 at once (whole wave calls it)
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   const uint64_t b = (uint64_t)__double_as_longlong(v);

@@ -101,6 +101,15 @@ struct IcpState {
   double last_upd[16];  // the last ΔT a solve produced (I since the reset): m3d_icp_result.update
 };
 
+// What the state kernels (icp.hip) know of a loop's two clouds: the frames the fp32 search runs in
+// and the magnitudes its error bounds are made of
+struct FrameParams {
+  double cs[3], ct[3];  // the source's and the target's centre
+  double pinf, qinf;    // the largest |coordinate| of the centred source / target
+  double s16;  // the target cloud's fp16 operand scale (power of two)
+  int shared;  // the target's frame is shared by every shard (m3d_cloud_create_framed)
+};
+
 // Uniform grid over a cloud's centred fp32 points (grid.hip): kernel view + owner.
 struct GridDev {
   float o[3];
@@ -571,6 +580,11 @@ bool nn_plan_on();  // M3D_NN_PLAN in the environment (0: the uniform 2-D launch
 void nn_plan_shape(int64_t ns, int32_t* qblocks, int32_t* budget);
 PlanArgs nn_plan_args(const m3d_icp* s);
 hipError_t launch_icp_reset(const m3d_icp* s, const double* T, bool apply_init, hipStream_t st);
+// The state part of a reset, for any loop that owns an IcpState (icp.hip icp_init_kernel): T = the
+// affine T (bottom row 0 0 0 1), dT = T when apply_init, else I; nothing evaluated, radius² r2, the
+// search fields of frame f
+hipError_t launch_icp_state_init(IcpState* state, const double* T, bool apply_init, double r2, const FrameParams& f,
+                                 hipStream_t st);
 hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st);
 hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t st);
 hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStream_t st);
@@ -625,6 +639,11 @@ hipError_t launch_shard_winner(const m3d_icp* s, int64_t off, int64_t* dkey, hip
                                int64_t q0 = 0, int64_t q1 = -1);
 hipError_t launch_shard_claim(const m3d_icp* s, const int64_t* dmin, int32_t* claim, hipStream_t st);
 hipError_t launch_icp_solve(const m3d_icp* s, const double* sums, hipStream_t st);
+// the same solve (icp.hip solve_state: the RegistrationICP stop rule and update on the reduced sums)
+// from its pieces; center: what the point-to-point sums were centred on
+hipError_t launch_icp_solve_state(IcpState* state, const double* sums, double relative_fitness, double relative_rmse,
+                                  int32_t max_iteration, int32_t estimation, int64_t ns, const double* center,
+                                  const FrameParams& f, hipStream_t st);
 // grid over xyz32[0, n) with cell ≈ `cell`: asynchronous when `lohi` (per-axis min[3], max[3] of
 // the points) is given, else one sync for the bounds; temporaries from `ta` (null: hipMalloc)
 hipError_t grid_build(const float4* xyz32, int64_t n, double cell, hipStream_t st, Grid* g,
@@ -646,12 +665,15 @@ hipError_t launch_grid_nn(const float4* src32, int64_t ns, const Grid* qgrid, co
 // the ICP source's Morton-slot copy (out, gout freshly allocated structs): grid.hip morton_source
 hipError_t morton_source(const m3d_cloud* src, double cell, m3d_cloud* out, Grid* gout, TmpArena* ta,
                          hipStream_t st);
-// dst[slot[k]] = v[k], k < n (slot-ordered loop arrays → the caller's source order)
 // correspondence pairs (i, v[i]) for v[i] >= 0 in increasing i; cnt: (n + 1023) / 1024 + 1 ints of
 // scratch, the total in cnt[(n + 1023) / 1024] (cnt[0] when n == 0)
 hipError_t launch_corr_pairs(const int32_t* v, int64_t n, int32_t* cnt, int32_t* pairs, hipStream_t st);
+// order changes by a slot table, k < n (icp.hip permute_kernel): scatter dst[slot[k]] = v[k]
+// (slot-ordered loop arrays → the caller's source order; a null slot copies), gather dst[k] = v[slot[k]]
 hipError_t launch_scatter_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst,
                               hipStream_t st);
+hipError_t launch_scatter_f64(const double* v, const int32_t* slot, int64_t n, double* dst, hipStream_t st);
+hipError_t launch_gather_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst, hipStream_t st);
 hipError_t launch_keys_to_idx(const int64_t* keys, int64_t n, int32_t* idx, hipStream_t st);
 hipError_t launch_icp_set_T(const m3d_icp* s, const double* T_dev, hipStream_t st);
 // a6 batched validation: states[k] ← evaluation state of T[list[k]] (icp_set_T semantics), then
@@ -784,9 +806,11 @@ hipError_t mesh_closest_grid(m3d_ctx* ctx, m3d_mesh* m, const double* xyz, int64
 // the triangle grid of a mesh with usable triangles, built once (mesh.hip; synchronous)
 hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why);
 // ICP against a mesh (mesh_icp.hip): the device arrays of one loop, every per-point array in the
-// source's Morton slot order.  state: an IcpState of the loop's own (T, dT, last_upd, fitness, rmse,
-// the previous pair, count, evals, iters, done, converged and r2 are used: the struct launch_reduce
-// reads `done` from); tri / d2 / pt: the scan's records (tri doubles as the next scan's seed).
+// source's Morton slot order.  state: an IcpState of the loop's own, reset by launch_icp_state_init and
+// advanced by launch_icp_solve_state with mesh_icp_frame() — the cloud loop's kernels; the loop reads
+// T, dT, last_upd, fitness, rmse, count, iters, done, converged and r2, and never the NN search
+// fields those kernels also fill; tri / d2 / pt: the scan's records (tri doubles as the next scan's
+// seed).
 struct MeshIcpLoop {
   IcpState* state = nullptr;
   double* pcd64 = nullptr;     // ns×3, the loop's points
@@ -798,16 +822,15 @@ struct MeshIcpLoop {
   int64_t ns = 0;
   double max_dist = 0.0;
 };
+// The frame of a loop without an NN search: no centring, no magnitudes, fp16 scale 1, not shared.
+// The search fields the state kernels derive from it stay finite (refresh_rt32_from divides by
+// s16² only) and bound_ok stays 0.
+inline FrameParams mesh_icp_frame() { return FrameParams{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 0.0, 1.0, 0}; }
 // enqueue only.  scan: brute force, or the one-box grid scan (the mesh's grid is built; seed: L.tri
-// holds each point's seed triangle); terms: the rows of kind / k and their reduce → sums; solve:
-// the RegistrationICP rule on sums
+// holds each point's seed triangle); terms: the rows of kind / k and their reduce → sums
 hipError_t launch_mesh_icp_scan(const m3d_mesh* m, const MeshIcpLoop& L, bool brute, bool seed, hipStream_t st);
 hipError_t launch_mesh_icp_terms(const m3d_mesh* m, const MeshIcpLoop& L, int32_t kind, double k, double* sums,
                                  hipStream_t st);
-hipError_t launch_mesh_icp_solve(const MeshIcpLoop& L, const double* sums, const m3d_icp_params& p, hipStream_t st);
-// dst[k] = v[slot[k]] / dst[slot[k]] = v[k], k < n
-hipError_t launch_gather_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst, hipStream_t st);
-hipError_t launch_scatter_f64(const double* v, const int32_t* slot, int64_t n, double* dst, hipStream_t st);
 size_t fgr_terms_scratch_bytes(int64_t n);
 // one iteration's sums over n ≥ 1 given rows (path as m3d_fgr_params.path) → sums27 [host].  Synchronous.
 hipError_t fgr_terms(m3d_ctx* ctx, const double* p, const double* q, int64_t n, double par, int path,

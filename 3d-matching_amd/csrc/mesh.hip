@@ -287,22 +287,9 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_brute_kernel(const double* __
   const bool valid = i < n;
   double q[3] = {0.0, 0.0, 0.0};
   if (valid) load_query(xyz, i, T, q);
-  double bd = INFINITY;
-  int32_t bt = -1;
-  for (int64_t f0 = 0; f0 < nf; f0 += kMeshBruteTile) {  // nf == 0: no tile is read
-    const int cnt = (int)std::min<int64_t>(kMeshBruteTile, nf - f0);
-    __syncthreads();
-    for (int k = threadIdx.x; k < cnt * 9; k += kMeshBlock) s9[k] = tri9[9 * f0 + k];
-    for (int k = threadIdx.x; k < cnt; k += kMeshBlock) sok[k] = ok[f0 + k];
-    __syncthreads();
-    if (!valid) continue;
-    for (int j = 0; j < cnt; ++j) {
-      if (!sok[j]) continue;
-      TriHit h;
-      tri_closest(s9 + 9 * j, s9 + 9 * j + 3, s9 + 9 * j + 6, q, h);
-      take_min(bd, bt, h.d2, (int32_t)(f0 + j));
-    }
-  }
+  double bd;
+  int32_t bt;
+  tri_min_brute<kMeshBlock>(tri9, ok, nf, q, valid, s9, sok, bd, bt);
   if (valid) write_result(out, i, tri9, q, bt);
 }
 
@@ -333,25 +320,7 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_grid_kernel(const double* __r
                      c1[2] == g.n[2] - 1;
   double bd = INFINITY;
   int32_t bt = -1;
-  for (int cz = c0[2]; cz <= c1[2]; ++cz)
-    for (int cy = c0[1]; cy <= c1[1]; ++cy) {
-      const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
-      const int32_t j0 = g.start[row + c0[0]], j1 = g.start[row + c1[0] + 1];
-      for (int32_t j = j0 + lane; j < j1; j += kWave) {
-        const int32_t t = g.refs[j];
-        const double* t9 = tri9 + 9 * (int64_t)t;
-        TriHit h;
-        tri_closest(t9, t9 + 3, t9 + 6, q, h);
-        take_min(bd, bt, h.d2, t);
-      }
-    }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double od = xor_lane_f64(bd, o);
-    const int32_t ot = xor_lane(bt, o, kWave);
-    take_min(bd, bt, od, ot);
-  }
-  // every lane holds the wave's minimum
+  tri_min_box(tri9, g, c0, c1, lane, q, bd, bt);  // every lane holds the wave's minimum
   const bool finished = whole || (bt >= 0 && bd < (double)Rf * (double)Rf);
   if (lane != 0) return;
   if (finished) {

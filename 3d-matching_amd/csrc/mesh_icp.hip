@@ -25,12 +25,17 @@
 //   Reduction.  block_partial over kSideBlock consecutive slots, then launch_reduce: the fixed order
 //     of every loop here (icp.hip, "reduce"); no floating-point atomics.  The source runs in the
 //     Morton slot order of its cloud (cell = 1.001·max_dist, as m3d_icp), whichever path scans.
-//   Solve (mesh_icp_solve_kernel, the rule of icp.hip solve_state<M3D_EST_POINT_TO_PLANE>, operation
-//     for operation): fitness = count / ns, rmse = sqrt(Σd² / count), 0 / 0 → 0; stop when evals > 0
-//     and |Δfitness| < relative_fitness and |Δrmse| < relative_rmse (converged), or when
-//     max_iteration updates are applied; else JᵀJ·x = −Jᵀr by ldlt6_solve_spd, a failed one by the
-//     pivoted ldlt6_solve, x → matrix by vec6_to_matrix_wave (all linalg.h), a non-finite update is
-//     the identity, T ← ΔT·T by matmul4_affine, dT ← ΔT.
+//   Solve.  Not here: icp.hip's solve_state<M3D_EST_POINT_TO_PLANE>, the cloud loops' own kernel
+//     (launch_icp_solve_state), on this loop's IcpState.  fitness = count / ns, rmse =
+//     sqrt(Σd² / count), 0 / 0 → 0; stop when evals > 0 and |Δfitness| < relative_fitness and
+//     |Δrmse| < relative_rmse (converged), or when max_iteration updates are applied; else
+//     JᵀJ·x = −Jᵀr by ldlt6_solve_spd, a failed one by the pivoted ldlt6_solve, x → matrix by
+//     vec6_to_matrix_wave (all linalg.h), a non-finite update is the identity, T ← ΔT·T by
+//     matmul4_affine, dT ← ΔT.  That kernel also refreshes the fp32 search fields of the state
+//     for the frame it is given; this loop hands it mesh_icp_frame() (m3d_internal.h) and reads none
+//     of them.
+//   State.  Reset by icp.hip's icp_init_kernel (launch_icp_state_init), as m3d_icp_reset: T = init
+//     with the bottom row (0, 0, 0, 1), dT = init unless it isIdentity().
 //   ns = 0: fitness 0, T = init, no pairs — not an error.
 //
 // SCAN, grid path: one wave per point over the mesh's triangle grid (mesh.hip builds it), ONE box
@@ -52,7 +57,9 @@
 //   winner, its d² and its point are the unseeded scan's, bit for bit; a seed that names no usable
 //   triangle is ignored.
 // SCAN, brute path: one thread per point, the triangles staged through LDS in tiles of
-// kMeshBruteTile, as mesh_brute_kernel: the definition, and the path for small meshes.
+// kMeshBruteTile: the definition, and the path for small meshes.
+// Both scans are mesh.hip's searches (mesh_tri.h: tri_min_brute, tri_min_box); a kernel here keeps
+// the query (dT applied, written back), the box's rule and the record (write_rec).
 //
 // Both paths, seed on and off, and two runs give the same bits in the records, the sums, the pose
 // and the pairs: a point's record depends on its own scan alone, and the sums are added in the
@@ -66,7 +73,6 @@
 
 #include <cmath>
 
-#include "linalg.h"
 #include "m3d_internal.h"
 #include "knn_wave.h"
 #include "mesh_tri.h"
@@ -120,22 +126,9 @@ __global__ __launch_bounds__(kScanBlock) void mesh_icp_brute_kernel(double* __re
     const double p[3] = {pcd64[3 * i], pcd64[3 * i + 1], pcd64[3 * i + 2]};
     q64_of(s->dT, p, q);
   }
-  double bd = INFINITY;
-  int32_t bt = -1;
-  for (int64_t f0 = 0; f0 < nf; f0 += kMeshBruteTile) {
-    const int cnt = (int)std::min<int64_t>(kMeshBruteTile, nf - f0);
-    __syncthreads();
-    for (int k = threadIdx.x; k < cnt * 9; k += kScanBlock) s9[k] = tri9[9 * f0 + k];
-    for (int k = threadIdx.x; k < cnt; k += kScanBlock) sok[k] = ok[f0 + k];
-    __syncthreads();
-    if (!valid) continue;
-    for (int j = 0; j < cnt; ++j) {
-      if (!sok[j]) continue;
-      TriHit h;
-      tri_closest(s9 + 9 * j, s9 + 9 * j + 3, s9 + 9 * j + 6, q, h);
-      take_min(bd, bt, h.d2, (int32_t)(f0 + j));
-    }
-  }
+  double bd;
+  int32_t bt;
+  tri_min_brute<kScanBlock>(tri9, ok, nf, q, valid, s9, sok, bd, bt);
   if (valid) write_rec(out, pcd64, i, tri9, q, bd, bt, s->r2);
 }
 
@@ -181,25 +174,9 @@ __global__ __launch_bounds__(kScanBlock) void mesh_icp_grid_kernel(double* __res
       c0[k] = all ? 0 : grid_coord(below(q[k], Rf), g.o[k], g.inv_h, g.n[k]);
       c1[k] = all ? g.n[k] - 1 : grid_coord(above(q[k], Rf), g.o[k], g.inv_h, g.n[k]);
     }
-    for (int cz = c0[2]; cz <= c1[2]; ++cz)
-      for (int cy = c0[1]; cy <= c1[1]; ++cy) {
-        const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
-        const int32_t j0 = g.start[row + c0[0]], j1 = g.start[row + c1[0] + 1];
-        for (int32_t j = j0 + lane; j < j1; j += kWave) {
-          const int32_t t = g.refs[j];
-          const double* t9 = tri9 + 9 * (int64_t)t;
-          TriHit h;
-          tri_closest(t9, t9 + 3, t9 + 6, q, h);
-          take_min(bd, bt, h.d2, t);
-        }
-      }
+    tri_box_walk(tri9, g, c0, c1, lane, q, bd, bt);
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double od = xor_lane_f64(bd, o);
-    const int32_t ot = xor_lane(bt, o, kWave);
-    take_min(bd, bt, od, ot);
-  }
+  tri_wave_min(bd, bt);
   if (lane == 0) write_rec(out, pcd64, i, tri9, q, bd, bt, r2);
 }
 
@@ -238,83 +215,6 @@ __global__ __launch_bounds__(kSideBlock) void mesh_icp_terms_kernel(const double
   block_partial<kTermSlots, kTermsUsed, kSideBlock>(v, partials);
 }
 
-// One wave: the header's solve rule on the reduced sums.
-__global__ void mesh_icp_solve_kernel(const double* __restrict__ sums, IcpState* __restrict__ s, double rel_fit,
-                                      double rel_rmse, int max_iter, int64_t ns) {
-  if (threadIdx.x >= kWave || s->done) return;
-  double sm[30];
-#pragma unroll
-  for (int k = 0; k < 30; ++k) sm[k] = sums[k];
-  const int32_t evals = s->evals, iters = s->iters;
-  const double prev_fit = s->prev_fitness, prev_rmse = s->prev_rmse;
-  double T[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) T[k] = s->T[k];
-  const double count = sm[28];
-  double A[36], b[6], x[6];
-  {
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int c = a; c < 6; ++c) {
-        A[a * 6 + c] = sm[k];
-        A[c * 6 + a] = sm[k];
-        ++k;
-      }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; ++a) b[a] = -sm[21 + a];
-  const bool spd_ok = ldlt6_solve_spd(A, b, x);
-  const double fit = count > 0.0 ? count / (double)ns : 0.0;
-  const double rmse = count > 0.0 ? sqrt(sm[29] / count) : 0.0;
-  bool stop = false;
-  if (evals > 0 && fabs(prev_fit - fit) < rel_fit && fabs(prev_rmse - rmse) < rel_rmse) {
-    s->converged = 1;
-    stop = true;
-  } else if (iters >= max_iter) {
-    stop = true;
-  }
-  s->fitness = fit;
-  s->rmse = rmse;
-  s->count = (int64_t)count;
-  s->prev_fitness = fit;
-  s->prev_rmse = rmse;
-  s->evals = evals + 1;
-  if (stop) {
-    s->done = 1;
-    return;
-  }
-  double upd[16];
-  for (int k = 0; k < 16; ++k) upd[k] = (k % 5 == 0) ? 1.0 : 0.0;
-  if (count > 0.0) {
-    if (!spd_ok) ldlt6_solve(A, b, x);
-    vec6_to_matrix_wave(x, upd);
-  }
-  bool finite = true;
-  for (int k = 0; k < 16; ++k) finite = finite && isfinite(upd[k]);
-  if (!finite)
-    for (int k = 0; k < 16; ++k) upd[k] = (k % 5 == 0) ? 1.0 : 0.0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) s->dT[k] = s->last_upd[k] = upd[k];
-  matmul4_affine(upd, T, T);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) s->T[k] = T[k];
-  s->iters = iters + 1;
-}
-
-// dst[k] = v[slot[k]] (the caller's order → slot order), dst[slot[k]] = v[k] (back)
-__global__ void gather_i32_kernel(const int32_t* __restrict__ v, const int32_t* __restrict__ slot, int64_t n,
-                                  int32_t* __restrict__ dst) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k < n) dst[k] = v[slot[k]];
-}
-__global__ void scatter_f64_kernel(const double* __restrict__ v, const int32_t* __restrict__ slot, int64_t n,
-                                   double* __restrict__ dst) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k < n) dst[slot[k]] = v[k];
-}
-
 unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -345,24 +245,6 @@ hipError_t launch_mesh_icp_terms(const m3d_mesh* m, const MeshIcpLoop& L, int32_
     });
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? launch_reduce(L.partials, nb, kTermSlots, sums, L.state, nullptr, st) : e;
-}
-
-hipError_t launch_mesh_icp_solve(const MeshIcpLoop& L, const double* sums, const m3d_icp_params& p, hipStream_t st) {
-  mesh_icp_solve_kernel<<<1, kWave, 0, st>>>(sums, L.state, p.relative_fitness, p.relative_rmse, p.max_iteration,
-                                             L.ns);
-  return hipGetLastError();
-}
-
-hipError_t launch_gather_i32(const int32_t* v, const int32_t* slot, int64_t n, int32_t* dst, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  gather_i32_kernel<<<blocks_of(n, 256), 256, 0, st>>>(v, slot, n, dst);
-  return hipGetLastError();
-}
-
-hipError_t launch_scatter_f64(const double* v, const int32_t* slot, int64_t n, double* dst, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  scatter_f64_kernel<<<blocks_of(n, 256), 256, 0, st>>>(v, slot, n, dst);
-  return hipGetLastError();
 }
 
 }  // namespace m3d

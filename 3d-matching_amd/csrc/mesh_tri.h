@@ -1,10 +1,14 @@
 // mesh_tri.h — the pieces of the point-to-mesh contract (mesh.hip's header) that more than one
-// translation unit evaluates: closest(p, triangle), the running (d², index) minimum, the outward
-// fp32 roundings of the covering argument and a triangle's cell range.  mesh.hip (the distance
-// query) and mesh_icp.hip (ICP against a mesh) include it; tri_closest is the ONE function every
-// kernel calls, so no two of them can disagree on a winner.
+// translation unit evaluates: closest(p, triangle), the running (d², index) minimum, the two
+// searches for it — the brute-force sweep over all triangles and the wave's walk over a cell box of
+// the triangle grid —, the outward fp32 roundings of the covering argument and a triangle's cell
+// range.  mesh.hip (the distance query) and mesh_icp.hip (ICP against a mesh) include it;
+// tri_closest is the ONE function every kernel calls and the two searches exist once, so no two
+// kernels can disagree on a winner.  A kernel keeps its query load, its rule for the box and its
+// own record write.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 
 #include "m3d_internal.h"
@@ -88,6 +92,68 @@ __device__ __forceinline__ void tri_cells(const double* __restrict__ t9, const T
     lo[k] = grid_coord(below(mn, g.margin), g.o[k], g.inv_h, g.n[k]);
     hi[k] = grid_coord(above(mx, g.margin), g.o[k], g.inv_h, g.n[k]);
   }
+}
+
+// THE BRUTE-FORCE SWEEP: the minimum (bd, bt) of one thread's query q over all nf triangles, the
+// usable ones (ok), staged through LDS in tiles of kMeshBruteTile by the kBlock threads of the block.
+// Every thread of the block calls it; one without a query (valid false) stages and takes no minimum.
+// s9: kMeshBruteTile × 9 doubles of LDS, sok: kMeshBruteTile bytes.  nf == 0: no tile is read.
+template <int kBlock>
+__device__ __forceinline__ void tri_min_brute(const double* __restrict__ tri9, const uint8_t* __restrict__ ok,
+                                              int64_t nf, const double q[3], bool valid, double* s9, uint8_t* sok,
+                                              double& bd, int32_t& bt) {
+  bd = INFINITY;
+  bt = -1;
+  for (int64_t f0 = 0; f0 < nf; f0 += kMeshBruteTile) {
+    const int cnt = (int)std::min<int64_t>(kMeshBruteTile, nf - f0);
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt * 9; k += kBlock) s9[k] = tri9[9 * f0 + k];
+    for (int k = threadIdx.x; k < cnt; k += kBlock) sok[k] = ok[f0 + k];
+    __syncthreads();
+    if (!valid) continue;
+    for (int j = 0; j < cnt; ++j) {
+      if (!sok[j]) continue;
+      TriHit h;
+      tri_closest(s9 + 9 * j, s9 + 9 * j + 3, s9 + 9 * j + 6, q, h);
+      take_min(bd, bt, h.d2, (int32_t)(f0 + j));
+    }
+  }
+}
+
+// THE BOX WALK: one wave's minimum of its query q over the triangles referenced from the cells
+// [c0, c1] of the grid g, in two steps.  tri_box_walk: the cell rows of the box, lanes over a row's
+// references, each lane folding what it meets into its own (bd, bt) — which comes in as (+inf, −1)
+// or as a candidate all lanes hold alike (a seed).  tri_wave_min: the butterfly that leaves the
+// wave's minimum in EVERY lane.  tri_min_box is both; a kernel that walks no box for some queries
+// (mesh_icp.hip: a point that is not finite) calls the steps.  The order of the references changes
+// nothing under the minimum, nor does a triangle met more than once.
+__device__ __forceinline__ void tri_box_walk(const double* __restrict__ tri9, const TriGridDev& g, const int c0[3],
+                                             const int c1[3], int lane, const double q[3], double& bd, int32_t& bt) {
+  for (int cz = c0[2]; cz <= c1[2]; ++cz)
+    for (int cy = c0[1]; cy <= c1[1]; ++cy) {
+      const int64_t row = ((int64_t)cz * g.n[1] + cy) * g.n[0];
+      const int32_t j0 = g.start[row + c0[0]], j1 = g.start[row + c1[0] + 1];
+      for (int32_t j = j0 + lane; j < j1; j += kWave) {
+        const int32_t t = g.refs[j];
+        const double* t9 = tri9 + 9 * (int64_t)t;
+        TriHit h;
+        tri_closest(t9, t9 + 3, t9 + 6, q, h);
+        take_min(bd, bt, h.d2, t);
+      }
+    }
+}
+__device__ __forceinline__ void tri_wave_min(double& bd, int32_t& bt) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const double od = xor_lane_f64(bd, o);
+    const int32_t ot = xor_lane(bt, o, kWave);
+    take_min(bd, bt, od, ot);
+  }
+}
+__device__ __forceinline__ void tri_min_box(const double* __restrict__ tri9, const TriGridDev& g, const int c0[3],
+                                            const int c1[3], int lane, const double q[3], double& bd, int32_t& bt) {
+  tri_box_walk(tri9, g, c0, c1, lane, q, bd, bt);
+  tri_wave_min(bd, bt);
 }
 
 // (float)x rounded toward −inf / +inf on the host

@@ -427,3 +427,29 @@ def test_flat_square_surface_against_its_vertices():
     vert = matcher.registration_icp(pts, PointCloud(sq, up), 1.0)
     np.testing.assert_array_equal(vert.transformation, np.eye(4))
     assert vert.fitness == 0.0
+
+
+# ------------------------------------------------------------------ bits of the recorded build
+@pytest.mark.parametrize("call", ["run", "terms", "closest"])
+def test_bits_of_the_recorded_build(call, golden):
+    """m3d_mesh_icp_run (T, update, fitness, rmse, count, iterations, converged, triangles),
+    m3d_mesh_icp_terms (30 sums, triangles, d²) and m3d_mesh_closest (d², triangle, point, uv,
+    region) return, on the fixed cases of tests/mesh_bits_cases.py and on every path variant, the
+    bits recorded in tests/golden/mesh_icp_bits.npz (tools/gen_mesh_bits.py) from the build that
+    still had its own solve kernel, host-built state, triangle sweep and box walk in mesh_icp.hip."""
+    import mesh_bits_cases as B
+
+    assert B.TILE == TILE
+    blob = golden("mesh_icp_bits.npz")[call].tobytes()
+    at, seen = {}, 0
+    for key, variant, fields in B.record(call):
+        if key not in at:  # a case's variants share one record
+            at[key], seen = seen, seen + sum(np.ascontiguousarray(a).nbytes for a in fields.values())
+        o = at[key]
+        for name, a in fields.items():
+            got = np.ascontiguousarray(a).tobytes()
+            exp = blob[o:o + len(got)]
+            assert got == exp, (f"{key} {variant}: {name} differs from the recorded bits: "
+                                f"{a.ravel()[:8]} != {np.frombuffer(exp, a.dtype)[:8]}")
+            o += len(got)
+    assert seen == len(blob) and len(at) >= len(B.SHAPES)

@@ -16,10 +16,12 @@ rigid motion; radius --radius.
   matcher.refine_registration against the mesh's vertices on the same pair, with both final pose
   errors (the largest |T·p − T_true·p| over the scan).
 
-Needs the GPU; prints readable lines and one JSON line.
+Needs the GPU; prints readable lines and one JSON line.  AB_LIB=<libm3d.so of another build>
+times that build instead (tools/ab_build.sh).
 Usage: python tools/mesh_icp_timing.py [--mesh 300] [--radius 0.12] [--evals 8] [--repeats 5] [--warmup 2]"""
 import argparse
 import json
+import os
 import statistics
 import sys
 import time
@@ -32,6 +34,9 @@ import torch
 
 import matcher
 from m3d import _lib, synth
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 from m3d import cache as _cache
 from m3d.core import Cloud, context, device_empty, icp, ptr, stream_handle, to_device
 from m3d.mesh import TriangleMesh, closest_points, icp_to_mesh

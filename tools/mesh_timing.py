@@ -15,11 +15,13 @@ the same surface in the same frame, so the scan lies on the model up to the tess
 * The yardstick users have today, in the same run: matcher.compute_point_cloud_distance of the
   scan against the mesh's VERTICES (whole call, the clouds packed and cached by the warm-up).
 
-Needs the GPU; prints readable lines and one JSON line.
+Needs the GPU; prints readable lines and one JSON line.  AB_LIB=<libm3d.so of another build>
+times that build instead (tools/ab_build.sh).
 Usage: python tools/mesh_timing.py [--mesh 300] [--repeats 7] [--warmup 2] [--brute-limit 20]"""
 import argparse
 import ctypes as C
 import json
+import os
 import statistics
 import sys
 import time
@@ -31,6 +33,9 @@ import numpy as np
 import torch
 
 from m3d import _lib, synth
+
+if os.environ.get("AB_LIB"):  # another build of libm3d.so (tools/ab_build.sh)
+    _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 from m3d.core import context, device_empty, ptr, stream_handle, to_device
 from m3d.mesh import TriangleMesh
 
