@@ -1274,8 +1274,9 @@ int ensure_morton_source(m3d_ctx* ctx, const m3d_cloud* c, double cell, const m3
 // self_seed (m3d_icp_step's fused loop): when the previous fused tail left every key at
 // kKeyNone (s->keys_clean), the brute-force scan seeds itself and the keyinit launch is skipped.
 // [q0, q1): a slot range of the sources (q1 < 0: all), see icp_nn_splits.
+// with_terms: the NN kernel that also runs the terms pass (m3d_icp_step, nn_terms_selected).
 hipError_t enqueue_nn(m3d_icp* s, int64_t off, hipStream_t st, bool self_seed = false, int64_t q0 = 0,
-                      int64_t q1 = -1) {
+                      int64_t q1 = -1, bool with_terms = false) {
   m3d_ctx* ctx = s->ctx;
   const bool whole = q0 == 0 && (q1 < 0 || q1 == s->src->n);
   const bool seeded = self_seed && s->keys_clean && off == 0 && whole;
@@ -1291,7 +1292,7 @@ hipError_t enqueue_nn(m3d_icp* s, int64_t off, hipStream_t st, bool self_seed = 
     if (e != hipSuccess) return e;
   }
   KTimer kt(ctx, M3D_KERNEL_NN, st);
-  return launch_icp_nn(s, off, seeded, st, q0, q1);
+  return launch_icp_nn(s, off, seeded, st, q0, q1, with_terms);
 }
 }  // namespace
 
@@ -1411,7 +1412,8 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
       if (params->nn_method == M3D_NN_BRUTE) nn_plan_shape(src->n, &s->nn_qblocks, &s->nn_budget);
       if (s->nn_qblocks > 0) {  // the brute-force NN's slice plan (nn_plan.h), on the state's page: the fused
                                 // tail's last block reads both
-        cv.add(&s->nn_cnt, (size_t)s->nn_qblocks);
+        cv.add(&s->nn_cnt, 2 * (size_t)s->nn_qblocks);  // and nn_tix behind it
+        cv.add(&s->nn_targs, (nn_terms_dev_bytes() + 7) / 8);
         cv.add(&s->nn_seen, (size_t)s->nn_qblocks);
         cv.add(&s->nn_table, (size_t)s->nn_budget);
       }
@@ -1444,8 +1446,18 @@ int icp_create(m3d_ctx* ctx, const m3d_cloud* src, const m3d_cloud* tgt, double 
     // likewise the NN plan's tile counters (the planner re-zeroes them, and every reset of the loop's
     // state: launch_icp_reset, launch_icp_set_T)
     if (!grc && s->nn_cnt != nullptr &&
-        hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t), nullptr) != hipSuccess)
+        hipMemsetAsync(s->nn_cnt, 0, 2 * (size_t)s->nn_qblocks * sizeof(uint32_t), nullptr) != hipSuccess)
       grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: NN plan counters");
+    // the terms arguments nn_mfma_terms_kernel reads from device memory: constants of the loop
+    if (!grc && s->nn_cnt != nullptr) {
+      s->nn_tix = s->nn_cnt + s->nn_qblocks;
+      s->src = src_m;
+      s->tgt = tgt;
+      s->tgrid = tg;
+      s->params = *params;
+      if (launch_nn_terms_setup(s, nullptr) != hipSuccess)
+        grc = m3d_fail(ctx, M3D_ERR_HIP, "loop arrays: NN terms arguments");
+    }
     // the setup above ran asynchronously on the null stream: finish it before the loop object is
     // used on the caller's streams
     if (!grc) {
@@ -1566,6 +1578,30 @@ bool fused_tail(const m3d_icp* s, bool keys_back) {
   }();
   return env && (keys_back || s->nblocks <= 256);
 }
+
+// M3D_NN_TERMS=0 in the environment: the terms pass never runs inside the NN launch
+bool nn_terms_env() {
+  static const bool on = [] {
+    const char* e = getenv("M3D_NN_TERMS");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+
+// m3d_icp_step's view of a loop for nn_terms_selected (it passes no claim)
+NnTermsSel nn_terms_sel(const m3d_icp* s, bool fused, bool reset) {
+  NnTermsSel c;
+  c.planned = s->params.nn_method == M3D_NN_BRUTE && s->nn_targs != nullptr && icp_nn_planned(s);
+  c.fused = fused;
+  c.reset = reset;
+  c.p2plane = s->params.estimation == M3D_EST_POINT_TO_PLANE;
+  c.rec64 = s->tgt->rec64 != nullptr;
+  c.seed = s->seed != nullptr;
+  c.claim = false;
+  c.one_device = s->ns_total == 0;
+  c.on = nn_terms_env() && !s->nn_terms_off;
+  return c;
+}
 }  // namespace
 
 int m3d_icp_step(m3d_icp* s, void* stream) {
@@ -1576,6 +1612,15 @@ int m3d_icp_step(m3d_icp* s, void* stream) {
   // brute force: the fused tail hands the keys back as kKeyNone, the next NN seeds itself
   const bool reset = s->params.nn_method != M3D_NN_GRID && s->src->n > 0;
   const bool fused = fused_tail(s, reset);
+  if (nn_terms_selected(nn_terms_sel(s, fused, reset))) {
+    // the terms pass runs inside the NN launch, query block by query block; what is left is one
+    // block: reduce, solve, plan (the M3D_KERNEL_TERMS events then time that block alone)
+    HIPX(ctx, enqueue_nn(s, 0, st, true, 0, -1, true));
+    KTimer kt(ctx, M3D_KERNEL_TERMS, st);
+    HIPX(ctx, launch_icp_reduce_solve_block(s, st));
+    s->keys_clean = true;
+    return M3D_OK;
+  }
   HIPX(ctx, enqueue_nn(s, 0, st, fused));
   if (fused) {
     KTimer kt(ctx, M3D_KERNEL_TERMS, st);
@@ -3489,6 +3534,44 @@ int m3d_debug_icp_seed_read(m3d_icp* s, float* seed, int32_t* corr, float* tgt32
     HIPX(s->ctx, hipMemcpyAsync(tgt32, s->tgt->xyz32, sizeof(float4) * nt, hipMemcpyDeviceToHost, S(stream)));
   HIPX(s->ctx, hipStreamSynchronize(S(stream)));
   return M3D_OK;
+}
+
+int m3d_debug_icp_nn_terms(m3d_icp* s, int on) {
+  if (!s) return M3D_ERR_INVALID;
+  s->nn_terms_off = on == 0;
+  // a captured step sequence holds the other iteration's kernels
+  for (int k = 0; k < 2; ++k) {
+    if (s->graph[k] != nullptr) hipGraphExecDestroy(s->graph[k]);
+    s->graph[k] = nullptr;
+    s->graph_n[k] = s->seen_n[k] = -1;
+  }
+  const bool reset = s->params.nn_method != M3D_NN_GRID && s->src->n > 0;
+  return nn_terms_selected(nn_terms_sel(s, fused_tail(s, reset), reset)) ? 1 : 0;
+}
+
+int m3d_debug_icp_nn_terms_read(m3d_icp* s, uint32_t* tickets, uint32_t* counts, void* stream) {
+  if (!s) return M3D_ERR_INVALID;
+  if (s->nn_tix == nullptr) return 0;
+  Touch tch{s->ctx, S(stream)};
+  const size_t bytes = sizeof(uint32_t) * (size_t)s->nn_qblocks;
+  if (tickets) HIPX(s->ctx, hipMemcpyAsync(tickets, s->nn_tix, bytes, hipMemcpyDeviceToHost, S(stream)));
+  if (counts) HIPX(s->ctx, hipMemcpyAsync(counts, s->nn_cnt, bytes, hipMemcpyDeviceToHost, S(stream)));
+  HIPX(s->ctx, hipStreamSynchronize(S(stream)));
+  return s->nn_qblocks;
+}
+
+int m3d_debug_nn_terms_select(uint32_t bits) {
+  NnTermsSel c;
+  c.planned = bits & 1u;
+  c.fused = bits & 2u;
+  c.reset = bits & 4u;
+  c.p2plane = bits & 8u;
+  c.rec64 = bits & 16u;
+  c.seed = bits & 32u;
+  c.claim = bits & 64u;
+  c.one_device = bits & 128u;
+  c.on = bits & 256u;
+  return nn_terms_selected(c) ? 1 : 0;
 }
 
 }  // extern "C"

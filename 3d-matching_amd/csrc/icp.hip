@@ -39,6 +39,12 @@ constexpr int kTermsBlock = 512;
 constexpr double kU = 5.9604644775390625e-08;
 constexpr double kU64 = 1.1102230246251565e-16;
 
+// nn_brute_terms.hip compiles this file again with M3D_ICP_TERMS_ONLY=1 and keeps only the terms
+// pass (terms_block and what it calls) for the NN kernel that runs it in place
+#ifndef M3D_ICP_TERMS_ONLY
+#define M3D_ICP_TERMS_ONLY 0
+#endif
+#if !M3D_ICP_TERMS_ONLY
 
 // ------------------------------------------------------------------------------- state
 // FrameParams: m3d_internal.h
@@ -215,6 +221,7 @@ __global__ __launch_bounds__(256) void keyinit_kernel(const float4* __restrict__
   near2[i] = kNearNone;
 }
 
+#endif  // !M3D_ICP_TERMS_ONLY
 // ------------------------------------------------------------------------------- terms
 // Transposing wave reduction of 32 per-lane slots: each butterfly step halves the slots a lane
 // keeps (the partner gets the other half), so 32 slots cost 31 pair exchanges instead of
@@ -324,6 +331,14 @@ struct TermsArgs {
   int64_t* reset_keys;   // fused single-device loop: hand the keys back as kKeyNone
   float4* seed;          // with reset_keys and rec64: the next scan's seed records (below), else null
 };
+// What the NN kernel that runs the terms pass in place (nn_brute.hip nn_mfma_terms_kernel) reads
+// through ONE kernel argument: a device-resident copy, written when the loop is created — every
+// member points into the loop's state or is a constant of the loop
+struct NnTermsDev {
+  TermsArgs a;       // terms_args(s, 0, no claim, reset_keys)
+  double* partials;
+  uint32_t* tix;     // per query block: the slices that have published (m3d_icp::nn_tix)
+};
 
 // est: M3D_EST_POINT_TO_PLANE → slots 0..20 JTJ (upper, row-major), 21..26 JTr, 27 Σr²
 //      M3D_EST_POINT_TO_POINT → slots 0..2 Σp_c, 3..5 Σq_c, 6..14 Σ p_c q_cᵀ (row-major)
@@ -354,9 +369,12 @@ __device__ unsigned long long g_terms_clock[4096 * 8];
   do {             \
   } while (0)
 #endif
-template <bool kWT, int kEst>
+// bx: the block's index (its 512 sources and its partial).  kSc1: the keys and runner-ups are read
+// with sc1 loads — the caller is the NN kernel whose blocks published them a moment ago
+// (nn_brute.hip nn_terms_handoff).
+template <bool kWT, int kEst, bool kSc1 = false>
 __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* __restrict__ s,
-                                            double* __restrict__ partials) {
+                                            double* __restrict__ partials, const unsigned bx) {
   __shared__ double red[kTermSlots][kTermsBlock / kWave];
 #if M3D_TERMS_CLOCK
   unsigned long long tph_[8];
@@ -380,13 +398,18 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
   float n2[kP];
 #pragma unroll
   for (int u = 0; u < kP; ++u) {
-    const int64_t i = ((int64_t)blockIdx.x * kP + u) * kTermsBlock + threadIdx.x;
+    const int64_t i = ((int64_t)bx * kP + u) * kTermsBlock + threadIdx.x;
     valid[u] = i < a.ns;
     ii[u] = valid[u] ? i : 0;
     gj[u] = -1;
     d2[u] = 0.0;
     fixed[u] = true;
-    if (a.claim == nullptr) {
+    if (kSc1) {
+      k1[u] = valid[u] ? (uint64_t)__hip_atomic_load(&a.keys[ii[u]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                       : (uint64_t)kKeyNone;
+      n2[u] = valid[u] ? __uint_as_float(__hip_atomic_load(&a.near2[ii[u]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                       : kInf;
+    } else if (a.claim == nullptr) {
       k1[u] = valid[u] ? (uint64_t)a.keys[ii[u]] : (uint64_t)kKeyNone;
       n2[u] = valid[u] ? __uint_as_float(a.near2[ii[u]]) : kInf;
     } else if (valid[u]) {
@@ -420,7 +443,7 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
       amb[u] = X[u] >= 0.0f && n2[u] <= X[u];
 #if M3D_TAIL_CLOCK
       {
-        const int64_t gw = (int64_t)blockIdx.x * (kTermsBlock / kWave) + threadIdx.x / kWave;
+        const int64_t gw = (int64_t)bx * (kTermsBlock / kWave) + threadIdx.x / kWave;
         const int na = __popcll(__ballot(amb[u]));
         if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096) g_tail_clock[2 * 4096 + 8 + gw] = na;
       }
@@ -518,7 +541,7 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
     double v = 0.0;
     if (threadIdx.x < 30)
       for (int w = 0; w < kTermsBlock / kWave; ++w) v += red[threadIdx.x][w];
-    double* dst = partials + (int64_t)blockIdx.x * kTermSlots + threadIdx.x;
+    double* dst = partials + (int64_t)bx * kTermSlots + threadIdx.x;
     if (kWT)
       __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst), __double_as_longlong(v),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -528,18 +551,19 @@ __device__ __forceinline__ void terms_block(const TermsArgs& a, const IcpState* 
   M3D_TPH(7);
 #if M3D_TERMS_CLOCK
   {
-    const int64_t gw = (int64_t)blockIdx.x * (kTermsBlock / kWave) + threadIdx.x / kWave;
+    const int64_t gw = (int64_t)bx * (kTermsBlock / kWave) + threadIdx.x / kWave;
     if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096)
       for (int k = 0; k < 8; ++k) g_terms_clock[8 * gw + k] = tph_[k];
   }
 #endif
 }
 
+#if !M3D_ICP_TERMS_ONLY
 template <int kEst>
 __global__ __launch_bounds__(kTermsBlock) void terms_kernel(TermsArgs a, const IcpState* __restrict__ s,
                                                             double* __restrict__ partials) {
   if (s->done) return;
-  terms_block<false, kEst>(a, s, partials);
+  terms_block<false, kEst>(a, s, partials, blockIdx.x);
 }
 
 // Target-sharded evaluation, step 1 (m3d_icp_shard_nn): this shard's fp64 winner of every query
@@ -934,39 +958,15 @@ __device__ void plan_wave(const PlanArgs& pa, IcpState* s, int lane, const PlanI
 struct PlanNone {
   static constexpr int32_t n = 0;
 };
-template <int kEst, bool kPlanner>
-__global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
-    TermsArgs a, IcpState* s, double* partials, int64_t nblocks, double* __restrict__ sums,
-    SolveParams sp, int do_solve, std::conditional_t<kPlanner, PlanArgs, PlanNone> pa) {
-  // do_solve = 0: the sharded tail (m3d_icp_shard_terms) — terms + the fixed-order reduce into
-  // `sums` in one launch; the caller all-reduces them and runs m3d_icp_solve
-  if (s->done) return;
-#if M3D_TAIL_CLOCK
-  const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  terms_block<true, kEst>(a, s, partials);
-#if M3D_TAIL_CLOCK
-  {
-    const unsigned long long clk1 = __builtin_amdgcn_s_memrealtime();
-    const int64_t gw = (int64_t)blockIdx.x * (kTermsBlock / kWave) + threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096) {
-      g_tail_clock[2 * gw] = clk0;
-      g_tail_clock[2 * gw + 1] = clk1;
-    }
-  }
-#endif
+// What one block does once every partial is in memory: the fixed-order reduce into `sums`, then
+// wave 0 solves (do_solve) while wave 1 plans (kPlanner) — what terms_solve_kernel's last block
+// runs behind its ticket (the same text there), as a function for reduce_solve_kernel, whose
+// partials come from the NN kernel before it (nn_brute.hip nn_mfma_terms_kernel).
+template <int kEst, bool kPlanner, class Plan>
+__device__ __forceinline__ void reduce_solve_block(IcpState* s, double* partials, int64_t nblocks,
+                                                   double* __restrict__ sums, const SolveParams& sp, int do_solve,
+                                                   const Plan& pa) {
   __shared__ double red[kReduceGroups][kTermSlots];
-  __shared__ int last;
-  // the partial went out write-through (sc1): drain it, then one lane takes the ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t t =
-        __hip_atomic_fetch_add(&s->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = (t == (uint32_t)(nblocks - 1));
-  }
-  __syncthreads();
-  if (!last) return;
   M3D_TCLK(0);
   SolveIn in;
   if (do_solve && threadIdx.x < kWave) solve_in(s, in);
@@ -1022,6 +1022,107 @@ __global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
     if constexpr (kPlanner) plan_wave(pa, s, threadIdx.x - kWave, pin);
   }
   M3D_TCLK(2);
+}
+
+template <int kEst, bool kPlanner>
+__global__ __launch_bounds__(kTermsBlock) void terms_solve_kernel(
+    TermsArgs a, IcpState* s, double* partials, int64_t nblocks, double* __restrict__ sums,
+    SolveParams sp, int do_solve, std::conditional_t<kPlanner, PlanArgs, PlanNone> pa) {
+  // do_solve = 0: the sharded tail (m3d_icp_shard_terms) — terms + the fixed-order reduce into
+  // `sums` in one launch; the caller all-reduces them and runs m3d_icp_solve
+  if (s->done) return;
+#if M3D_TAIL_CLOCK
+  const unsigned long long clk0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  terms_block<true, kEst>(a, s, partials, blockIdx.x);
+#if M3D_TAIL_CLOCK
+  {
+    const unsigned long long clk1 = __builtin_amdgcn_s_memrealtime();
+    const int64_t gw = (int64_t)blockIdx.x * (kTermsBlock / kWave) + threadIdx.x / kWave;
+    if ((threadIdx.x & (kWave - 1)) == 0 && gw < 4096) {
+      g_tail_clock[2 * gw] = clk0;
+      g_tail_clock[2 * gw + 1] = clk1;
+    }
+  }
+#endif
+  __shared__ double red[kReduceGroups][kTermSlots];
+  __shared__ int last;
+  // the partial went out write-through (sc1): drain it, then one lane takes the ticket
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t t =
+        __hip_atomic_fetch_add(&s->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = (t == (uint32_t)(nblocks - 1));
+  }
+  __syncthreads();
+  if (!last) return;
+  // (reduce_solve_block's text, kept in place: calling it from here re-times this kernel —
+  // docs/EXPERIMENTS.md §R29)
+  M3D_TCLK(0);
+  SolveIn in;
+  if (do_solve && threadIdx.x < kWave) solve_in(s, in);
+  // wave 1: the NN slice planner's counts (plan_wave below), in flight with the partials as well
+  const bool planner = kPlanner && pa.n > 0 && threadIdx.x >= kWave && threadIdx.x < 2 * kWave;
+  PlanIn pin;
+  if constexpr (kPlanner)
+    if (planner) plan_in(pa, s, threadIdx.x - kWave, pin);
+  // every load of the other blocks' partials is an sc1 load (L2-coherent, bypasses L1)
+  const int slot = threadIdx.x & (kTermSlots - 1);
+  constexpr int kG = kReduceGroups / (kTermsBlock / kTermSlots);  // groups per thread
+  double gv[kG];
+#pragma unroll
+  for (int u = 0; u < kG; ++u) gv[u] = 0.0;
+  const int g0 = threadIdx.x / kTermSlots;
+  constexpr int kR = 8;  // rounds of kReduceGroups blocks in flight per batch (kR·kG loads):
+                         // 256 blocks (cfg1: 196) in ONE batch of dependent loads
+  for (int64_t b0 = 0; b0 < nblocks; b0 += kR * kReduceGroups) {
+    double t[kR][kG];
+#pragma unroll
+    for (int r = 0; r < kR; ++r)
+#pragma unroll
+      for (int u = 0; u < kG; ++u) {
+        const int64_t b = b0 + r * kReduceGroups + g0 + u * (kTermsBlock / kTermSlots);
+        t[r][u] = b < nblocks
+                      ? __longlong_as_double(__hip_atomic_load(
+                            reinterpret_cast<unsigned long long*>(partials + b * kTermSlots + slot),
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                      : 0.0;
+      }
+#pragma unroll
+    for (int r = 0; r < kR; ++r)
+#pragma unroll
+      for (int u = 0; u < kG; ++u) gv[u] += t[r][u];
+  }
+  M3D_TCLK(8);  // thread 0's loads landed and added
+#pragma unroll
+  for (int u = 0; u < kG; ++u) red[g0 + u * (kTermsBlock / kTermSlots)][slot] = gv[u];
+  __syncthreads();
+  if (threadIdx.x < kTermSlots) {
+    double t = 0.0;
+    for (int k = 0; k < kReduceGroups; ++k) t += red[k][threadIdx.x];
+    red[0][threadIdx.x] = t;  // row 0 is consumed by this thread only before the overwrite
+    sums[threadIdx.x] = t;
+  }
+  M3D_TCLK(9);
+  __syncthreads();
+  M3D_TCLK(1);
+  if (threadIdx.x < kWave) {
+    if (threadIdx.x == 0) s->ticket = 0;
+    if (do_solve) solve_state<kEst>(red[0], s, sp, in);
+  } else if (planner) {
+    if constexpr (kPlanner) plan_wave(pa, s, threadIdx.x - kWave, pin);
+  }
+  M3D_TCLK(2);
+}
+
+// The tail of an iteration whose terms ran inside the NN kernel (nn_mfma_terms_kernel): one block,
+// launched behind it — the kernel boundary is the hand-off, every partial is in memory.
+__global__ __launch_bounds__(kTermsBlock) void reduce_solve_kernel(IcpState* s, double* partials, int64_t nblocks,
+                                                                   double* __restrict__ sums, SolveParams sp,
+                                                                   PlanArgs pa) {
+  if (s->done) return;
+  reduce_solve_block<M3D_EST_POINT_TO_PLANE, true>(s, partials, nblocks, sums, sp, 1, pa);
 }
 
 // finalize standalone NN (m3d_nn1): the fp64 winner (nnkey.h winner_fp64) and its d64
@@ -1195,7 +1296,8 @@ static hipError_t reset_points(const m3d_icp* s, hipStream_t st) {
 // kPlanTmax, and sums over evaluations size the slices like one evaluation's counts.)
 static hipError_t reset_plan_counts(const m3d_icp* s, hipStream_t st) {
   if (s->nn_cnt == nullptr) return hipSuccess;
-  return hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t), st);
+  // (and the query blocks' tickets of nn_mfma_terms_kernel, which follow the counts in the arena)
+  return hipMemsetAsync(s->nn_cnt, 0, (size_t)s->nn_qblocks * sizeof(uint32_t) * (s->nn_tix != nullptr ? 2 : 1), st);
 }
 
 hipError_t launch_icp_state_init(IcpState* state, const double* T, bool apply_init, double r2, const FrameParams& f,
@@ -1471,6 +1573,28 @@ hipError_t launch_icp_terms_solve(const m3d_icp* s, bool reset_keys, hipStream_t
   return hipGetLastError();
 }
 
+// ---- the iteration whose terms pass runs inside the NN kernel (nn_brute.hip nn_mfma_terms_kernel)
+__global__ void store_nn_terms_kernel(NnTermsDev v, NnTermsDev* dst) { *dst = v; }
+
+size_t nn_terms_dev_bytes() { return sizeof(NnTermsDev); }
+
+// the loop's NnTermsDev (s->nn_targs), once, at m3d_icp_create
+hipError_t launch_nn_terms_setup(const m3d_icp* s, hipStream_t st) {
+  NnTermsDev v;
+  v.a = terms_args(s, 0, nullptr, nullptr, true);
+  v.partials = s->partials;
+  v.tix = s->nn_tix;
+  store_nn_terms_kernel<<<1, 1, 0, st>>>(v, reinterpret_cast<NnTermsDev*>(s->nn_targs));
+  return hipGetLastError();
+}
+
+// its tail: one block reduces the partials the NN kernel left, solves and plans
+hipError_t launch_icp_reduce_solve_block(const m3d_icp* s, hipStream_t st) {
+  reduce_solve_kernel<<<1, kTermsBlock, 0, st>>>(s->state, s->partials, s->nblocks, s->sums, solve_params(s),
+                                                 nn_plan_args(s));
+  return hipGetLastError();
+}
+
 hipError_t launch_nn_finalize(const m3d_icp* s, int32_t* idx, double* d2, hipStream_t st) {
   const int64_t ns = s->src->n;
   if (ns == 0) return hipSuccess;
@@ -1534,6 +1658,7 @@ hipError_t launch_keys_to_idx(const int64_t* keys, int64_t n, int32_t* idx, hipS
 
 int64_t terms_blocks(int64_t ns) { return ns > 0 ? (ns + kTermsBlock - 1) / kTermsBlock : 1; }
 
+#endif  // !M3D_ICP_TERMS_ONLY
 }  // namespace m3d
 
 #if M3D_TERMS_CLOCK

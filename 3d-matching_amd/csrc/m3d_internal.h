@@ -444,6 +444,12 @@ struct m3d_icp {
   uint32_t* nn_table = nullptr;
   int32_t nn_qblocks = 0;
   int32_t nn_budget = 0;
+  // the iteration whose terms pass runs inside the NN kernel (nn_brute.hip nn_mfma_terms_kernel):
+  // per query block the ticket its slices add to (behind nn_cnt in the arena, zeroed with it), the
+  // device-resident NnTermsDev (icp.hip), and the per-loop switch of m3d_debug_icp_nn_terms
+  uint32_t* nn_tix = nullptr;
+  uint64_t* nn_targs = nullptr;
+  bool nn_terms_off = false;
   int32_t* corr = nullptr;         // ns current correspondence (-1 none)
   float4* seed = nullptr;          // ns seed records of the self-seeded brute-force scan: corr[i]'s centred
                                    // fp32 point and index (w; -1 none), written by the fused tail that
@@ -572,7 +578,28 @@ bool icp_nn_range_ok(const m3d_icp* s);
 hipError_t launch_icp_keyinit(const m3d_icp* s, int64_t shard_offset, hipStream_t st, int64_t q0 = 0,
                               int64_t q1 = -1);
 hipError_t launch_icp_nn(const m3d_icp* s, int64_t shard_offset, bool self_seed, hipStream_t st,
-                         int64_t q0 = 0, int64_t q1 = -1);
+                         int64_t q0 = 0, int64_t q1 = -1, bool with_terms = false);
+// Which iteration m3d_icp_step runs.  The pair nn_mfma_terms_kernel + reduce_solve_kernel — the NN
+// launch whose blocks also run the terms pass, then one block that reduces, solves and plans — only
+// when every condition holds; anything else runs the launches it always ran.
+struct NnTermsSel {
+  bool planned;     // the NN launch would be the planned (1-D) one (icp_nn_planned)
+  bool fused;       // the tail would be the fused one (fused_tail) ...
+  bool reset;       // ... handing the keys back
+  bool p2plane;     // point-to-plane
+  bool rec64;       // the target has its 64-B records
+  bool seed;        // the loop has seed records
+  bool claim;       // a claim (target shard)
+  bool one_device;  // not a shard of a multi-device loop
+  bool on;          // M3D_NN_TERMS in the environment and the loop's debug switch
+};
+inline bool nn_terms_selected(const NnTermsSel& c) {
+  return c.planned && c.fused && c.reset && c.p2plane && c.rec64 && c.seed && !c.claim && c.one_device && c.on;
+}
+bool icp_nn_planned(const m3d_icp* s);
+size_t nn_terms_dev_bytes();
+hipError_t launch_nn_terms_setup(const m3d_icp* s, hipStream_t st);
+hipError_t launch_icp_reduce_solve_block(const m3d_icp* s, hipStream_t st);
 // the blocks of nn_mfma_kernel resident on the device at once (0: unknown), and the plan shape of a
 // brute-force loop over ns sources: query blocks and budget, 0 / 0 when no plan can apply
 int64_t nn_resident_slots();

@@ -24,9 +24,25 @@
 #ifndef M3D_NN_CLOCK
 #define M3D_NN_CLOCK 0
 #endif
-#define M3D_NN_TU_MAIN (!M3D_NN_BRUTE_PLAN_TU)
-#define M3D_NN_TU_PLAN_KERNEL (M3D_NN_BRUTE_PLAN_TU ? !M3D_NN_CLOCK : M3D_NN_CLOCK)
-#if M3D_NN_TU_MAIN || M3D_NN_TU_PLAN_KERNEL
+// A third unit, nn_brute_terms.hip (M3D_NN_BRUTE_TERMS_TU=1), holds nn_mfma_terms_kernel: the planned
+// kernel whose blocks also run their query block's terms pass (nn_terms_handoff below), with
+// icp.hip's terms pass compiled into it (M3D_ICP_TERMS_ONLY).  One kernel per unit, as above.
+#ifndef M3D_NN_BRUTE_TERMS_TU
+#define M3D_NN_BRUTE_TERMS_TU 0
+#endif
+#define M3D_NN_TU_MAIN (!M3D_NN_BRUTE_PLAN_TU && !M3D_NN_BRUTE_TERMS_TU)
+#define M3D_NN_TU_PLAN_KERNEL (M3D_NN_BRUTE_PLAN_TU ? !M3D_NN_CLOCK : (M3D_NN_TU_MAIN && M3D_NN_CLOCK))
+#define M3D_NN_TU_TERMS_KERNEL (M3D_NN_BRUTE_TERMS_TU ? !M3D_NN_CLOCK : (M3D_NN_TU_MAIN && M3D_NN_CLOCK))
+#if M3D_NN_TU_MAIN || M3D_NN_TU_PLAN_KERNEL || M3D_NN_TU_TERMS_KERNEL
+#if M3D_NN_TU_TERMS_KERNEL
+// the terms pass (terms_block, TermsArgs, NnTermsDev) without the tail's clock stamps
+#undef M3D_TAIL_CLOCK
+#undef M3D_TERMS_CLOCK
+#define M3D_TAIL_CLOCK 0
+#define M3D_TERMS_CLOCK 0
+#define M3D_ICP_TERMS_ONLY 1
+#include "icp.hip"
+#endif
 
 namespace m3d {
 
@@ -403,7 +419,7 @@ __device__ __forceinline__ float wave_minmax(float v) {
 // diagnostic builds only (tools/nn_clock.py): per-block timeline and tile counts of the last
 // nn_mfma_kernel launch, s_memrealtime (100 MHz: one clock for every block, whichever XCD runs it)
 #if M3D_NN_CLOCK
-constexpr int kClkBlocks = 16384, kClkWords = 8;
+constexpr int kClkBlocks = 16384, kClkWords = 10;  // words 8, 9: nn_terms_handoff's stamps
 __device__ unsigned long long g_nn_clock[kClkWords * kClkBlocks];
 #endif
 struct QBox {
@@ -784,19 +800,59 @@ __device__ __forceinline__ void nn_push_hits(uint32_t m, const float4* rows, int
   }
 }
 
+#if M3D_NN_TU_TERMS_KERNEL
+// The per-query-block hand-off of nn_mfma_terms_kernel (DESIGN.md §3.6 "Hand-off", once per query
+// block instead of once per launch).  A block calls it after its publish — agent-scope atomics on
+// keys and near2 — and its count: every wave drains its own (vmcnt(0)), the block meets at a
+// barrier, one lane adds to the query block's ticket.  The block whose add returns S − 1 is the
+// last of the query block's S slices: every other slice's publish was drained before its add, so
+// the keys are final, and this block runs the query block's terms pass right here — terms_block
+// with sc1 loads of keys and near2 — exactly what block x of the fused tail's terms phase does:
+// partial x (write-through), corr, seed records, pcd64, keys handed back as kKeyNone.  Then it
+// clears the ticket for the next launch (nothing else adds to it in this one).  No block waits for
+// another: the last adder does the work.
+// clk (clock builds; null: none): the block's record — word 8 the ticket's return, word 9 the end
+// of the terms pass where the block ran it, else 0.
+__device__ __forceinline__ void nn_terms_handoff(const NnTermsDev* __restrict__ td, const IcpState* __restrict__ s,
+                                                 unsigned x, unsigned S, unsigned long long* clk = nullptr) {
+  __shared__ uint32_t tk_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t t = __hip_atomic_fetch_add(&td->tix[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tk_last = t == S - 1u ? 1u : 0u;
+#if M3D_NN_CLOCK
+    if (clk != nullptr) {
+      clk[8] = __builtin_amdgcn_s_memrealtime();
+      clk[9] = 0;
+    }
+#endif
+  }
+  __syncthreads();
+  if (!tk_last) return;
+  terms_block<true, M3D_EST_POINT_TO_PLANE, true>(td->a, s, td->partials, x);
+  if (threadIdx.x == 0) __hip_atomic_store(&td->tix[x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if M3D_NN_CLOCK
+  if (clk != nullptr && threadIdx.x == 0) clk[9] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+#endif
+
 // The body of the two NN kernels below.  kPlan = false is nn_mfma_kernel, the 2-D launch: the
 // block's slice is (blockIdx.x, blockIdx.y) of gridDim.y, from the hardware at every use, and none
 // of the plan's code is in it — no table, no LDS word, no counter: the launches the plan does not
 // apply to (the 1M source: 1954 query blocks; any grid.x) run the code they ran before the plan.
 // kPlan = true is nn_mfma_plan_kernel, the 1-D launch of pl.budget blocks (at most kPlanMaxQ
 // query blocks: x fits the 16 bits of a table entry and of the LDS word).
-template <bool kPlan>
+// kTerms (with kPlan) is nn_mfma_terms_kernel: the planned body, and at both of its ends — the
+// publish and the plain scan — nn_terms_handoff; td = its NnTermsDev (null otherwise).
+template <bool kPlan, bool kTerms = false>
 __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, int64_t ns,
                                              const uint4* __restrict__ tgt16, const float4* __restrict__ tgt32,
                                              const float4* __restrict__ tbox, int64_t nt_pad, int64_t off,
                                              const IcpState* __restrict__ s, int64_t* __restrict__ keys,
                                              uint32_t* __restrict__ near2, const SeedArgs& sa, int64_t q0,
-                                             const NnPlan& pl) {
+                                             const NnPlan& pl, const void* td = nullptr) {
 #if M3D_NN_ENTRY
   // One scalar round trip at entry: the block's table entry (the launch has exactly the table's
   // pl.budget blocks: blockIdx.x is in range whatever the state says) and the state words that
@@ -846,6 +902,9 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
     for (int64_t t0 = (int64_t)(kPlan ? bs.y : blockIdx.y) * kTT; t0 < nt_pad; t0 += tstep)
       nn_slice_scan(src32, ns, tgt32, t0, min(nt_pad, t0 + kTT), off, s, keys, near2, sa, q0,
                     kPlan ? bs.x : blockIdx.x, kPlan ? bs.y : blockIdx.y);
+#if M3D_NN_TU_TERMS_KERNEL
+    if constexpr (kTerms) nn_terms_handoff(static_cast<const NnTermsDev*>(td), s, bs.x, bs.S);
+#endif
     return;
   }
   __shared__ uint4 t16[2][2][kTT];
@@ -867,7 +926,8 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
   uint32_t kept = 0;
   // (x, y) again at the publish, from LDS: held in SGPRs across the sweep they cost spills
   __shared__ uint32_t slice_xy;
-  if (kPlan && threadIdx.x == 0) slice_xy = bs.x | (bs.y << 16);  // (visible after the boxes' barrier)
+  // (kTerms: and S, for the hand-off — the table entry's own layout, nn_plan.h)
+  if (kPlan && threadIdx.x == 0) slice_xy = bs.x | (bs.y << 16) | (kTerms ? bs.S << 24 : 0u);  // (visible after the boxes' barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const float r2_hi = s->r2_hi, eps = s->screen_eps_m, S = s->mfma_scale, be = s->band_e;
@@ -1116,7 +1176,7 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
 #endif
   const uint32_t sxy = kPlan ? slice_xy : 0u;
   const int64_t sxl = (int64_t)(sxy & 0xFFFFu);
-  const unsigned syl = sxy >> 16;
+  const unsigned syl = kTerms ? (sxy >> 16) & 0xFFu : sxy >> 16;
 // (macros, not values: the 2-D kernel reads the hardware's coordinates at each use, as before)
 #define M3D_NN_SX (kPlan ? sxl : (int64_t)blockIdx.x)
 #define M3D_NN_SY (kPlan ? syl : blockIdx.y)
@@ -1160,9 +1220,20 @@ __device__ __forceinline__ void nn_mfma_body(const float4* __restrict__ src32, i
         rec[5] = atomicMax(&clk_slow, 0u);
         rec[6] = (unsigned long long)M3D_NN_SX | ((unsigned long long)M3D_NN_SY << 32) | ((unsigned long long)cur.ty << 48);
         rec[7] = clk2b;  // the deferred passes done (the writer's own: the last wave out)
+        if (!kTerms) rec[8] = rec[9] = 0;  // (kTerms: thread 0, behind the hand-off's barrier)
       }
     }
   }
+#endif
+  // (behind the clock builds' record: its exit stamp is the publish's end)
+#if M3D_NN_TU_TERMS_KERNEL
+#if M3D_NN_CLOCK
+  if constexpr (kTerms)
+    nn_terms_handoff(static_cast<const NnTermsDev*>(td), s, (unsigned)sxl, sxy >> 24,
+                     blockIdx.x < kClkBlocks ? g_nn_clock + kClkWords * (int64_t)blockIdx.x : nullptr);
+#else
+  if constexpr (kTerms) nn_terms_handoff(static_cast<const NnTermsDev*>(td), s, (unsigned)sxl, sxy >> 24);
+#endif
 #endif
 }
 
@@ -1194,6 +1265,25 @@ hipError_t launch_nn_plan_kernel(unsigned blocks, hipStream_t st, M3D_NN_KERNEL_
 int nn_plan_kernel_blocks_per_cu() {
   int per = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_plan_kernel, kMBlock, 0) != hipSuccess) return 0;
+  return per > 0 ? per : 1;
+}
+#endif
+// nn_mfma_terms_kernel's launch and resident blocks per CU, likewise; td: the loop's NnTermsDev
+hipError_t launch_nn_terms_kernel(unsigned blocks, hipStream_t st, M3D_NN_KERNEL_ARGS, NnPlan pl, const void* td);
+int nn_terms_kernel_blocks_per_cu();
+#if M3D_NN_TU_TERMS_KERNEL
+__global__ __launch_bounds__(kMBlock) __attribute__((amdgpu_waves_per_eu(4))) void nn_mfma_terms_kernel(
+    M3D_NN_KERNEL_ARGS, NnPlan pl, const NnTermsDev* __restrict__ td) {
+  nn_mfma_body<true, true>(src32, ns, tgt16, tgt32, tbox, nt_pad, off, s, keys, near2, sa, q0, pl, td);
+}
+hipError_t launch_nn_terms_kernel(unsigned blocks, hipStream_t st, M3D_NN_KERNEL_ARGS, NnPlan pl, const void* td) {
+  nn_mfma_terms_kernel<<<dim3(blocks), kMBlock, 0, st>>>(src32, ns, tgt16, tgt32, tbox, nt_pad, off, s, keys, near2, sa,
+                                                         q0, pl, static_cast<const NnTermsDev*>(td));
+  return hipGetLastError();
+}
+int nn_terms_kernel_blocks_per_cu() {
+  int per = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_terms_kernel, kMBlock, 0) != hipSuccess) return 0;
   return per > 0 ? per : 1;
 }
 #endif
@@ -1262,23 +1352,50 @@ bool icp_nn_range_ok(const m3d_icp* s) {
 // Brute-force NN into s->keys (after launch_icp_keyinit, or self_seed: keys all kKeyNone, see
 // SeedArgs): nn_mfma_kernel alone (its exact in-kernel scan covers transforms whose operands do
 // not fit fp16).  m3d_icp_create builds the target's MFMA tiles for every brute-force loop.
+// The launch's shape for queries [q0, ns): query blocks, the uniform slices, and whether it is the
+// planned (1-D) one — whenever the loop's plan can apply: the whole source, M3D_NN_PLAN on, and
+// (nn_plan_shape, at create) resident slots known and more of them than query blocks.
+struct NnLaunchShape {
+  int64_t bx, gy;
+  bool planned;
+};
+static NnLaunchShape nn_launch_shape(const m3d_icp* s, int64_t q0, int64_t ns) {
+  const int64_t tt = (int64_t)kTH * kMTile;
+  const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
+  const int64_t gy = nn_grid_y(bx, s->tgrid->mf_npad / tt, nn_resident_slots(), M3D_NN_CULL != 0);
+  const bool planned = nn_plan_on() && s->nn_qblocks > 0 && q0 == 0 && ns == s->src->n && bx == s->nn_qblocks &&
+                       bx * gy <= s->nn_budget;
+  return NnLaunchShape{bx, gy, planned};
+}
+
+// whether the whole-source launch of this loop is the planned one (and launches at all)
+bool icp_nn_planned(const m3d_icp* s) {
+  if (s->src->n <= 0 || s->tgt->n == 0 || !icp_nn_uses_mfma(s) || s->tgrid->mf_npad % ((int64_t)kTH * kMTile) != 0)
+    return false;
+  return nn_launch_shape(s, 0, s->src->n).planned;
+}
+
+// with_terms: nn_mfma_terms_kernel, whose blocks also run the terms pass (the caller has checked
+// nn_terms_selected: the launch is the planned one)
 hipError_t launch_icp_nn(const m3d_icp* s, int64_t off, bool self_seed, hipStream_t st, int64_t q0,
-                         int64_t q1) {
+                         int64_t q1, bool with_terms) {
   const int64_t ns = q1 < 0 ? s->src->n : q1;  // queries: visit positions [q0, ns)
-  if (ns <= q0 || s->tgt->n == 0) return hipSuccess;
+  if (ns <= q0 || s->tgt->n == 0) return with_terms ? hipErrorInvalidValue : hipSuccess;
   const Grid* tg = s->tgrid;
   const int64_t tt = (int64_t)kTH * kMTile;
   if (!icp_nn_uses_mfma(s) || tg->mf_npad % tt != 0) return hipErrorInvalidValue;  // pack16 pads to kMTilePad
-  const int64_t slots = nn_resident_slots();
-  const int64_t bx = (ns - q0 + kMQueries - 1) / kMQueries;
-  const int64_t gy = nn_grid_y(bx, tg->mf_npad / tt, slots, M3D_NN_CULL != 0);
+  const NnLaunchShape sh = nn_launch_shape(s, q0, ns);
+  const int64_t bx = sh.bx, gy = sh.gy;
   // (the records exist where the fused tail wrote them: icp.hip terms_args, the same condition)
   const bool by_rec = M3D_NN_SEED_REC != 0 && self_seed && off == 0 && s->tgt->rec64 != nullptr && s->seed != nullptr;
   const SeedArgs sa{s->corr, by_rec ? s->seed : s->tgt->xyz32, s->tgt->n, by_rec ? 2 : self_seed ? 1 : 0};
-  // The planned launch whenever the loop's plan can apply: the whole source, M3D_NN_PLAN on, and
-  // (nn_plan_shape, at create) resident slots known and more of them than query blocks.
-  const bool planned = nn_plan_on() && s->nn_qblocks > 0 && q0 == 0 && ns == s->src->n && bx == s->nn_qblocks &&
-                       bx * gy <= s->nn_budget;
+  const bool planned = sh.planned;
+  if (with_terms) {
+    if (!planned || s->nn_targs == nullptr) return hipErrorInvalidValue;
+    return launch_nn_terms_kernel((unsigned)s->nn_budget, st, s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox,
+                                  tg->mf_npad, off, s->state, s->keys, s->near2, sa, q0,
+                                  NnPlan{s->nn_table, s->nn_cnt, (int)bx, (int)gy}, s->nn_targs);
+  }
   if (planned)
     return launch_nn_plan_kernel((unsigned)s->nn_budget, st, s->src->xyz32, ns, tg->mf16, tg->mf32, tg->mfbox,
                                  tg->mf_npad, off, s->state, s->keys, s->near2, sa, q0,
@@ -1295,10 +1412,11 @@ int64_t nn_resident_slots() {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return (int64_t)0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, nn_mfma_kernel, kMBlock, 0) != hipSuccess)
       return (int64_t)0;
-    // both kernels hold two blocks per CU (128 VGPRs, 67 KB of LDS); the smaller count if they ever differ
-    const int pp = nn_plan_kernel_blocks_per_cu();
+    // all three kernels hold two blocks per CU (128 VGPRs, 67 KB of LDS); the smaller count if they ever differ
+    const int pp = nn_plan_kernel_blocks_per_cu(), pt = nn_terms_kernel_blocks_per_cu();
     per = per > 0 ? per : 1;
     if (pp > 0 && pp < per) per = pp;
+    if (pt > 0 && pt < per) per = pt;
     return (int64_t)p.multiProcessorCount * per;
   }();
   return slots;

@@ -1,7 +1,7 @@
 // nn_plan.h — the slice plan of the brute-force NN launch: how many blocks S_x
 // each 512-query block x of nn_mfma_kernel gets, sized from the target tiles t_x the query block
 // kept in the previous evaluation.  The rule, shared by the device planner (icp.hip: wave 1 of
-// terms_solve_kernel's last block), the host entry m3d_debug_nn_plan_host and the launch:
+// terms_solve_kernel's last block, and of reduce_solve_kernel), the host entry m3d_debug_nn_plan_host and the launch:
 //   S_x(τ) = clamp(⌈t_x / τ⌉, 1, cap),  cap = min(S_max, ntiles),
 //   τ = the smallest integer ≥ 1 with Σ_x S_x(τ) ≤ B (the block budget: the resident slots);
 // Σ S_x(τ) does not grow with τ and equals n ≤ B at τ = max t_x, so a bisection over [1, max t_x]

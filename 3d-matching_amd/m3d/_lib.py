@@ -261,6 +261,9 @@ SIGNATURES = {
     "m3d_debug_icp_nn_plan": (C.c_int, [vp, vp, C.c_int64, vp]),
     "m3d_debug_icp_nn_plan_read": (C.c_int, [vp, vp, vp, vp, vp]),
     "m3d_debug_icp_seed_read": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "m3d_debug_icp_nn_terms": (C.c_int, [vp, C.c_int]),
+    "m3d_debug_icp_nn_terms_read": (C.c_int, [vp, vp, vp, vp]),
+    "m3d_debug_nn_terms_select": (C.c_int, [C.c_uint32]),
     "m3d_parse_ascii_rows": (C.c_int, [C.c_char_p, C.c_size_t, i64, i32, C.POINTER(dbl),
                                        C.POINTER(C.c_size_t)]),
     "m3d_format_ascii_rows": (C.c_int, [C.POINTER(dbl), i64, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -1044,6 +1044,20 @@ int m3d_debug_icp_nn_plan_read(m3d_icp* s, uint32_t* counts, uint32_t* table, in
  * take the plain fallback)}.  M3D_ERR_INVALID for a loop without records (grid NN, empty target).
  * Within ABI 13. */
 int m3d_debug_icp_seed_read(m3d_icp* s, float* seed, int32_t* corr, float* tgt32, int32_t* info2, void* stream);
+/* The iteration whose terms pass runs inside the brute-force NN launch: on = 0
+ * turns it off for this loop, anything else back on; the loop's captured step graphs are dropped.
+ * Returns 1 when m3d_icp_step of this loop now runs that iteration, 0 when it runs the two
+ * launches it ran before (the switch off, or a loop the iteration does not apply to).
+ * m3d_debug_icp_nn_terms_read (synchronous): tickets / counts [host, query blocks; either may be
+ * NULL] = the query blocks' hand-off tickets and tile counts as they are on the device; returns
+ * the number of query blocks (0: the loop has neither).
+ * m3d_debug_nn_terms_select (host only): the selection rule itself on nine conditions, bit 0 the
+ * NN launch is the planned one, 1 the tail is the fused one, 2 it hands the keys back, 3
+ * point-to-plane, 4 target records, 5 seed records, 6 a claim, 7 one device, 8 switched on;
+ * returns 1 when the iteration is selected.  Within ABI 13. */
+int m3d_debug_icp_nn_terms(m3d_icp* s, int on);
+int m3d_debug_icp_nn_terms_read(m3d_icp* s, uint32_t* tickets, uint32_t* counts, void* stream);
+int m3d_debug_nn_terms_select(uint32_t bits);
 
 /* ------------------------------------------------------------------ host text I/O (§8(f) rank 4) */
 

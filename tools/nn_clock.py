@@ -7,7 +7,12 @@ and when its last wave out finished the deferred exact passes, with the tiles th
 half tiles its slowest wave swept, and its slice: query block x, slice y and — since the
 slice plan (nn_plan.h, EXPERIMENTS §R19) — the query block's slice count S (x | y << 32 | S << 48;
 a build from before the plan leaves S at 0: grid.y).  With the plan it prints the S histogram and
-the block durations against S.  M3D_NN_PLAN=0 in the environment: the uniform launch."""
+the block durations against S.  M3D_NN_PLAN=0 in the environment: the uniform launch.
+Where the launch is nn_mfma_terms_kernel (the terms pass inside the NN launch) the
+record has two more words — the return of the block's hand-off ticket and, for the block that ran
+its query block's terms pass, the end of that pass — and the tool prints how many query blocks had
+finished their terms before the launch's last scan ended, and how long the launch runs past that
+point.  A build from before those words (8 per record) is read as such."""
 import ctypes as C
 import os
 import sys
@@ -22,7 +27,7 @@ from m3d import _lib, synth
 _lib.LIB_PATH = Path(os.environ["AB_LIB"]).resolve()
 from m3d.core import Cloud, IcpLoop, context
 
-CLK_BLOCKS, CLK_WORDS = 16384, 8  # nn_brute.hip kClkBlocks, kClkWords
+CLK_BLOCKS, CLK_WORDS = 16384, 10  # nn_brute.hip kClkBlocks, kClkWords (8 before the hand-off's stamps)
 
 
 def stats(v):
@@ -42,10 +47,15 @@ def main():
     for _ in range(evals):  # single steps: every evaluation is a launch of its own
         lp.step()
     torch.cuda.synchronize()
-    buf = (C.c_ulonglong * (CLK_WORDS * CLK_BLOCKS))()
-    rc = ctx.lib.m3d_debug_nn_clock(buf, C.c_int(CLK_WORDS * CLK_BLOCKS))
+    for words in (CLK_WORDS, 8):
+        buf = (C.c_ulonglong * (words * CLK_BLOCKS))()
+        rc = ctx.lib.m3d_debug_nn_clock(buf, C.c_int(words * CLK_BLOCKS))
+        if rc == 0:
+            break
     assert rc == 0, "m3d_debug_nn_clock failed"
-    a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, CLK_WORDS).astype(np.int64)
+    a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, words).astype(np.int64)
+    if words == 8:
+        a = np.column_stack([a, np.zeros((len(a), 2), np.int64)])
     a = a[a[:, 3] > 0]
     bx, by, bs = a[:, 6] & 0xFFFFFFFF, (a[:, 6] >> 32) & 0xFFFF, a[:, 6] >> 48
     gx, gy = int(bx.max()) + 1, int(by.max()) + 1
@@ -99,6 +109,17 @@ def main():
           f"(setup {setup[k]:.2f}, loop {loop[k]:.2f}, rest {rest[k]:.2f}), tiles {tiles[k]}, slowest wave {slow[k]} halves")
     hist, edges = np.histogram(en, bins=12)
     print("ends per bin:  ", " ".join(f"{e:.1f}:{h}" for e, h in zip(edges[:-1], hist)))
+    if (a[:, 8] > 0).any():  # nn_mfma_terms_kernel: the hand-off and the in-kernel terms
+        tick, tend = (a[:, 8] - t0) * us, (a[:, 9] - t0) * us
+        ran = a[:, 9] > 0
+        last_scan = en.max()  # (en: the blocks' publish done, before the hand-off)
+        launch_end = max(tick.max(), tend[ran].max())
+        print(f"hand-off: ticket back {stats(tick - en)} us after the block's publish")
+        print(f"in-kernel terms ({ran.sum()} query blocks): duration {stats(tend[ran] - tick[ran])}; "
+              f"ends {stats(tend[ran])}")
+        print(f"{(tend[ran] <= last_scan).sum()} of {ran.sum()} query blocks finished their terms before the "
+              f"launch's last scan ended ({last_scan:.2f} us); the launch runs {launch_end - last_scan:.2f} us past it "
+              f"(to {launch_end:.2f} us)")
 
 
 if __name__ == "__main__":
