@@ -3208,6 +3208,7 @@ void m3d_mesh_destroy(m3d_mesh* m) {
   if (!m) return;
   ReleaseScope rs(m->ctx, m->ctx_id);
   if (m->gblock) block_release(m->gblock);
+  if (m->sblock) block_release(m->sblock);
   if (m->block) block_release(m->block);
   delete m;
 }
@@ -3251,6 +3252,72 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4) {
   out4[1] = mesh->grid_built ? mesh->nrefs : 0;
   out4[2] = mesh->grid_built ? mesh->doublings : 0;
   out4[3] = mesh->last_rounds;
+  return M3D_OK;
+}
+
+// ------------------------------------------------------------------------------- surface sampling
+// mesh_sample.hip; the cumulative weights are built by the first call and cached on the mesh
+namespace {
+int mesh_sample_ready(m3d_ctx* ctx, m3d_mesh* mesh, hipStream_t st) {
+  CHECK_ARG(ctx, mesh->usable > 0, "the mesh has no usable triangle (none, or every one degenerate or not finite)");
+  if (!mesh->sample_built) {
+    hipSetDevice(ctx->device);
+    Touch tch{ctx, st};
+    HIPX(ctx, mesh_sample_build(ctx, mesh, st));
+  }
+  CHECK_ARG(ctx, mesh->sample_W > 0, "the mesh has no triangle with a finite non-zero area");
+  return M3D_OK;
+}
+}  // namespace
+
+int m3d_mesh_sample(m3d_ctx* ctx, m3d_mesh* mesh, int64_t n, uint64_t seed, double* points_out,
+                    int32_t* triangle_out, double* uv_out, double* normals_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, mesh && n >= 0 && n < ((int64_t)1 << 31), "invalid arguments");
+  hipStream_t st = S(stream);
+  const int rc = mesh_sample_ready(ctx, mesh, st);
+  if (rc) return rc;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  Touch tch{ctx, st};
+  HIPX(ctx, mesh_sample(mesh, n, seed, points_out, triangle_out, uv_out, normals_out, st));
+  HIPX(ctx, hipStreamSynchronize(st));
+  return M3D_OK;
+}
+
+int m3d_mesh_sample_info(const m3d_mesh* mesh, uint64_t* out2) {
+  if (!mesh || !out2) return M3D_ERR_INVALID;
+  out2[0] = mesh->sample_built ? mesh->sample_W : 0;
+  out2[1] = mesh->sample_built ? (uint64_t)mesh->sample_nonzero : 0;
+  return M3D_OK;
+}
+
+// ------------------------------------------------------------------------------- minimum-distance thinning
+// thin.hip; the grid of cell `radius` cached on the cloud, scratch from the preprocessing buffer
+int m3d_thin_min_distance(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, uint64_t seed, int32_t* decided_out,
+                          int64_t* kept_count_out, int32_t* rounds_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, cloud && (decided_out || cloud->n == 0), "invalid arguments");
+  CHECK_ARG(ctx, std::isfinite(radius) && radius > 0.0, "thin_min_distance: radius must be finite and > 0");
+  if (kept_count_out) *kept_count_out = 0;
+  if (rounds_out) *rounds_out = 0;
+  if (cloud->n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  const Grid* g = nullptr;
+  int rc = ensure_grid(ctx, cloud, radius, st, &g);
+  if (rc) return rc;
+  char* scratch = nullptr;
+  rc = prep_buffer(ctx, thin_scratch_bytes(cloud->n), &scratch);
+  if (rc) return rc;
+  std::string why;
+  int64_t kept = 0;
+  int32_t rounds = 0;
+  hipError_t e = thin_min_distance(cloud, g, radius, seed, decided_out, &kept, &rounds, scratch, st, &why);
+  if (rounds_out) *rounds_out = rounds;
+  if (e != hipSuccess) return clean_fail(ctx, "thin_min_distance", e, why);
+  if (kept_count_out) *kept_count_out = kept;
   return M3D_OK;
 }
 

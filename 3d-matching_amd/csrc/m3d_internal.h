@@ -405,6 +405,14 @@ struct m3d_mesh {
   int64_t nrefs = 0;
   int32_t doublings = 0;    // cell-size doublings of the build
   int32_t last_rounds = 0;  // ladder rounds of the last call (0: brute force)
+  // the sampling weights (mesh_sample.hip), built by the first m3d_mesh_sample and dropped with the
+  // mesh: cum[f] = the sum of the integer weights of triangles 0..f, W = cum[nf − 1]
+  bool sample_built = false;
+  uint64_t* cum = nullptr;
+  void* sblock = nullptr;  // cum
+  size_t sblock_bytes = 0;
+  uint64_t sample_W = 0;
+  int64_t sample_nonzero = 0;  // triangles with a non-zero weight
 };
 
 struct m3d_icp {
@@ -832,6 +840,20 @@ hipError_t mesh_closest_grid(m3d_ctx* ctx, m3d_mesh* m, const double* xyz, int64
                              hipStream_t st, std::string* why);
 // the triangle grid of a mesh with usable triangles, built once (mesh.hip; synchronous)
 hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why);
+// surface sampling (mesh_sample.hip).  mesh_sample_build: the cumulative integer weights of a mesh
+// with usable triangles, built once (synchronous; m->sample_W == 0 afterwards: no triangle has a
+// finite non-zero weight).  mesh_sample: enqueue only, n ≥ 0 samples of a built mesh with
+// sample_W > 0; every output [device] or null.
+hipError_t mesh_sample_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st);
+hipError_t mesh_sample(const m3d_mesh* m, int64_t n, uint64_t seed, double* points, int32_t* triangle, double* uv,
+                       double* normals, hipStream_t st);
+// minimum-distance thinning (thin.hip).  g: the cloud's grid of cell `radius`; n ≥ 1; decided
+// [device] n int32; scratch: thin_scratch_bytes(n) bytes.  Synchronous.  why: the message of a failure
+// that is not a HIP error (hipErrorUnknown).
+size_t thin_scratch_bytes(int64_t n);
+hipError_t thin_min_distance(const m3d_cloud* c, const Grid* g, double radius, uint64_t seed, int32_t* decided,
+                             int64_t* kept_out, int32_t* rounds_out, void* scratch, hipStream_t st,
+                             std::string* why);
 // ICP against a mesh (mesh_icp.hip): the device arrays of one loop, every per-point array in the
 // source's Morton slot order.  state: an IcpState of the loop's own, reset by launch_icp_state_init and
 // advanced by launch_icp_solve_state with mesh_icp_frame() — the cloud loop's kernels; the loop reads

@@ -155,19 +155,7 @@ __device__ __forceinline__ void write_result(const MeshOut& o, int64_t i, const 
 }
 
 // ------------------------------------------------------------------------------- upload
-// order-preserving map of a double onto unsigned integers (integer atomic min / max of coordinates)
-__host__ __device__ inline uint64_t ord_of(double x) {
-  uint64_t b;
-  memcpy(&b, &x, sizeof b);
-  return (b >> 63) != 0 ? ~b : (b | 0x8000000000000000ull);
-}
-inline double ord_inv(uint64_t k) {
-  const uint64_t b = (k >> 63) != 0 ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  double x;
-  memcpy(&x, &b, sizeof x);
-  return x;
-}
-
+// (ord_of / ord_inv, the order-preserving integer image of a double: mesh_tri.h)
 // what m3d_mesh_create reads back: an index out of range, the usable triangles, their box
 struct MeshInfo {
   int32_t bad, usable;

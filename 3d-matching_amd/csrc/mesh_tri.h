@@ -8,6 +8,8 @@
 // own record write.
 #pragma once
 
+#include <string.h>
+
 #include <algorithm>
 #include <cmath>
 
@@ -15,6 +17,20 @@
 #include "knn_wave.h"
 
 namespace m3d {
+
+// order-preserving map of a double onto unsigned integers (integer atomic min / max of coordinates
+// in mesh.hip, of the triangles' doubled areas in mesh_sample.hip)
+__host__ __device__ inline uint64_t ord_of(double x) {
+  uint64_t b;
+  memcpy(&b, &x, sizeof b);
+  return (b >> 63) != 0 ? ~b : (b | 0x8000000000000000ull);
+}
+inline double ord_inv(uint64_t k) {
+  const uint64_t b = (k >> 63) != 0 ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  double x;
+  memcpy(&x, &b, sizeof x);
+  return x;
+}
 
 struct TriHit {
   double d2, pt[3], v, w;

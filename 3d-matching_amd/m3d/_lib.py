@@ -241,6 +241,9 @@ SIGNATURES = {
     "m3d_mesh_icp_run": (C.c_int, [vp, vp, vp, C.POINTER(dbl), dbl, C.POINTER(IcpParams), C.POINTER(RobustKernel),
                                    i32, i32, C.POINTER(IcpResult), vp, vp]),
     "m3d_mesh_grid_info": (C.c_int, [vp, C.POINTER(i64)]),
+    "m3d_mesh_sample": (C.c_int, [vp, vp, i64, u64, vp, vp, vp, vp, vp]),
+    "m3d_mesh_sample_info": (C.c_int, [vp, C.POINTER(u64)]),
+    "m3d_thin_min_distance": (C.c_int, [vp, vp, dbl, u64, vp, C.POINTER(i64), C.POINTER(i32), vp]),
     "m3d_mesh_brute_tile": (i32, []),
     "m3d_mesh_auto_brute_max": (i32, []),
     "m3d_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -8,6 +8,9 @@ What an Open3D user runs after registering a CAD model against a scan and its re
 | ``t.geometry.RaycastingScene.add_triangles``                   | ``RaycastingScene.add_triangles``      |
 | ``RaycastingScene.compute_closest_points`` / ``compute_distance`` | the same methods, ``closest_points`` |
 | ``registration_icp`` against points sampled from the model      | ``icp_to_mesh`` (``matcher.registration_icp_to_mesh``): the surface itself as target |
+| ``mesh.sample_points_uniformly(n)``                             | ``TriangleMesh.sample_points_uniformly``, ``sample_points`` |
+| ``mesh.sample_points_poisson_disk(n)``                          | ``TriangleMesh.sample_points_poisson_disk`` (dart throwing, not sample elimination) |
+| ``mesh.get_surface_area()``                                     | ``TriangleMesh.get_surface_area``      |
 
 The contract is mesh.hip's (restated in numpy by tests/mesh_restatement.py): Ericson's closest point
 on a triangle in fp64 in one fixed operation order, the winner the smallest (d², triangle index)
@@ -18,6 +21,10 @@ works in float32).  Ray casting, occupancy and signed distance (ray parity in Op
 ``icp_to_mesh`` / ``icp_to_mesh_terms`` are mesh_icp.hip's loop and its one-evaluation hook
 (restated by tests/mesh_icp_restatement.py): point-to-plane ICP whose target is the closest point
 on the mesh's surface with the winning triangle's face normal.
+
+``sample_points`` is mesh_sample.hip's call (restated by tests/mesh_sample_restatement.py): points
+drawn from the surface with probability proportional to area, in integer weights and one fixed fp64
+operation order, so a sample's bits depend on (mesh, seed, sample number) alone.
 """
 
 from __future__ import annotations
@@ -30,7 +37,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["TriangleMesh", "RaycastingScene", "read_triangle_mesh", "closest_points", "icp_to_mesh",
-           "icp_to_mesh_terms"]
+           "icp_to_mesh_terms", "sample_points"]
 
 INVALID_ID = np.uint32(0xFFFFFFFF)  # Open3D RaycastingScene.INVALID_ID
 
@@ -110,6 +117,126 @@ class TriangleMesh:
         ctx.check(ctx.lib.m3d_mesh_grid_info(h, out), "mesh_grid_info")
         return {"cells": out[0], "references": out[1], "doublings": out[2], "rounds": out[3]}
 
+    def sample_info(self) -> dict:
+        """m3d_mesh_sample_info: the total integer weight ``W`` of the sampling table and the
+        number of triangles with a non-zero weight (0 and 0 before the first sampling call)."""
+        ctx, h = self._handle()
+        out = (C.c_uint64 * 2)()
+        ctx.check(ctx.lib.m3d_mesh_sample_info(h, out), "mesh_sample_info")
+        return {"W": int(out[0]), "nonzero": int(out[1])}
+
+    def get_surface_area(self) -> float:
+        """Open3D ``TriangleMesh.get_surface_area``: the sum of the triangles' areas (host numpy;
+        a triangle with a coordinate that is not finite counts as 0)."""
+        if not self.has_triangles():
+            return 0.0
+        a, b, c = (self.vertices[self.triangles[:, k]] for k in range(3))
+        with np.errstate(all="ignore"):
+            ar = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+        return float(ar[np.isfinite(ar)].sum())
+
+    def sample_points_uniformly(self, number_of_points: int = 100, use_triangle_normal: bool = True,
+                                seed: int = 0, with_details: bool = False):
+        """Open3D ``TriangleMesh.sample_points_uniformly`` on the device (``sample_points``) → a
+        ``PointCloud`` of ``number_of_points`` points with the face normal of each point's triangle
+        (this mesh keeps no vertex normals, so ``use_triangle_normal=False`` returns the points
+        without normals).  ``with_details=True`` → (cloud, {"triangle", "uv"}).  The same ``seed``
+        gives the same bits; sample k does not depend on ``number_of_points``."""
+        from .types import PointCloud
+
+        n = int(number_of_points)
+        if n < 0:
+            raise ValueError("number_of_points must be >= 0")
+        out = sample_points(self, n, seed)
+        pc = PointCloud(out["point"], out["normal"] if use_triangle_normal else None)
+        return (pc, {"triangle": out["triangle"], "uv": out["uv"]}) if with_details else pc
+
+    def sample_points_poisson_disk(self, number_of_points=None, init_factor: int = 5, radius=None, seed: int = 0,
+                                   with_details: bool = False):
+        """The call shape of Open3D ``TriangleMesh.sample_points_poisson_disk``; the method is
+        DART THROWING, not Open3D's sample elimination: ``init_factor``·N uniform samples
+        (``sample_points_uniformly``) thinned to a minimum distance (``prep.thin_min_distance``), so
+        no two returned points are closer than the radius used and every point is an original
+        uniform sample with its face normal.
+
+        ``radius`` given: the samples are thinned at it and every kept point is returned (N, where
+        ``number_of_points`` is None, is ceil(area / radius²) — the count at which the start radius
+        below would be this one).  ``number_of_points`` = N alone: the radius starts at
+        sqrt(area / N), is bracketed by factors of 1.5 and then cut by at most 6 geometric
+        bisections; of the radii tried the largest whose kept count is ≥ N is used and the first N
+        kept points in key order (the thinning's own rank) are returned.
+        → ``PointCloud``; ``with_details=True`` → (cloud, {"radius", "indices" into the uniform
+        samples, "kept" at that radius, "tried": [(radius, kept count)]})."""
+        from . import prep
+        from .types import PointCloud
+
+        if number_of_points is None and radius is None:
+            raise ValueError("sample_points_poisson_disk: number_of_points or radius")
+        if radius is not None and not (np.isfinite(float(radius)) and float(radius) > 0.0):
+            raise ValueError("sample_points_poisson_disk: radius must be finite and > 0")
+        if number_of_points is not None and int(number_of_points) < 1:
+            raise ValueError("sample_points_poisson_disk: number_of_points >= 1")
+        if int(init_factor) < 1:
+            raise ValueError("sample_points_poisson_disk: init_factor >= 1")
+        area = self.get_surface_area()
+        if radius is not None and number_of_points is None:
+            N = max(int(np.ceil(area / (float(radius) * float(radius)))), 1)
+        else:
+            N = int(number_of_points)
+        base = self.sample_points_uniformly(int(init_factor) * N, seed=seed)
+        tried = []
+
+        def kept_at(r):
+            idx = prep.thin_min_distance(base.points, r, seed=seed)
+            tried.append((float(r), len(idx)))
+            return idx
+
+        if radius is not None:
+            r_used, idx = float(radius), kept_at(float(radius))
+        else:
+            if not area > 0.0:
+                raise ValueError("sample_points_poisson_disk: the mesh has no surface area")
+            r = float(np.sqrt(area / N))
+            idx = kept_at(r)
+            lo = hi = None  # lo: the largest radius tried with ≥ N kept; hi: the smallest with fewer
+            if len(idx) >= N:
+                lo = (r, idx)
+                for _ in range(24):
+                    r *= 1.5
+                    idx = kept_at(r)
+                    if len(idx) < N:
+                        hi = r
+                        break
+                    lo = (r, idx)
+            else:
+                hi = r
+                for _ in range(64):
+                    r /= 1.5
+                    idx = kept_at(r)
+                    if len(idx) >= N:
+                        lo = (r, idx)
+                        break
+                    hi = r
+                if lo is None:
+                    raise ValueError(f"sample_points_poisson_disk: fewer than {N} distinct samples")
+            if hi is not None:
+                for _ in range(6):
+                    mid = float(np.sqrt(lo[0] * hi))
+                    idx = kept_at(mid)
+                    if len(idx) >= N:
+                        lo = (mid, idx)
+                    else:
+                        hi = mid
+            r_used, idx = lo
+        kept = len(idx)
+        if number_of_points is not None and radius is None:
+            key = _sample_keys(seed, idx)
+            idx = np.sort(idx[np.lexsort((idx, key))[:N]])
+        pc = PointCloud(base.points[idx], base.normals[idx])
+        if not with_details:
+            return pc
+        return pc, {"radius": r_used, "indices": idx, "kept": kept, "tried": tried}
+
     def __repr__(self):
         return f"TriangleMesh with {len(self.vertices)} points and {len(self.triangles)} triangles."
 
@@ -168,6 +295,41 @@ def closest_points(mesh: TriangleMesh, points, transformation=None, path=None, r
                                        ptr(pt), ptr(uv), ptr(reg), stream_handle()), "mesh_closest")
     return {"d2": d2[:n].cpu().numpy(), "triangle": tri[:n].cpu().numpy(), "point": pt[:n].cpu().numpy(),
             "uv": uv[:n].cpu().numpy(), "region": reg[:n].cpu().numpy()}
+
+
+def _sample_keys(seed: int, index) -> np.ndarray:
+    """sampler.h ``sample_base(seed, i)`` for every i of ``index`` (uint64): the thinning's rank key."""
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        z = (u(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ (np.asarray(index).astype(u) * u(0x9E3779B97F4A7C15))) \
+            + u(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+        return z ^ (z >> u(31))
+
+
+def sample_points(mesh: TriangleMesh, n: int, seed: int = 0) -> dict:
+    """m3d_mesh_sample: ``n`` points of the surface of ``mesh`` drawn with probability proportional
+    to area → ``point`` (n, 3) f64, ``triangle`` (n,) int32, ``uv`` (n, 2) f64 (``closest_points``'
+    convention: point ≈ (1−u−v)·a + u·b + v·c), ``normal`` (n, 3) f64 (the triangle's unit face
+    normal).  Sample k of a call is a function of (mesh, seed, k) alone.  ValueError for a mesh
+    without a usable triangle (or without one of finite non-zero area)."""
+    from .core import _torch, device_empty, ptr, stream_handle
+
+    n = int(n)
+    if n < 0:
+        raise ValueError("sample_points: n >= 0")
+    ctx, h = mesh._handle()
+    torch = _torch()
+    m = max(n, 1)
+    pt = device_empty((m, 3), torch.float64)
+    tri = device_empty((m,), torch.int32)
+    uv = device_empty((m, 2), torch.float64)
+    nrm = device_empty((m, 3), torch.float64)
+    ctx.check(ctx.lib.m3d_mesh_sample(ctx.h, h, n, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(pt), ptr(tri), ptr(uv),
+                                      ptr(nrm), stream_handle()), "mesh_sample")
+    return {"point": pt[:n].cpu().numpy(), "triangle": tri[:n].cpu().numpy(), "uv": uv[:n].cpu().numpy(),
+            "normal": nrm[:n].cpu().numpy()}
 
 
 # The seeded box of the grid scan (mesh_icp.hip) never changes a bit of the result; it is on by

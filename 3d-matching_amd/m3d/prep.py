@@ -17,6 +17,7 @@ oracle/prep_oracle.py; parity against Open3D itself unpinned — SURVEY.md §8(c
 | ``pcd.cluster_dbscan(eps, min_points)`` (users)          | ``cluster_dbscan``                |
 | ``keypoint.compute_iss_keypoints(pcd, ...)`` (users)     | ``compute_iss_keypoints``, ``model_resolution`` |
 | ``registration_fgr_based_on_correspondence`` (users)     | ``fgr_on_correspondences``, ``fgr_tuple_test``, ``fgr_terms`` |
+| (none: a minimum point distance, keeping original points) | ``thin_min_distance``             |
 
 All entry points take host or device arrays and return numpy arrays (the reference works in
 numpy / Open3D host containers); the arithmetic runs on the GPU.
@@ -269,6 +270,66 @@ def cluster_dbscan(points, eps: float, min_points: int, *, with_details: bool = 
         return labels
     return labels, DbscanOutcome(int(r.num_clusters), int(r.num_core), int(r.num_noise), int(r.largest_label),
                                  int(r.largest_size), sizes[: int(r.num_clusters)].cpu().numpy(), cnt.cpu().numpy())
+
+
+@dataclass
+class ThinOutcome:
+    """What ``thin_min_distance`` found besides the kept indices."""
+    decided: np.ndarray  # (n,) int32: +k kept in round k, −k dropped in round k
+    rounds: int          # launches of the device loop
+    kept: int
+
+
+def thin_min_distance(points, radius: float, seed: int = 0, with_details: bool = False):
+    """Thin a cloud to a minimum point distance on the device (m3d_thin_min_distance; the contract
+    is in include/m3d.h): dart throwing in the order of the hashed keys ``sample_base(seed, i)`` —
+    a point is kept unless a kept point of lower rank lies strictly inside ``radius``.  The kept
+    points are original points (a voxel mean is not), no two closer than ``radius``, and every
+    dropped point has a kept one inside it.  → ascending int64 indices of the kept points;
+    ``with_details=True`` → (indices, ``ThinOutcome``).  A host point with a coordinate that is
+    not finite is never kept and blocks nobody; a ``Cloud`` must be finite."""
+    if not (np.isfinite(float(radius)) and float(radius) > 0.0):
+        raise ValueError("thin_min_distance: radius must be finite and > 0")
+    if _empty(points):
+        idx = np.zeros(0, np.int64)
+        return (idx, ThinOutcome(np.zeros(0, np.int32), 0, 0)) if with_details else idx
+    torch = _torch()
+    if not isinstance(points, Cloud) and not isinstance(points, torch.Tensor):
+        p = np.asarray(points, np.float64).reshape(-1, 3)
+        ok = np.isfinite(p).all(axis=1)
+        if not ok.all():
+            finite = np.flatnonzero(ok)
+            if len(finite) == 0:
+                idx = np.zeros(0, np.int64)
+                return (idx, ThinOutcome(np.full(len(p), -1, np.int32), 1, 0)) if with_details else idx
+            return _thin_subset(p, finite, radius, seed, with_details)
+        points = p
+    c = _cloud(points)
+    ctx = c.ctx
+    dec = device_empty((c.n,), torch.int32)
+    kept, rounds = C.c_int64(0), C.c_int32(0)
+    ctx.check(ctx.lib.m3d_thin_min_distance(ctx.h, c.h, float(radius), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(dec),
+                                            C.byref(kept), C.byref(rounds), stream_handle()), "thin_min_distance")
+    decided = dec.cpu().numpy()
+    idx = np.flatnonzero(decided > 0).astype(np.int64)
+    return (idx, ThinOutcome(decided, int(rounds.value), int(kept.value))) if with_details else idx
+
+
+def _thin_subset(p: np.ndarray, finite: np.ndarray, radius: float, seed: int, with_details: bool):
+    """``thin_min_distance`` of a host cloud with rows that are not finite.  A device cloud's frame
+    (its mean) does not survive such a row, and the ranks are those of the ORIGINAL indices, so the
+    rows cannot simply be left out: they are parked together at one point more than two radii
+    outside the finite rows' box — where they meet only each other — and reported as dropped in
+    round 1 whatever happened to them there.  (``rounds`` counts the parked rows' rounds too: two.)"""
+    q = p.copy()
+    bad = np.setdiff1d(np.arange(len(p)), finite)
+    far = float(np.abs(p[finite]).max()) + 2.5 * float(radius)
+    q[bad] = [far, far, far]
+    _, out = thin_min_distance(q, radius, seed, with_details=True)
+    decided = out.decided.copy()
+    decided[bad] = -1
+    idx = np.flatnonzero(decided > 0).astype(np.int64)
+    return (idx, ThinOutcome(decided, out.rounds, len(idx))) if with_details else idx
 
 
 def model_resolution(points) -> float:

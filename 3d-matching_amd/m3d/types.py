@@ -144,6 +144,15 @@ class PointCloud:
 
         return cluster_dbscan(self.points, eps, min_points)
 
+    def thin_min_distance(self, radius: float, seed: int = 0):
+        """The cloud thinned to a minimum point distance on the device (m3d.prep
+        ``thin_min_distance``: original points, no two closer than ``radius``) →
+        (thinned cloud, kept indices)."""
+        from .prep import thin_min_distance
+
+        ind = thin_min_distance(self.points, radius, seed=seed)
+        return self.select_by_index(ind), ind
+
     def transform(self, T):
         T = np.asarray(T, np.float64)
         self.points = self.points @ T[:3, :3].T + T[:3, 3]

@@ -36,7 +36,7 @@ from .ransac import (
     global_registration,
     run_ransac,
 )
-from .register import register
+from .register import register, register_to_mesh
 from .robust import CauchyLoss, GMLoss, HuberLoss, L1Loss, L2Loss, TukeyLoss
 
 __all__ = [
@@ -67,4 +67,5 @@ __all__ = [
     "registration_icp",
     "registration_icp_to_mesh",
     "register",
+    "register_to_mesh",
 ]

@@ -10,6 +10,10 @@ the same two stages on the device:
    Global Registration instead (``matcher.fgr``: no sample budget, no dependence on a seed's luck);
 2. fine: ``refine_registration`` (point-to-plane ICP, radius 0.4·voxel) from the coarse result;
    ``kernel``: a robust kernel of ``matcher.robust`` for that stage.
+
+``register_to_mesh(source, mesh)`` is the same pipeline against a CAD model: the coarse stage runs
+against ``Ply.from_mesh`` (points sampled from the model's SURFACE, with its face normals), the
+fine stage against the surface itself (``refine_registration_to_mesh``).
 """
 
 from __future__ import annotations
@@ -58,3 +62,29 @@ def register(source, target, voxel_size=None, correspondences=None, ransac_itera
     if not refine:
         return coarse
     return refine_registration(source, target, coarse.transformation, v, kernel)
+
+
+def register_to_mesh(source, mesh, voxel_size=None, coarse: str = "ransac", number_of_points=None, seed: int = 0,
+                     kernel=None, **register_kwargs):
+    """Register the scan ``source`` (a ``Ply``) against the triangle mesh ``mesh`` (a
+    ``TriangleMesh``, a ``(vertices, triangles)`` pair or the path of an STL file), end to end:
+
+    1. ``target = Ply.from_mesh(mesh, v, number_of_points, seed)``: uniform samples of the surface,
+       preprocessed like a scan (``number_of_points`` None: ``Ply.from_mesh``'s default density);
+    2. ``first = register(source, target, v, refine=False, coarse=coarse, **register_kwargs)``;
+    3. ``refine_registration_to_mesh(source, mesh, first.transformation, v, kernel)``: point-to-plane
+       ICP against the surface itself.
+
+    ``voxel_size`` None: ``source.voxel_size`` (default 0.3)."""
+    from ply.ply import Ply, _mesh_of
+
+    from .mesh_icp import refine_registration_to_mesh
+
+    if "refine" in register_kwargs:
+        raise TypeError("register_to_mesh always refines against the mesh; use register(..., refine=False) with "
+                        "Ply.from_mesh for the coarse stage alone")
+    v = voxel_size if voxel_size is not None else getattr(source, "voxel_size", 0.3)
+    m = _mesh_of(mesh)
+    target = Ply.from_mesh(m, voxel_size=v, number_of_points=number_of_points, seed=seed)
+    first = register(source, target, v, refine=False, coarse=coarse, **register_kwargs)
+    return refine_registration_to_mesh(source, m, first.transformation, v, kernel)

@@ -34,6 +34,12 @@ by the device path of ``m3d.prep``:
 
 ``Ply.from_arrays`` builds one from arrays (synthetic clouds, tests, benchmarks) without any
 preprocessing unless ``preprocess=True``.
+
+``Ply.from_mesh`` builds one from a triangle mesh (a CAD model, an STL file): ``pcd`` is points drawn
+uniformly from the model's SURFACE with their face normals (``TriangleMesh.sample_points_uniformly``)
+and goes through the same steps 1a–6.  The reference's way from an STL to a ``Ply`` keeps the STL's
+vertices and drops its faces (``convert_stl-ply.py``); ``Ply(path)`` itself keeps refusing anything
+but a ``.ply``.
 """
 
 from __future__ import annotations
@@ -44,6 +50,31 @@ from pathlib import Path
 import numpy as np
 
 from m3d.types import Feature, PointCloud
+
+# Ply.from_mesh's default sample count: 16 samples per voxel-sized square of surface, so that a
+# voxel of the down-sampled cloud averages about that many; clamped to [MIN, MAX].  A stated
+# default, not a tuned one.
+MESH_SAMPLES_PER_VOXEL_AREA = 16
+MESH_SAMPLES_MIN = 10_000
+MESH_SAMPLES_MAX = 5_000_000
+
+
+def _mesh_of(mesh):
+    """A ``TriangleMesh``, a ``(vertices, triangles)`` pair, or the path of an STL file."""
+    from m3d import mesh as M
+
+    if isinstance(mesh, M.TriangleMesh):
+        return mesh
+    if isinstance(mesh, (str, Path)):
+        return M.read_triangle_mesh(mesh)
+    vertices, triangles = mesh
+    return M.TriangleMesh(vertices, triangles)
+
+
+def mesh_sample_count(area: float, voxel_size: float) -> int:
+    """``Ply.from_mesh``'s default ``number_of_points``: ceil(16·area / voxel²) in [10,000, 5,000,000]."""
+    want = np.ceil(MESH_SAMPLES_PER_VOXEL_AREA * float(area) / (float(voxel_size) * float(voxel_size)))
+    return int(min(max(want, MESH_SAMPLES_MIN), MESH_SAMPLES_MAX)) if np.isfinite(want) else MESH_SAMPLES_MAX
 
 
 class Ply:
@@ -193,4 +224,29 @@ class Ply:
             return obj
         obj.pcd_down = PointCloud(points if points_down is None else points_down)
         obj.pcd_fpfh = None if fpfh is None else Feature(np.asarray(fpfh, np.float64))
+        return obj
+
+    @classmethod
+    def from_mesh(cls, mesh, voxel_size: float = 0.3, number_of_points: int | None = None, seed: int = 0,
+                  remove_outliers: dict | None = None, remove_plane: dict | None = None,
+                  keep_cluster: dict | None = None, keypoints: dict | None = None):
+        """A ``Ply`` of a triangle mesh (``TriangleMesh``, ``(vertices, triangles)`` or an STL path):
+        ``pcd`` = ``number_of_points`` uniform samples of the surface with their face normals (None:
+        ``mesh_sample_count(area, voxel_size)``), then the unchanged preprocessing — the face normals
+        orient the estimated ones, which a PLY of the model's vertices never had."""
+        m = _mesh_of(mesh)
+        if not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0.0):
+            raise ValueError("voxel_size must be finite and > 0")
+        if number_of_points is None:
+            number_of_points = mesh_sample_count(m.get_surface_area(), voxel_size)
+        if int(number_of_points) < 1:
+            raise ValueError("number_of_points >= 1")
+        obj = cls.__new__(cls)
+        obj.path = Path(mesh) if isinstance(mesh, (str, Path)) else None
+        obj.voxel_size = voxel_size
+        t0 = time.perf_counter()
+        obj.pcd = m.sample_points_uniformly(int(number_of_points), seed=seed)
+        obj.stage_ms = {"sample": (time.perf_counter() - t0) * 1e3}
+        obj.mesh = m
+        obj._preprocess(voxel_size, remove_outliers, remove_plane, keep_cluster, keypoints)
         return obj

@@ -950,6 +950,47 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4);
 int32_t m3d_mesh_brute_tile(void);
 int32_t m3d_mesh_auto_brute_max(void);
 
+/* ------------------------------------------------------------------ surface sampling (mesh_sample.hip)
+ * (added within ABI 13, the version number is unchanged)  Open3D
+ * TriangleMesh.sample_points_uniformly: n points drawn from the mesh's surface with probability
+ * proportional to area.  The contract (mesh_sample.hip, restated in numpy by
+ * tests/mesh_sample_restatement.py), all in fp64, one operation at a time:
+ *   weights   len_f = sqrt((cx*cx + cy*cy) + cz*cz) of c = ab × ac for a usable triangle with a finite
+ *             len_f, else 0; L = max len_f = m·2^e, m in [0.5, 1); w_f = (uint64) trunc(ldexp(len_f,
+ *             32 − e)); cum_f = w_0 + … + w_f, W = cum_{F−1}.  A triangle more than about 2^32 times
+ *             smaller than the largest has weight 0 and is never drawn.  Built by the first call,
+ *             cached on the mesh, dropped with it.
+ *   sample k  base = sample_base(seed, k), x_j = splitmix64(base + j); t = high 64 bits of x_0·W; the
+ *             triangle is the smallest f with cum_f > t; u = (x_1 >> 11)·2^-53, v = (x_2 >> 11)·2^-53,
+ *             both replaced by 1 − themselves when u + v > 1; point = (a + ab*u) + ac*v per
+ *             coordinate; normal = c / len.
+ * Outputs [device], each may be NULL: points_out n×3 f64, triangle_out n int32, uv_out n×2 f64 (m3d_mesh_closest's
+ * convention: point ≈ (1−u−v)·a + u·b + v·c), normals_out n×3 f64 (the triangle's unit face
+ * normal).  A sample's bits depend on (mesh, seed, k) alone.  n == 0 launches nothing.
+ * M3D_ERR_INVALID: a mesh without a usable triangle, or none with a finite non-zero weight;
+ * n < 0 or n >= 2^31.  Synchronous. */
+int m3d_mesh_sample(m3d_ctx* ctx, m3d_mesh* mesh, int64_t n, uint64_t seed, double* points_out,
+                    int32_t* triangle_out, double* uv_out, double* normals_out, void* stream);
+/* out2 [host]: W and the number of triangles with a non-zero weight (0 0 before the first
+ * m3d_mesh_sample of the mesh). */
+int m3d_mesh_sample_info(const m3d_mesh* mesh, uint64_t* out2);
+
+/* ------------------------------------------------------------------ minimum-distance thinning (thin.hip)
+ * (added within ABI 13)  The points of a cloud kept by dart throwing in a hashed order: key_i =
+ * sample_base(seed, i), points ranked by (key_i, i); point i is kept iff no kept point j of lower
+ * rank has d²(i, j) < radius·radius, d² = ((dx·dx + dy·dy) + dz·dz) in fp64 on the original
+ * coordinates, strictly.  The kept points are original points, no two closer than radius, and every
+ * dropped point has a kept one strictly inside radius.  A point with a coordinate that is not
+ * finite is never kept and blocks nobody.  The result is unique (restated in numpy by
+ * tests/mesh_sample_restatement.py).
+ * decided_out [device] n int32: +k kept in round k, −k dropped in round k (k >= 1; never 0 on
+ * success).  *kept_count_out, *rounds_out [host], each may be NULL: the points kept and the rounds
+ * (launches) the call took — deterministic as well.  An empty cloud: nothing is touched, 0 and 0.
+ * M3D_ERR_INVALID: radius <= 0 or not finite.  M3D_ERR_HIP with a message: more than 256 rounds.
+ * Synchronous. */
+int m3d_thin_min_distance(m3d_ctx* ctx, const m3d_cloud* cloud, double radius, uint64_t seed, int32_t* decided_out,
+                          int64_t* kept_count_out, int32_t* rounds_out, void* stream);
+
 /* ------------------------------------------------------------------ ICP against a mesh (mesh_icp.hip)
  * registration_icp with the SURFACE of a triangle mesh as target (added within ABI 13, the version
  * number is unchanged): m3d_icp_run's loop — the transformed copy of the source, `init` applied
