@@ -3255,6 +3255,59 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4) {
   return M3D_OK;
 }
 
+// ------------------------------------------------------------------------------- ray casting
+// mesh_ray.hip; the two calls differ in their outputs alone (count_out null: the first hit)
+namespace {
+int mesh_rays(m3d_ctx* ctx, m3d_mesh* mesh, const double* rays, int64_t n, double tnear, double tfar, int32_t path,
+              double* t_out, int32_t* tri_out, double* uv_out, int32_t* count_out, void* stream, const char* what) {
+  CHECK_ARG(ctx, path >= 0 && path <= 2, "path: 0 automatic, 1 brute force, 2 grid");
+  CHECK_ARG(ctx, mesh->usable > 0, "the mesh has no usable triangle (none, or every one degenerate or not finite)");
+  const bool brute = path == 1 || (path == 0 && mesh->nf <= kMeshRayAutoBruteMax);
+  mesh->last_ray_path = brute ? 1 : 2;
+  mesh->last_ray_fallback = 0;
+  if (n == 0) return M3D_OK;
+  hipSetDevice(ctx->device);
+  hipStream_t st = S(stream);
+  Touch tch{ctx, st};
+  if (brute) {
+    HIPX(ctx, mesh_rays_brute(mesh, rays, n, tnear, tfar, t_out, tri_out, uv_out, count_out, st));
+    return M3D_OK;
+  }
+  char* scratch = nullptr;
+  const int rc = prep_buffer(ctx, 256, &scratch);
+  if (rc) return rc;
+  std::string why;
+  const hipError_t e = mesh_rays_grid(ctx, mesh, rays, n, tnear, tfar, t_out, tri_out, uv_out, count_out, scratch,
+                                      &mesh->last_ray_fallback, st, &why);
+  if (e != hipSuccess) return clean_fail(ctx, what, e, why);
+  return M3D_OK;
+}
+}  // namespace
+
+int m3d_mesh_cast_rays(m3d_ctx* ctx, m3d_mesh* mesh, const double* rays, int64_t n, double tnear, double tfar,
+                       int32_t path, double* t_out, int32_t* tri_out, double* uv_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, mesh && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || rays), "invalid arguments");
+  return mesh_rays(ctx, mesh, rays, n, tnear, tfar, path, t_out, tri_out, uv_out, nullptr, stream, "mesh_cast_rays");
+}
+
+int m3d_mesh_count_rays(m3d_ctx* ctx, m3d_mesh* mesh, const double* rays, int64_t n, double tnear, double tfar,
+                        int32_t path, int32_t* count_out, void* stream) {
+  if (!ctx) return M3D_ERR_INVALID;
+  CHECK_ARG(ctx, mesh && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (rays && count_out)), "invalid arguments");
+  return mesh_rays(ctx, mesh, rays, n, tnear, tfar, path, nullptr, nullptr, nullptr, count_out, stream,
+                   "mesh_count_rays");
+}
+
+int m3d_mesh_ray_info(const m3d_mesh* mesh, int64_t* out2) {
+  if (!mesh || !out2) return M3D_ERR_INVALID;
+  out2[0] = mesh->last_ray_path;
+  out2[1] = mesh->last_ray_fallback;
+  return M3D_OK;
+}
+
+int32_t m3d_mesh_ray_auto_brute_max(void) { return kMeshRayAutoBruteMax; }
+
 // ------------------------------------------------------------------------------- surface sampling
 // mesh_sample.hip; the cumulative weights are built by the first call and cached on the mesh
 namespace {

@@ -176,6 +176,13 @@ constexpr int kMeshAutoBruteMax = 960;
 // F = 256, 355 µs against 248–281 µs at F = 576; brute force grows by 0.58 µs per triangle and meets
 // the grid between F ≈ 370 (unseeded) and 420 (seeded)
 constexpr int kMeshIcpAutoBruteMax = 400;
+// m3d_mesh_cast_rays / m3d_mesh_count_rays path 0: brute force up to this many triangles, the grid
+// walk above.  Measured with 179,776 rays of a pinhole view (tools/mesh_ray_timing.py):
+// first hit, brute force 119 µs against the walk's 159 µs at F = 256, 239 µs against 212 µs at
+// F = 576; brute force grows by 0.38 µs per triangle, the walk by 0.17, and they meet at F ≈ 450.
+// The count walks the whole ray (no early stop) and meets brute force only at F ≈ 3,100; between
+// the two a count on path 0 is up to 1.9 × slower than path 1 (715 µs against 377 µs at F = 1,024).
+constexpr int kMeshRayAutoBruteMax = 448;
 
 // Device scratch for the temporaries of setup work (grid sorts, Morton copies, cloud packing):
 // grown on demand and owned by the context.  Setup work runs in stream order, so consecutive
@@ -405,6 +412,10 @@ struct m3d_mesh {
   int64_t nrefs = 0;
   int32_t doublings = 0;    // cell-size doublings of the build
   int32_t last_rounds = 0;  // ladder rounds of the last call (0: brute force)
+  // the last ray call (mesh_ray.hip): its path (0 none yet, 1 brute force, 2 grid) and how many of
+  // its rays took the whole-grid fallback
+  int32_t last_ray_path = 0;
+  int64_t last_ray_fallback = 0;
   // the sampling weights (mesh_sample.hip), built by the first m3d_mesh_sample and dropped with the
   // mesh: cum[f] = the sum of the integer weights of triangles 0..f, W = cum[nf − 1]
   bool sample_built = false;
@@ -840,6 +851,15 @@ hipError_t mesh_closest_grid(m3d_ctx* ctx, m3d_mesh* m, const double* xyz, int64
                              hipStream_t st, std::string* why);
 // the triangle grid of a mesh with usable triangles, built once (mesh.hip; synchronous)
 hipError_t mesh_grid_build(m3d_ctx* ctx, m3d_mesh* m, hipStream_t st, std::string* why);
+// ray casting (mesh_ray.hip).  rays [device] n×6 f64 (origin, direction).  count_out null: the first
+// hit into t_out / tri_out / uv_out (each may be null); otherwise the hit count alone.  Synchronous.
+// The grid call builds the mesh's grid on first use; scratch: 4 bytes; *fallback_out: the rays that
+// took the whole grid.
+hipError_t mesh_rays_brute(const m3d_mesh* m, const double* rays, int64_t n, double tnear, double tfar, double* t_out,
+                           int32_t* tri_out, double* uv_out, int32_t* count_out, hipStream_t st);
+hipError_t mesh_rays_grid(m3d_ctx* ctx, m3d_mesh* m, const double* rays, int64_t n, double tnear, double tfar,
+                          double* t_out, int32_t* tri_out, double* uv_out, int32_t* count_out, void* scratch,
+                          int64_t* fallback_out, hipStream_t st, std::string* why);
 // surface sampling (mesh_sample.hip).  mesh_sample_build: the cumulative integer weights of a mesh
 // with usable triangles, built once (synchronous; m->sample_W == 0 afterwards: no triangle has a
 // finite non-zero weight).  mesh_sample: enqueue only, n ≥ 0 samples of a built mesh with

@@ -4,7 +4,7 @@ Host layer (Python, ctypes) over libm3d.so, the HIP kernels behind the C ABI of
 ``include/m3d.h``.  See DESIGN.md for the path, the data layout and the kernels.
 """
 
-from . import _lib, synth  # noqa: F401
+from . import _lib, raycast, synth  # noqa: F401
 from .types import PointCloud, RegistrationResult  # noqa: F401
 
 __version__ = "0.1.0"

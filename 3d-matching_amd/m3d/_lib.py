@@ -246,6 +246,10 @@ SIGNATURES = {
     "m3d_thin_min_distance": (C.c_int, [vp, vp, dbl, u64, vp, C.POINTER(i64), C.POINTER(i32), vp]),
     "m3d_mesh_brute_tile": (i32, []),
     "m3d_mesh_auto_brute_max": (i32, []),
+    "m3d_mesh_cast_rays": (C.c_int, [vp, vp, vp, i64, dbl, dbl, i32, vp, vp, vp, vp]),
+    "m3d_mesh_count_rays": (C.c_int, [vp, vp, vp, i64, dbl, dbl, i32, vp, vp]),
+    "m3d_mesh_ray_info": (C.c_int, [vp, C.POINTER(i64)]),
+    "m3d_mesh_ray_auto_brute_max": (i32, []),
     "m3d_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "m3d_comm_init": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(vp)]),
     "m3d_comm_destroy": (None, [vp]),

@@ -11,12 +11,15 @@ What an Open3D user runs after registering a CAD model against a scan and its re
 | ``mesh.sample_points_uniformly(n)``                             | ``TriangleMesh.sample_points_uniformly``, ``sample_points`` |
 | ``mesh.sample_points_poisson_disk(n)``                          | ``TriangleMesh.sample_points_poisson_disk`` (dart throwing, not sample elimination) |
 | ``mesh.get_surface_area()``                                     | ``TriangleMesh.get_surface_area``      |
+| ``RaycastingScene.cast_rays`` / ``test_occlusions`` / ``count_intersections`` / ``compute_occupancy`` / ``compute_signed_distance`` | ``m3d.raycast.RaycastingScene`` (a subclass of the scene here), ``m3d.raycast.cast_rays``, ``virtual_scan`` |
 
 The contract is mesh.hip's (restated in numpy by tests/mesh_restatement.py): Ericson's closest point
 on a triangle in fp64 in one fixed operation order, the winner the smallest (d², triangle index)
 over every usable triangle.  Queries are float64 (n, 3); the arithmetic runs on the GPU, the brute
 force path and the grid path return the same bits.  Parity with Open3D itself is unpinned (Embree
-works in float32).  Ray casting, occupancy and signed distance (ray parity in Open3D) are not here.
+works in float32).  Ray casting, occupancy and signed distance (ray parity in Open3D) are in
+``m3d.raycast``, whose ``RaycastingScene`` extends the one here; the six ray methods of this
+module's scene stay stubs that say so.
 
 ``icp_to_mesh`` / ``icp_to_mesh_terms`` are mesh_icp.hip's loop and its one-evaluation hook
 (restated by tests/mesh_icp_restatement.py): point-to-plane ICP whose target is the closest point
@@ -446,22 +449,23 @@ class RaycastingScene:
         """(n,) float64: the distance to the closest triangle, sqrt of the contract's d²."""
         return np.sqrt(closest_points(self._scene(), _queries(query_points))["d2"])
 
-    # Open3D methods that need a ray caster, which this project does not have yet
+    # Open3D methods that need a ray caster: m3d.raycast.RaycastingScene, a subclass, has them
     def cast_rays(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.cast_rays: ray casting is not implemented")
+        raise NotImplementedError("RaycastingScene.cast_rays: use m3d.raycast.RaycastingScene")
 
     def test_occlusions(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.test_occlusions: ray casting is not implemented")
+        raise NotImplementedError("RaycastingScene.test_occlusions: use m3d.raycast.RaycastingScene")
 
     def count_intersections(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.count_intersections: ray casting is not implemented")
+        raise NotImplementedError("RaycastingScene.count_intersections: use m3d.raycast.RaycastingScene")
 
     def list_intersections(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.list_intersections: ray casting is not implemented")
+        raise NotImplementedError("RaycastingScene.list_intersections: not implemented (a variable-length "
+                                  "output; m3d.raycast has the other ray queries)")
 
     def compute_signed_distance(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.compute_signed_distance: the sign is ray parity in "
-                                  "Open3D and needs a ray caster")
+        raise NotImplementedError("RaycastingScene.compute_signed_distance: use m3d.raycast.RaycastingScene "
+                                  "(the sign is ray parity)")
 
     def compute_occupancy(self, *args, **kwargs):
-        raise NotImplementedError("RaycastingScene.compute_occupancy: needs a ray caster")
+        raise NotImplementedError("RaycastingScene.compute_occupancy: use m3d.raycast.RaycastingScene")

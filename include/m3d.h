@@ -950,6 +950,42 @@ int m3d_mesh_grid_info(const m3d_mesh* mesh, int64_t* out4);
 int32_t m3d_mesh_brute_tile(void);
 int32_t m3d_mesh_auto_brute_max(void);
 
+/* ------------------------------------------------------------------ ray casting (mesh_ray.hip)
+ * (added within ABI 13, the version number is unchanged)  Open3D
+ * t.geometry.RaycastingScene.cast_rays / count_intersections; occupancy and the sign of a signed
+ * distance are the parity of the count.  The contract (mesh_ray.h, restated in numpy by
+ * tests/mesh_ray_restatement.py), all in fp64, one operation at a time: a ray is (o, d); the test is
+ * the watertight test of Woop, Benthin and Wald (2013):
+ *   per ray       kz = the axis of the largest |d| (the lowest wins a tie), kx = (kz+1)%3,
+ *                 ky = (kx+1)%3, swapped when d[kz] < 0; Sx = d[kx]/d[kz], Sy = d[ky]/d[kz], Sz = 1/d[kz].
+ *   per triangle  A = a − o (B, C alike); Ax = A[kx] − Sx*A[kz], Ay = A[ky] − Sy*A[kz];
+ *                 U = Cx*By − Cy*Bx, V = Ax*Cy − Ay*Cx, W = Bx*Ay − By*Ax; miss if one of them is < 0
+ *                 and one > 0; det = (U+V)+W, miss if det == 0; Az = Sz*A[kz];
+ *                 t = ((U*Az + V*Bz) + W*Cz) / det; hit iff tnear <= t && t <= tfar;
+ *                 (u, v) = (V/det, W/det): point ≈ (1−u−v)·a + u·b + v·c.
+ * Both orientations hit; t is in units of d, which need not be normalised.  A ray with a component
+ * that is not finite or with d == 0 hits nothing; unusable triangles are skipped.  An edge value that
+ * is exactly zero counts for both triangles of the edge (a ray from the centre of a unit cube along
+ * +x, through a face diagonal, counts 2).  The brute-force path and the grid path (a walk of the
+ * triangle grid along the ray) return the same bits.
+ *
+ * rays [device] n×6 f64 (origin, direction).  path: 0 automatic, 1 brute force, 2 grid.
+ * m3d_mesh_cast_rays: the first hit, the smallest (t, triangle index); outputs [device], each may be
+ * NULL: t_out n f64 (+inf on a miss), tri_out n int32 (−1), uv_out n×2 f64 (NaN).
+ * m3d_mesh_count_rays: count_out [device] n int32, the usable triangles hit.
+ * M3D_ERR_INVALID: the mesh has no usable triangle, an unknown path.  n == 0 returns at once.
+ * Synchronous. */
+int m3d_mesh_cast_rays(m3d_ctx* ctx, m3d_mesh* mesh, const double* rays, int64_t n, double tnear, double tfar,
+                       int32_t path, double* t_out, int32_t* tri_out, double* uv_out, void* stream);
+int m3d_mesh_count_rays(m3d_ctx* ctx, m3d_mesh* mesh, const double* rays, int64_t n, double tnear, double tfar,
+                        int32_t path, int32_t* count_out, void* stream);
+/* out2 [host]: the path the last ray call of the mesh ran (1 brute force, 2 grid; 0 before the
+ * first), and how many of its rays took the whole-grid fallback (an origin farther than 2^18 times
+ * the mesh's largest coordinate, or outside fp32's range). */
+int m3d_mesh_ray_info(const m3d_mesh* mesh, int64_t* out2);
+/* the triangle count up to which path 0 of the two ray calls runs brute force */
+int32_t m3d_mesh_ray_auto_brute_max(void);
+
 /* ------------------------------------------------------------------ surface sampling (mesh_sample.hip)
  * (added within ABI 13, the version number is unchanged)  Open3D
  * TriangleMesh.sample_points_uniformly: n points drawn from the mesh's surface with probability
