@@ -1551,6 +1551,7 @@ int icp_reset(m3d_icp* s, const double* init, bool open3d_init, void* stream) {
   if (s->hcnt != nullptr) HIPX(ctx, hipMemsetAsync(s->hcnt, 0, kDeferWords * sizeof(uint32_t), st));
   HIPX(ctx, launch_icp_reset(s, T, apply_init_of(T, open3d_init), st));
   s->keys_clean = false;
+  s->points_moved = false;
   return M3D_OK;
 }
 }  // namespace
@@ -1612,6 +1613,7 @@ int m3d_icp_step(m3d_icp* s, void* stream) {
   // brute force: the fused tail hands the keys back as kKeyNone, the next NN seeds itself
   const bool reset = s->params.nn_method != M3D_NN_GRID && s->src->n > 0;
   const bool fused = fused_tail(s, reset);
+  s->points_moved = true;  // every path below enqueues a terms pass
   if (nn_terms_selected(nn_terms_sel(s, fused, reset))) {
     // the terms pass runs inside the NN launch, query block by query block; what is left is one
     // block: reduce, solve, plan (the M3D_KERNEL_TERMS events then time that block alone)
@@ -1655,7 +1657,7 @@ int capture_steps(m3d_icp* s, int32_t n) {
     s->cap_stream = nullptr;
     return M3D_ERR_HIP;
   }
-  const bool kc0 = s->keys_clean;
+  const bool kc0 = s->keys_clean, pm0 = s->points_moved;
   const int slot = kc0 ? 1 : 0;
   if (hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
     return M3D_ERR_HIP;
@@ -1665,6 +1667,7 @@ int capture_steps(m3d_icp* s, int32_t n) {
   const hipError_t ee = hipStreamEndCapture(s->cap_stream, &g);
   const bool kc1 = s->keys_clean;
   s->keys_clean = kc0;  // nothing ran yet
+  s->points_moved = pm0;
   hipGraphExec_t ex = nullptr;
   if (rc == M3D_OK && ee == hipSuccess && g != nullptr &&
       hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess) {
@@ -1709,6 +1712,7 @@ int m3d_icp_steps(m3d_icp* s, int32_t n, void* stream) {
     if ((have || again) && !s->graph_off) {
       HIPX(s->ctx, hipGraphLaunch(s->graph[slot], S(stream)));
       s->keys_clean = s->graph_kc_out[slot];
+      s->points_moved = true;
       return M3D_OK;
     }
   }
@@ -1762,6 +1766,7 @@ int m3d_icp_shard_terms(m3d_icp* s, int64_t off, const int64_t* dmin, const int3
   CHECK_ARG(ctx, claim != nullptr || off == 0, "a target shard (offset > 0) needs dmin and claim");
   hipStream_t st = S(stream);
   s->keys_clean = false;
+  s->points_moved = true;
   // keys kept inside (source shard): the fused tail hands them back as kKeyNone like m3d_icp_step
   const bool reset = claim == nullptr && s->src->n > 0 && s->params.nn_method != M3D_NN_GRID;
   if (fused_tail(s, reset)) {  // terms + fixed-order reduce in one launch (same bits as the two kernels)
@@ -1943,6 +1948,7 @@ int one_evaluation(m3d_icp* s, const double* T, bool open3d_init, Pass pass, int
   if (!rc) rc = icp_reset(s, T, open3d_init, st);
   if (rc) return rc;
   hipError_t e = enqueue_nn(s, 0, st);
+  s->points_moved = true;  // the pass is a terms pass
   if (e == hipSuccess) e = pass(n > 0 ? pin_read<double>(ctx, true) : nullptr);
   if (e == hipSuccess && corr_idx != nullptr) e = launch_scatter_i32(s->corr, s->src->slot, s->src->n, corr_idx, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -2131,6 +2137,7 @@ int run_terms_loop(m3d_icp* s, int32_t max_iteration, Terms terms, m3d_icp_resul
   const bool search = s->src->n > 0 && s->tgt->n > 0;  // else: no scan, zero sums, every source unmatched
   auto step = [&](int32_t k) {
     hipError_t e = hipSuccess;
+    if (k > 0) s->points_moved = true;
     for (int32_t it = 0; it < k && e == hipSuccess; ++it) {
       if (search) e = enqueue_nn(s, 0, st);
       if (e == hipSuccess) {
@@ -3027,6 +3034,7 @@ int m3d_ransac_on_correspondences(m3d_ctx* ctx, const m3d_cloud* src, const m3d_
     out->corres_ratio = corres_ratio;
     if (e == hipSuccess && corr_set_out) {
       e = launch_icp_set_T(s, T.p + 16 * best, st);
+      s->points_moved = true;  // set_T, then the terms pass below
       if (e == hipSuccess) e = enqueue_nn(s, 0, st);
       if (e == hipSuccess) e = launch_icp_terms_mode(s, 0, nullptr, nullptr, st);
       if (e == hipSuccess)
@@ -3539,6 +3547,11 @@ int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6) {
   if (!A36 || !b6 || !x6) return M3D_ERR_INVALID;
   if (!ldlt6_solve_spd(A36, b6, x6)) ldlt6_solve(A36, b6, x6);  // the device solve's rule (icp.hip)
   return M3D_OK;
+}
+
+int m3d_debug_rotation_from_cov_host(const double* H9, double* R9) {
+  if (!H9 || !R9) return M3D_ERR_INVALID;
+  return rotation_from_cov(H9, R9);
 }
 
 int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3) {

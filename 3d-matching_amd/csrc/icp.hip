@@ -1326,12 +1326,16 @@ hipError_t launch_icp_set_T(const m3d_icp* s, const double* T_dev, hipStream_t s
 // init is still in dT (pcd64 = the source): apply it as the evaluation will (q64_of, Eigen's
 // order) — RegistrationICP's pcd at that point is init·source — unless dT is exactly I
 // (init isIdentity(): Open3D leaves pcd untouched, and I·p could turn a −0 into +0).
+// moved: the host enqueued a terms pass since the reset (m3d_icp::points_moved) — that pass wrote
+// dT·pcd64 back, and until its solve runs evals is still 0 (the shard protocol's terms → all-reduce
+// → solve): the points are pcd64 as it stands.
 __global__ void copy_points_kernel(const IcpState* __restrict__ s, const double* __restrict__ v,
-                                   const int32_t* __restrict__ slot, int64_t n, double* __restrict__ dst) {
+                                   const int32_t* __restrict__ slot, int64_t n, double* __restrict__ dst,
+                                   int moved) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const int64_t o = (int64_t)slot[k];
-  bool apply = s->evals == 0;
+  bool apply = s->evals == 0 && !moved;
   if (apply) {
     bool eye = true;
     for (int e = 0; e < 16; ++e) eye = eye && s->dT[e] == ((e % 5) == 0 ? 1.0 : 0.0);
@@ -1349,7 +1353,8 @@ __global__ void copy_points_kernel(const IcpState* __restrict__ s, const double*
 hipError_t launch_copy_points(const m3d_icp* s, double* dst, hipStream_t st) {
   const int64_t n = s->src->n;
   if (n == 0) return hipSuccess;
-  copy_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s->state, s->pcd64, s->src->slot, n, dst);
+  copy_points_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s->state, s->pcd64, s->src->slot, n, dst,
+                                                                  s->points_moved ? 1 : 0);
   return hipGetLastError();
 }
 

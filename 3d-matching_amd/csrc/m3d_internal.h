@@ -455,6 +455,10 @@ struct m3d_icp {
   // source's extent (a spatial shard), whose queries' work sits in a few Morton ranges
   int32_t scan_xchunk = 0;
   bool keys_clean = false;         // host view: every key is kKeyNone (fused tail reset them)
+  // host view: a terms pass was enqueued since the last reset / set_T, so pcd64 already holds the
+  // init applied (the pass writes dT·pcd64 back before the solve counts the evaluation):
+  // m3d_icp_copy_points must not apply dT again.  Set by every entry that enqueues a terms pass.
+  bool points_moved = false;
   // brute-force NN slice plan (nn_plan.h, nn_brute.hip): per query block the tiles kept, the
   // counts the planner last read, the table of nn_budget entries; nn_qblocks = 0: no plan (grid
   // NN, or as many query blocks as resident block slots)

@@ -280,6 +280,7 @@ SIGNATURES = {
     "m3d_debug_xxh3_128": (C.c_int, [vp, C.c_size_t, C.POINTER(u64)]),
     "m3d_debug_kabsch3_host":(C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_ldlt6_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
+    "m3d_debug_rotation_from_cov_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_sym3_eigenvalues_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl)]),
     "m3d_debug_sym3_eigen_host": (C.c_int, [C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
 }

@@ -294,7 +294,9 @@ int m3d_icp_reset(m3d_icp* s, const double* init_host, void* stream);
 /* The loop's fp64 points of the last evaluation (the source after init and every update but the
  * one the evaluation produced), dst [device] ns×3 f64 in the caller's source order.  After a reset
  * and before the first evaluation: the source with the init applied exactly as RegistrationICP's
- * pcd.Transform(init) (the source itself when init isIdentity()).  ABI 12; init applied ABI 13. */
+ * pcd.Transform(init) (the source itself when init isIdentity()).  An evaluation counts from its
+ * terms pass on: between m3d_icp_shard_terms and m3d_icp_solve (the shard protocol) the points are
+ * already that evaluation's.  ABI 12; init applied ABI 13. */
 int m3d_icp_copy_points(const m3d_icp* s, double* dst, void* stream);
 /* One full iteration on one device: NN evaluation + estimation terms + solve/update. */
 int m3d_icp_step(m3d_icp* s, void* stream);
@@ -1071,6 +1073,10 @@ int m3d_mesh_icp_run(m3d_ctx* ctx, m3d_mesh* mesh, const m3d_cloud* src, const d
 int m3d_debug_kabsch3_host(const double* src9, const double* tgt9, double* T16);
 int m3d_debug_ldlt6_host(const double* A36, const double* b6, double* x6);  // the device solve's
                                                                        // rule: unpivoted, pivoted fallback
+/* linalg.h rotation_from_cov, compiled for the host: H9 row-major (H = Σ p qᵀ, p source, q target)
+ * → R9 row-major, the proper rotation mapping source to target; returns the rank it used (2 for
+ * rank ≥ 2, 1, 0 for H = 0, −1 for a non-finite H: then R = I; −1 for a null pointer too) */
+int m3d_debug_rotation_from_cov_host(const double* H9, double* R9);
 /* linalg.h sym3_eigenvalues, compiled for the host: sym6 = (a00, a01, a02, a11, a12, a22) → lam3 ascending */
 int m3d_debug_sym3_eigenvalues_host(const double* sym6, double* lam3);
 /* linalg.h sym3_eigen, compiled for the host: lam3 as above, V9 row-major, column k a unit eigenvector of lam3[k] */
