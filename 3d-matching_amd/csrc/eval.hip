@@ -8,7 +8,7 @@
 // points q = (x, y, z) in the target's original fp64 coordinates (m3d_cloud::xyz64 — GᵀG is not
 // translation invariant, so not the centred fp32 frame): Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz.
 // The host assembles the 6×6 GᵀG of the rows G₁ = (0, z, −y, 1, 0, 0), G₂ = (−z, 0, x, 0, 1, 0),
-// G₃ = (y, −x, 0, 0, 0, 1) from them (api.cpp eval_information).
+// G₃ = (y, −x, 0, 0, 0, 1) from them (api_icp.cpp eval_information).
 //
 // Order of summation: the loop's fixed order (icp.hip, "reduce"; nnkey.h block_partial per block
 // of 256 consecutive slots, launch_reduce over the block partials) — two runs, and the brute-force

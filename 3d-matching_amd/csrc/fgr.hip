@@ -17,7 +17,7 @@
 // memory, where the last block to finish (an integer ticket) runs level 2.  Both therefore return
 // the same bits, as does a launch of any shape.  No floating-point atomics anywhere.
 //
-// Stages (api.cpp m3d_fgr_*):
+// Stages (api_prep.cpp m3d_fgr_*):
 //   normalise  the two means in the order above, the largest centred norm by an integer atomic max
 //              on the bit pattern of the non-negative fp64 norms, then each correspondence row's
 //              two points centred and divided: (S[i] − m0) / g, (G[j] − m1) / g

@@ -977,7 +977,7 @@ hipError_t launch_grid_nn(const float4* src32, int64_t ns, const Grid* qgrid, co
   const int xchunk = xchunk_env >= 0 ? xchunk_env : std::max(0, xchunk_loop);
   const int64_t unit = 8 * (int64_t)std::max(xchunk, 1);
   const unsigned launch = (unsigned)((nb + unit - 1) / unit * unit);
-  // deferral of dense-cell and ambiguous queries to grid_nn_heavy_kernel (api.cpp icp_create)
+  // deferral of dense-cell and ambiguous queries to grid_nn_heavy_kernel (api_icp.cpp icp_create)
   const bool defer = hlist != nullptr && hcnt != nullptr && cand_cap > 0 && hcap > 0 && g->dev.ncells > 0 &&
                      src64 != nullptr && tgt64 != nullptr;
   const int cap = defer ? cand_cap : 0x7FFFFFFF;

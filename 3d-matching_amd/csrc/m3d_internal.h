@@ -219,7 +219,7 @@ void host_pipeline(int64_t n, const std::function<void(int64_t)>& fn, const std:
 // 256-B aligned carve-out of a TmpArena reservation
 inline size_t tmp_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Device block cache (api.cpp): the blocks of clouds, grids, Morton copies, target records and
+// Device block cache (api_ctx.cpp): the blocks of clouds, grids, Morton copies, target records and
 // MFMA tiles go back to a process-wide cache when their object dies, and a later allocation of
 // a size in [need, 2·need] takes one.  hipFree of a 2–5 MB block costs ≈ 160 µs on the box
 // (unmapping; tools/ubench_alloc.hip), which a caller registering many pairs paid on every call
@@ -318,7 +318,7 @@ struct m3d_ctx {
   size_t scratch_bytes = 0;
   int64_t* stats = nullptr;  // [8] device counters
   m3d::RansacState* rstate = nullptr;
-  // cross-stream ordering of the scratch/rstate users (api.cpp Arena)
+  // cross-stream ordering of the scratch/rstate users (api_internal.h Arena)
   hipEvent_t scratch_ev = nullptr;
   hipStream_t scratch_stream = nullptr;
   bool scratch_used = false;
@@ -327,19 +327,19 @@ struct m3d_ctx {
   void* pin = nullptr;
   void* pin_dev = nullptr;
   uint32_t* one_ticket = nullptr;  // device: last-block ticket of count_one_kernel (kept at 0)
-  // neighbour lists of the synchronous preprocessing calls (api.cpp prep_lists), grown on demand
+  // neighbour lists of the synchronous preprocessing calls (api_prep.cpp prep_lists), grown on demand
   void* prep = nullptr;
   size_t prep_bytes = 0;
   m3d::TmpArena tmp;  // setup temporaries (grids, Morton copies, cloud packing)
-  m3d::TmpArena run;  // loop arrays of the synchronous one-shot ICP / NN calls (api.cpp icp_create)
+  m3d::TmpArena run;  // loop arrays of the synchronous one-shot ICP / NN calls (api_icp.cpp icp_create)
   // streams this context enqueued work on, each with an event re-recorded at every such call
-  // (api.cpp ctx_touch): the release marks of the block cache wait for all of them on `order`
+  // (api_ctx.cpp ctx_touch): the release marks of the block cache wait for all of them on `order`
   std::vector<std::pair<hipStream_t, hipEvent_t>> uses;  // (pruned of completed entries per mark)
   std::mutex uses_mu;  // ctx_touch vs ReleaseScope (destroys may run on finaliser threads)
   bool uses_lost = false;  // an event could not be made: releases fall back to a device sync
   hipStream_t order = nullptr;
-  bool counted = false;  // counted among its device's live contexts (api.cpp ctx_count)
-  uint64_t id = 0;       // unique per process (api.cpp ctx_register)
+  bool counted = false;  // counted among its device's live contexts (api_ctx.cpp ctx_count)
+  uint64_t id = 0;       // unique per process (api_ctx.cpp ctx_register)
 };
 
 struct m3d_corrset {
@@ -383,7 +383,7 @@ struct m3d_cloud {
   mutable std::vector<std::pair<double, m3d_cloud*>> morton;
   int32_t* slot = nullptr;
   // a Morton copy: live ICP loops running on it (m3d_icp_create / _destroy); the parent keeps at
-  // most kMortonKeep copies and evicts the oldest unreferenced one beyond that (api.cpp)
+  // most kMortonKeep copies and evicts the oldest unreferenced one beyond that (api_cloud.cpp)
   mutable int refs = 0;
   bool orphan = false;  // a Morton copy whose parent was destroyed while loops still ran on it
   // one allocation holding the point arrays (Carve; m3d_cloud_destroy frees it, not them)
@@ -436,7 +436,7 @@ struct m3d_icp {
   const m3d_cloud* tgt = nullptr;
   m3d_icp_params params{};
   double max_dist = 0.0;
-  void* block = nullptr;           // device: one allocation holding the arrays below (api.cpp)
+  void* block = nullptr;           // device: one allocation holding the arrays below (api_icp.cpp)
   m3d::IcpState* state = nullptr;  // device
   int64_t* keys = nullptr;         // ns packed NN keys: k1 = (d2f, index) minimum of the scan
   uint32_t* near2 = nullptr;       // ns: bits of the smallest d2f of any other target evaluated
@@ -493,7 +493,7 @@ struct m3d_icp {
   int64_t* xdk = nullptr;   // ns: d64 keys, MIN-reduced
   int32_t* xcl = nullptr;   // ns: claims, MIN-reduced
   double* xsums = nullptr;  // kTermSlots, SUM-reduced
-  // m3d_icp_steps replays: an n-step sequence captured into a HIP graph (api.cpp), one slot per
+  // m3d_icp_steps replays: an n-step sequence captured into a HIP graph (api_icp.cpp), one slot per
   // keys_clean state on entry; a slot captures a sequence requested a second time
   hipStream_t cap_stream = nullptr;
   hipGraphExec_t graph[2] = {nullptr, nullptr};
@@ -590,7 +590,7 @@ hipError_t launch_ransac_shard_key(const m3d_ransac_result* r, int64_t hyp0, int
                                    hipStream_t st);
 hipError_t launch_ransac_shard_pack(const m3d_ransac_result* r, int64_t hyp0, int64_t* buf,
                                     hipStream_t st);
-// target-shard loop pieces (api.cpp): the NN + this shard's winners of source slots [q0, q1), and
+// target-shard loop pieces (api_icp.cpp): the NN + this shard's winners of source slots [q0, q1), and
 // whether the loop's NN can run on a slot range (grid NN with a Morton query grid; brute force always)
 int icp_shard_nn_range(m3d_icp* s, int64_t off, int64_t q0, int64_t q1, int64_t* dkeys, hipStream_t st);
 bool icp_nn_range_ok(const m3d_icp* s);

@@ -516,7 +516,7 @@ size_t segment_plane_scratch_bytes(int64_t n, int batch) { return SegScratch(n, 
 hipError_t segment_plane(const m3d_cloud* c, const m3d_plane_params* p, int batch, const int32_t* samples,
                          m3d_plane_result* out, int32_t* inliers_out, int32_t* counts_out, double* err_out,
                          void* scratch, hipStream_t st, int* bad_sample) {
-  const int64_t n = c->n;  // >= ransac_n >= 3 (api.cpp)
+  const int64_t n = c->n;  // >= ransac_n >= 3 (api_prep.cpp)
   const int64_t H = p->num_iterations;
   const int rn = p->ransac_n;
   const double thr = p->distance_threshold;

@@ -467,7 +467,7 @@ static void free_all(std::initializer_list<void*> ps) {
   for (void* p : ps) hipFree(p);
 }
 
-// Device scratch of voxel_down_sample for n points (the caller's buffer, api.cpp): block
+// Device scratch of voxel_down_sample for n points (the caller's buffer, api_prep.cpp): block
 // partials of the bounds, 64-bit keys (in / sorted / unique), indices (in / sorted), run counts,
 // offsets, the run count, and hipcub's temporary storage.
 namespace {
@@ -603,7 +603,7 @@ hipError_t hybrid_search(const m3d_cloud* c, const Grid* g, double radius, int k
     hybrid_search_wave_kernel<2><<<wb, 256, 0, st>>>(c->xyz64, c->xyz32, c->n, g->dev, Rf,
                                                      radius * radius, eabs, k, gfd, Hf, h2safe,
                                                      idx, d2, cnt);
-  } else {  // k ≤ 256 (api.cpp); hybrid_fine_radius gives no first stage above 128
+  } else {  // k ≤ 256 (api_prep.cpp); hybrid_fine_radius gives no first stage above 128
     hybrid_search_wave_kernel<4><<<wb, 256, 0, st>>>(c->xyz64, c->xyz32, c->n, g->dev, Rf,
                                                      radius * radius, eabs, k, gfd, Hf, h2safe,
                                                      idx, d2, cnt);

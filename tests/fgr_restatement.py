@@ -386,7 +386,7 @@ class Result:
 
 
 def original_scale(T, nz):
-    """O = (R, ((−R·m1) + g·t) + m0) and the returned O⁻¹ = (Rᵀ, −Rᵀ·o) (api.cpp's order)."""
+    """O = (R, ((−R·m1) + g·t) + m0) and the returned O⁻¹ = (Rᵀ, −Rᵀ·o) (api_prep.cpp's order)."""
     m0, m1 = nz.mean_src, nz.mean_tgt
     o = [((0.0 - ((T[i, 0] * m1[0] + T[i, 1] * m1[1]) + T[i, 2] * m1[2])) + nz.g * T[i, 3]) + m0[i] for i in range(3)]
     out = np.eye(4)

@@ -1,4 +1,4 @@
-"""The device block cache (api.cpp, ABI 12-13): stream-ordered reuse, trimming, and the
+"""The device block cache (api_ctx.cpp, ABI 12-13): stream-ordered reuse, trimming, and the
 cloud-before-loop destruction order."""
 import time
 

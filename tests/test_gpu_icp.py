@@ -252,7 +252,7 @@ def test_icp_result_update_and_points_api():
 
 def test_morton_copies_stay_bounded_per_cloud():
     """nn1 with many different radii on one cloud pair (round-3 ADVICE): the per-cloud Morton
-    source copies are capped (api.cpp kMortonKeep), results stay exact."""
+    source copies are capped (api_cloud.cpp kMortonKeep), results stay exact."""
     tgt, _ = synth.surface_points(4000, seed=4)
     src, _ = synth.surface_points(3000, seed=5)
     s, t = Cloud(src), Cloud(tgt)
@@ -726,7 +726,7 @@ def test_icp_cfg1_point_to_point_matches_oracle():
 def test_fused_tail_beyond_256_blocks_equals_separate():
     """Past 256 terms blocks the fused tail's last block reduces the partials in several batches
     (brute force keeps the fused form: it hands the keys back) and the grid loop switches to the
-    separate terms / reduce / solve launches (api.cpp fused_tail).  A subprocess with
+    separate terms / reduce / solve launches (api_icp.cpp fused_tail).  A subprocess with
     M3D_ICP_FUSED=0 (all separate) and one with the default give the same bits at 300k sources
     (587 blocks)."""
     import json
@@ -800,7 +800,7 @@ for nn in ("brute", "grid"):
     c = lp.correspondences().cpu().numpy()
     out[nn] = [r.transformation.tolist(), r.fitness, r.inlier_rmse, r.iterations, int(c.sum()), int((c >= 0).sum())]
     # the same 41 steps as captured HIP graphs: a sequence requested twice is captured, then
-    # replayed (api.cpp capture_steps) — the deferral list is used inside the graph too
+    # replayed (api_icp.cpp capture_steps) — the deferral list is used inside the graph too
     g = IcpLoop(s, t, 0.12, relative_fitness=-1, relative_rmse=-1, max_iteration=40, nn=nn)
     for _ in range(3):
         g.reset(synth.random_rigid(3, rot_range=0.03, trans_range=0.05))

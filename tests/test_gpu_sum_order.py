@@ -61,7 +61,7 @@ def device_sum(v):
 
 
 def information_of(m):
-    """api.cpp eval_information, restated: GᵀG from (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz)."""
+    """api_icp.cpp eval_information, restated: GᵀG from (count, Σd², Σx Σy Σz, Σx² Σy² Σz², Σxy Σxz Σyz)."""
     n, x, y, z, xx, yy, zz, xy, xz, yz = (m[k] for k in (0, 2, 3, 4, 5, 6, 7, 8, 9, 10))
     U = np.array([[yy + zz, 0.0 - xy, 0.0 - xz, 0.0, 0.0 - z, y],
                   [0.0, xx + zz, 0.0 - yz, z, 0.0, 0.0 - x],
